@@ -22,7 +22,21 @@ closed-loop dual-arm MPC tick, 3 CEM iterations over a global 8192 x 50 batch
 split over the ranks, graph replay) -- the strong-scaling curves beside the
 weak one.  --config c5 makes the C5 tick the line itself.
 
-    python bench.py [--gpus N --steps K --warmup W] [--config c2|c3|c4|c5] [--scaling strong] [--no-sub]
+A plain run does only what the headline figure needs: set-up, warm-up, the
+timed steps, --dump-outputs, the result line.  --full adds everything else
+the bench measures, each in runs of its own: the host-core baselines (fp32 /
+fp64 C restatement), the contact report (an untimed trace of the batch), the
+"strong" and "c5" sub-records, and, for --config c5, the eager timing of the
+rollout call behind its roofline (--no-cpu-baseline, --no-contact-report and
+--no-sub drop single parts of a --full run).
+
+--dump-outputs DIR writes what the last timed step left in the caller's
+buffers as DIR/<name>.npy (fp32 / fp64; <name>_rank<r>.npy with more than one
+rank; 64 MB in DIR at most, over all ranks, by a seeded row sample): same
+arguments, same inputs, so two builds compare output for output.
+
+    python bench.py [--gpus N --steps K --warmup W] [--config c2|c3|c4|c5] [--scaling strong] [--full [--no-sub]]
+                    [--dump-outputs DIR]
     torchrun --nproc-per-node N bench.py --gpus N ...
 """
 
@@ -287,6 +301,51 @@ def committed_counters(kind, sfx):
     return path, "committed 1-GPU profile of this build (" + os.path.relpath(path, ROOT) + ")"
 
 
+DUMP_BUDGET = 64 * 1000 * 1000  # --dump-outputs: bytes in DIR at most, over every file of every rank
+NPY_HEADER = 256  # bytes allowed for one .npy file's header (numpy writes 128 for these shapes)
+# compute_cem's 9-tuple (SBP/mjx_planner.py:364-406), the names of a --config c5 dump
+C5_OUTPUTS = ("best_cost", "best_cost_g", "best_cost_r", "best_cost_c", "best_vels", "best_traj", "xi_mean",
+              "thetadot", "theta")
+
+
+def dump_outputs(out_dir, arrays, rank=0, world=1):
+    """--dump-outputs: each array as <out_dir>/<name>.npy (floating arrays as
+    fp32 / fp64 as they are, integer ones as fp64; <name>_rank<r>.npy with
+    more than one rank).  DUMP_BUDGET bounds everything written to out_dir:
+    each rank has DUMP_BUDGET / world bytes for its files, headers and row
+    numbers included.  A rank whose arrays exceed that keeps, of every array
+    above 1/16 of its share, a fixed, seeded, sorted sample of the rows (the
+    kept row numbers as <name>_rows.npy).  Returns the bytes it wrote."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrs = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        arrs[name] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+    share = DUMP_BUDGET // world
+    sfx = "" if world == 1 else f"_rank{rank}"
+    frac = 1.0
+    if sum(a.nbytes + NPY_HEADER for a in arrs.values()) > share:
+        big = [a for a in arrs.values() if a.ndim >= 1 and a.nbytes > share // 16]
+        # a sampled array costs two headers and 8 bytes of row number per kept row
+        fixed = sum(a.nbytes + NPY_HEADER for a in arrs.values()) - sum(a.nbytes for a in big) + NPY_HEADER * len(big)
+        frac = (share - fixed) / sum(a.nbytes + 8 * a.shape[0] for a in big) if big else 0.0
+        if frac <= 0:
+            raise SystemExit(f"--dump-outputs: {len(arrs)} arrays do not fit {share} bytes")
+    written = 0
+    for name, a in arrs.items():
+        files = {name: a}
+        if frac < 1.0 and a.ndim >= 1 and a.nbytes > share // 16:
+            keep = int(a.shape[0] * frac)
+            rows = np.sort(np.random.default_rng(20250629).choice(a.shape[0], keep, replace=False))
+            files = {name: a[rows], name + "_rows": rows.astype(np.float64)}
+        for fname, x in files.items():
+            path = os.path.join(out_dir, f"{fname}{sfx}.npy")
+            np.save(path, np.ascontiguousarray(x))
+            written += os.path.getsize(path)
+    assert written <= share, (written, share)
+    return written
+
+
 def synthetic_xi(n, H, seed):
     """The bench's synthetic candidates: xi ~ N(0, 10.003 I), 10-iteration ADMM
     projection (host, before any timing)."""
@@ -367,14 +426,15 @@ def strong_subrecord(eng, dev, rank, world, H, steps, warmup, n_global=4096):
             "best": {"index": idx, "cost": best}}
 
 
-def c5_run(rank, world, gpu, dev, n_global, H, iters, ticks, warmup, capture_exchange):
+def c5_run(rank, world, gpu, dev, n_global, H, iters, ticks, warmup, capture_exchange, kernel_timing=True):
     """C5 (BASELINE configs[4]): closed-loop MPC ticks on the dual-arm scene.
     A tick = compute_cem (SBP/mjx_planner.py:364-406: `iters` CEM iterations
     over the global batch, each rank its n_global / world share, sampling
     keyed by the global index, elites exchanged; the iterations replayed from
     HIP graphs) + the plant step with the mean of best_vels[1:H-2]
     (SBP/mpc_planner.py:151-233, headless).  Returns the timing and, for the
-    roofline, the rollout call timed eagerly on the last tick's samples."""
+    roofline (kernel_timing, runs of its own after the timed ticks), the
+    rollout call timed eagerly on the last tick's samples."""
     import torch
     import torch.distributed as dist
 
@@ -407,7 +467,7 @@ def c5_run(rank, world, gpu, dev, n_global, H, iters, ticks, warmup, capture_exc
     n = p.n_local
     st = torch.zeros(n, dtype=torch.int32, device=dev)
     kms = []
-    for k in range(ticks + 1):
+    for k in range(ticks + 1 if kernel_timing else 0):
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record()
         p.engine.rollout_cost_dp(p._xf, MPCR_LAYOUT_XI, p._par, p._costs[0], theta=p._theta[0],
@@ -417,10 +477,10 @@ def c5_run(rank, world, gpu, dev, n_global, H, iters, ticks, warmup, capture_exc
         if k:
             kms.append(a.elapsed_time(b))
     out = state["out"]
-    nefc_mean = float((st >> 11).double().mean().item()) / H
+    nefc_mean = float((st >> 11).double().mean().item()) / H if kernel_timing else None
     return {"elapsed": elapsed, "tick_ms": tick_ms, "tick_ms_each": [round(x, 3) for x in tick_each],
-            "kernel_ms": float(np.median(kms)), "n_local": n,
-            "nefc_mean": nefc_mean, "model": p.model, "engine": p.engine,
+            "kernel_ms": float(np.median(kms)) if kernel_timing else None, "n_local": n,
+            "nefc_mean": nefc_mean, "model": p.model, "engine": p.engine, "out": out,
             "best_cost": [float(x) for x in np.asarray(out[0])],
             "best_cost_grc": [float(out[1]), float(out[2]), float(out[3])],
             "eef_dist": float(np.linalg.norm(plant.site_xpos_tcp - np.asarray(PT))),
@@ -478,7 +538,7 @@ def main_c5(args, cfg):
     rank, world, local = md.env_rank()
     n_global, H, iters = args.n or cfg["n"], args.horizon or cfg["H"], cfg["iters"]
     cpu_rec = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # the scalar C restatement on host cores, a bounded sample of the
         # workload's rollouts (the dual arm is ~100x C3's CPU cost per rollout)
         usable, ncpu, model, aff, quota = _host_cpu()
@@ -494,12 +554,26 @@ def main_c5(args, cfg):
                    "reps": reps, "host": {"usable_cores": usable, "affinity_cores": aff, "cgroup_cpu_quota": quota,
                                           "nproc": ncpu, "cpu_model": model}}
     gpu, dev, ndev, backend = init_device(args, world, local)
-    r = c5_run(rank, world, gpu, dev, n_global, H, iters, args.steps, args.warmup, args.c5_capture_exchange)
+    r = c5_run(rank, world, gpu, dev, n_global, H, iters, args.steps, args.warmup, args.c5_capture_exchange,
+               kernel_timing=args.full)
+    if args.dump_outputs:
+        # compute_cem's 9-tuple of the last timed tick, as the caller receives it
+        # (return_rollouts=False: its thetadot / theta members are None)
+        dump_outputs(args.dump_outputs, {k: x for k, x in zip(C5_OUTPUTS, r["out"]) if x is not None}, rank, world)
     if rank == 0:
         coll = {"nccl": "RCCL (xGMI)", "gloo": "gloo (host-staged)"}.get(backend, str(backend))
-        fps = flops_per_step(r["model"], r["nefc_mean"], "dual_arm")
-        achieved_tf = fps * H * r["n_local"] / (r["kernel_ms"] * 1e-3) / 1e12
-        hbm_launch = r["n_local"] * (66 * 4 + 16 + 2 * 6 * H * 4 + 4)
+        roofline = None
+        if args.full:
+            fps = flops_per_step(r["model"], r["nefc_mean"], "dual_arm")
+            achieved_tf = fps * H * r["n_local"] / (r["kernel_ms"] * 1e-3) / 1e12
+            hbm_launch = r["n_local"] * (66 * 4 + 16 + 2 * 6 * H * 4 + 4)
+            roofline = {"bound": "valu", "achieved": round(achieved_tf, 3), "peak": PEAK_F32_VALU_TFLOPS,
+                        "unit": "TFLOP/s", "frac": round(achieved_tf / PEAK_F32_VALU_TFLOPS, 5), "traffic": None,
+                        "traffic_source": "not profiled in this run", "kernel": "rollout_kernel",
+                        "kernel_ms": round(r["kernel_ms"], 4),
+                        "kernel_timing": "the rank's rollout call on the last tick's samples, eager, HIP events "
+                                         "(graph replays are timed whole)",
+                        "flops_per_step": fps, "hbm_algorithmic_bytes": hbm_launch}
         rec = {
             "metric": METRIC, "value": round(n_global * iters * args.steps / r["elapsed"], 1), "unit": "rollouts/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -515,15 +589,10 @@ def main_c5(args, cfg):
                        "exchange": "none (one rank)" if world == 1 else
                        f"local top-E + {coll} all-gather of (xi, cost) rows + global top-E per iteration; "
                        f"best key MIN all-reduce + broadcast of the best row per tick"},
-            "roofline": {"bound": "valu", "achieved": round(achieved_tf, 3), "peak": PEAK_F32_VALU_TFLOPS,
-                         "unit": "TFLOP/s", "frac": round(achieved_tf / PEAK_F32_VALU_TFLOPS, 5), "traffic": None,
-                         "traffic_source": "not profiled in this run", "kernel": "rollout_kernel",
-                         "kernel_ms": round(r["kernel_ms"], 4),
-                         "kernel_timing": "the rank's rollout call on the last tick's samples, eager, HIP events "
-                                          "(graph replays are timed whole)",
-                         "flops_per_step": fps, "hbm_algorithmic_bytes": hbm_launch},
+            "roofline": roofline,
             "best": {"cost_per_iteration": r["best_cost"], "cost_grc": r["best_cost_grc"]},
-            "eef_dist_after": r["eef_dist"], "mean_constraint_rows": round(r["nefc_mean"], 2),
+            "eef_dist_after": r["eef_dist"],
+            "mean_constraint_rows": None if r["nefc_mean"] is None else round(r["nefc_mean"], 2),
             "ticks": {"timed": args.steps, "warmup": args.warmup, "ms_each": r["tick_ms_each"],
                       "note": "consecutive closed-loop ticks: each starts from the plant state the previous left"},
         }
@@ -556,15 +625,20 @@ def main():
     ap.add_argument("--cpu-sample", type=int, default=0, help="candidates timed on the host (0 = the whole batch)")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="0 = every usable host core (affinity mask capped by the cgroup CPU quota)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-contact-report", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need, in runs of their own: host-core "
+                         "baselines, contact report, the strong / C5 sub-records, c5's eager kernel timing")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the host-core baselines")
+    ap.add_argument("--no-contact-report", action="store_true", help="--full without the contact report")
     ap.add_argument("--pmc", default=None, help="rocprofv3 FETCH/WRITE CSV of this workload")
     ap.add_argument("--pmc-sq", default=None, help="rocprofv3 SQ counter CSV of this workload")
     ap.add_argument("--backend", choices=("nccl", "gloo"), default="nccl",
                     help="N > 1: nccl (= RCCL over xGMI, one GPU per rank) or gloo (host-staged; ranks may share "
                          "a GPU, device = local rank mod the visible GPUs: rehearses the multi-rank path on one GPU)")
     ap.add_argument("--no-sub", action="store_true",
-                    help="default line only: skip the strong (C3 4096 global) and C5 sub-records")
+                    help="--full without the strong (C3 4096 global) and C5 sub-records of the default line")
     ap.add_argument("--c5-capture-exchange", action="store_true",
                     help="c5: capture the RCCL elite all-gathers in the tick's graph (default: eager between replays)")
     ap.add_argument("--launch-selftest", action="store_true", help=argparse.SUPPRESS)
@@ -609,7 +683,7 @@ def main():
     xi_all = synthetic_xi(n_draw, H, 20250629 + 3 + (0 if args.scaling == "strong" else rank))
     xi_host = xi_all[base:base + n] if args.scaling == "strong" else xi_all
     cpu_rec = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # host-core baseline before the process initialises the GPU
         usable, ncpu, model, aff, quota = _host_cpu()
         threads = args.cpu_threads or usable
@@ -678,9 +752,17 @@ def main():
     idx, best = md.decode_key(int(key.item()))
     trunc = int((status & 1).sum().item())
     nefc_mean = float((status >> 11).double().mean().item()) / H
+    if args.dump_outputs:
+        # the caller's buffers as the last timed step left them (before the
+        # --full sub-records run anything else on this engine)
+        outs = {"cost4": cost4.cpu().numpy(), "theta": theta.cpu().numpy(), "thetadot": thetadot.cpu().numpy(),
+                "status": status.cpu().numpy(), "best": np.array([idx, best], dtype=np.float64)}
+        if "cost" in elites:
+            outs["elite_cost"] = elites["cost"].cpu().numpy()
+        dump_outputs(args.dump_outputs, outs, rank, world)
 
     contact = None
-    if rank == 0 and not args.no_contact_report and m.nslot:
+    if args.full and rank == 0 and not args.no_contact_report and m.nslot:
         # SURVEY §8d asks whether contacts activate (C2 "no contacts"): the
         # masked robot slots of this batch, traced outside the timed region
         tr = eng.trace(xi_host.numpy(), MPCR_LAYOUT_XI, Q0, W, PT, QT)
@@ -692,7 +774,7 @@ def main():
     # the default line (C3, weak) also carries the strong-scaling reading of
     # the same ranks and the C5 tick
     subs = {}
-    if args.config == "c3" and args.scaling == "weak" and args.n == cfg["n"] and not args.no_sub:
+    if args.full and args.config == "c3" and args.scaling == "weak" and args.n == cfg["n"] and not args.no_sub:
         subs["strong"] = strong_subrecord(eng, dev, rank, world, H, args.steps, args.warmup)
         subs["c5"] = c5_subrecord(rank, world, gpu, dev, min(args.steps, 5), 2)
 

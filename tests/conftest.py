@@ -7,7 +7,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-REFERENCE = "/root/reference"
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 
@@ -15,8 +14,31 @@ def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs an MI355X (gfx950); run with -m gpu")
 
 
-def has_reference():
-    return os.path.isdir(os.path.join(REFERENCE, "sampling_based_planner"))
+@pytest.fixture(scope="session")
+def mjcf_scenes(tmp_path_factory):
+    """The MJCF scenes the bundles were compiled from (tests/golden/mjcf: the
+    .xml files and, xz-compressed, the meshes they load), unpacked into a
+    temporary directory with their own layout; returns that directory."""
+    import lzma
+    import shutil
+    src = os.path.join(GOLDEN, "mjcf")
+    dst = str(tmp_path_factory.mktemp("mjcf"))
+    for d, _, files in os.walk(src):
+        out = os.path.join(dst, os.path.relpath(d, src))
+        os.makedirs(out, exist_ok=True)
+        for f in files:
+            with open(os.path.join(d, f), "rb") as fh:
+                data = fh.read()
+            if f.endswith(".xz"):
+                f, data = f[:-3], lzma.decompress(data)
+            with open(os.path.join(out, f), "wb") as fh:
+                fh.write(data)
+    # the planner scene loads the same two Hand-E meshes from a folder of its own: stored once
+    hande = os.path.join(dst, "sampling_based_planner", "ur5e_hande_mjx", "assets", "hande")
+    os.makedirs(hande)
+    for f in ("coupler.stl", "hande.stl"):
+        shutil.copy(os.path.join(dst, "universal_robots_ur5e", "assets", "hande", f), hande)
+    return dst
 
 
 @pytest.fixture(scope="session")

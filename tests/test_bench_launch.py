@@ -52,3 +52,33 @@ def test_parent_does_not_import_torch():
     assert "\nimport torch" not in head and "\nfrom torch" not in head
     body = src.split("def main():")[1]
     assert body.index("launch_ranks(") < body.index("import torch")
+
+
+def test_dump_outputs_keeps_types_and_budget(tmp_path, monkeypatch):
+    """--dump-outputs: fp32 / fp64 stay, integers become fp64, and a dump over
+    the byte budget keeps the same seeded, sorted row sample on every call."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(0)
+    arrays = {"a": rng.normal(size=(1000, 8)).astype(np.float32), "s": np.arange(1000, dtype=np.int32),
+              "k": np.array([3, 1.5])}
+    bench.dump_outputs(str(tmp_path / "all"), arrays)
+    got = {f[:-4]: np.load(tmp_path / "all" / f) for f in os.listdir(tmp_path / "all")}
+    assert sorted(got) == ["a", "k", "s"]
+    assert got["a"].dtype == np.float32 and got["s"].dtype == np.float64 and got["k"].dtype == np.float64
+    assert (got["a"] == arrays["a"]).all() and (got["s"] == arrays["s"]).all()
+    # the budget bounds the folder: every file of every rank, headers and row numbers included
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 8000)
+    for d in ("x", "y"):
+        for r in (0, 1):
+            bench.dump_outputs(str(tmp_path / d), arrays, rank=r, world=2)
+    assert sum(os.path.getsize(tmp_path / "x" / f) for f in os.listdir(tmp_path / "x")) <= 8000
+    x = {f[:-4]: np.load(tmp_path / "x" / f) for f in os.listdir(tmp_path / "x")}
+    y = {f[:-4]: np.load(tmp_path / "y" / f) for f in os.listdir(tmp_path / "y")}
+    assert sorted(x) == sorted(f"{n}_rank{r}" for n in ("a", "a_rows", "k", "s", "s_rows") for r in (0, 1))
+    assert (x["k_rank1"] == arrays["k"]).all()
+    rows = x["a_rows_rank1"].astype(int)
+    assert len(rows) > 0 and (np.diff(rows) > 0).all() and (x["a_rank1"] == arrays["a"][rows]).all()
+    assert (x["s_rank1"] == arrays["s"][x["s_rows_rank1"].astype(int)]).all()
+    assert all((x[k] == y[k]).all() for k in x)

@@ -10,7 +10,6 @@ import numpy as np
 import pytest
 
 import oracle
-from conftest import REFERENCE, has_reference
 from manipulator_mujoco_amd import basis, cmodel, mjcf, models
 
 
@@ -75,9 +74,8 @@ def test_connect_anchors_coincide_at_qpos0(dual):
         np.testing.assert_allclose(p1, p2, atol=1e-12)
 
 
-@pytest.mark.skipif(not has_reference(), reason="needs /root/reference MJCF")
-def test_dual_bundle_is_current():
-    m = mjcf.compile_mjcf(os.path.join(REFERENCE, "universal_robots_ur5e/dual_arm_gripper_scene.xml"), 0.05)
+def test_dual_bundle_is_current(mjcf_scenes):
+    m = mjcf.compile_mjcf(os.path.join(mjcf_scenes, "universal_robots_ur5e/dual_arm_gripper_scene.xml"), 0.05)
     assert m.to_blob() == models.load("dual_arm", 0.05).to_blob()
 
 

@@ -85,7 +85,7 @@ def test_bench_self_launch_two_ranks_equal_one_gpu():
     assert two["elites"]["first"] == one["elites"]["first"]
 
 
-SUB = ["--config", "c3", "--candidates", "4096", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+SUB = ["--config", "c3", "--candidates", "4096", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
        "--no-contact-report"]
 
 
@@ -110,11 +110,47 @@ def test_bench_default_line_carries_strong_and_c5_at_two_ranks():
     assert two["c5"]["best_cost"] == one["c5"]["best_cost"], (one["c5"], two["c5"])
 
 
-def test_bench_c5_line():
+def test_bench_c5_line(tmp_path):
     """--config c5: the closed-loop tick as the line (strong scaling), the
-    rollout kernel's roofline from an eager call of the rank's share."""
-    rec = _run([sys.executable, "bench.py", "--config", "c5", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"])
+    rollout kernel's roofline from an eager call of the rank's share, and
+    --dump-outputs: the last tick's compute_cem tuple under its members'
+    names (the rollouts the bench's planner does not return are left out)."""
+    import numpy as np
+    rec = _run([sys.executable, "bench.py", "--config", "c5", "--steps", "2", "--warmup", "1", "--full",
+                "--no-cpu-baseline", "--dump-outputs", str(tmp_path)])
+    out = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert sorted(out) == ["best_cost", "best_cost_c", "best_cost_g", "best_cost_r", "best_traj", "best_vels",
+                           "xi_mean"]
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in out.values())
+    assert out["best_vels"].shape == out["best_traj"].shape == (50, 6) and out["xi_mean"].shape == (66,)
+    assert [float(x) for x in out["best_cost"]] == rec["best"]["cost_per_iteration"]
+    assert [float(out[k].reshape(-1)[0]) for k in ("best_cost_g", "best_cost_r", "best_cost_c")] == \
+        rec["best"]["cost_grc"]
     assert rec["scaling"] == "strong" and rec["config"]["global_batch"] == 8192
     assert rec["config"]["cem_iters"] == 3 and len(rec["best"]["cost_per_iteration"]) == 3
     assert rec["roofline"]["kernel_ms"] > 0 and 0 < rec["roofline"]["frac"] < 1
     assert abs(rec["value"] - 8192 * 3 * 2 / (2 * rec["ms_per_step"] * 1e-3)) < 0.01 * rec["value"]
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) carries the headline fields and none of the
+    extra measurements; --dump-outputs writes the caller's buffers of the last
+    timed step as fp32 / fp64 .npy files that agree with the line's best."""
+    import numpy as np
+    n, H = 4096, 50  # the default size: the only one at which --full attaches the strong / c5 sub-records
+    rec = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1",
+                "--dump-outputs", str(tmp_path)])
+    assert rec["config"]["candidates_per_gpu"] == n
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in rec, k
+    assert rec["steps"] == 2 and rec["ms_per_step"] > 0 and rec["unit"] == "rollouts/s" and rec["dtype"] == "f32"
+    assert abs(rec["value"] - n * 2 / (2 * rec["ms_per_step"] * 1e-3)) < 0.01 * rec["value"]
+    for k in ("cpu_baseline", "contacts", "strong", "c5"):
+        assert k not in rec, k
+    out = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert sorted(out) == ["best", "cost4", "status", "theta", "thetadot"]
+    assert out["cost4"].shape == (n, 4) and out["theta"].shape == out["thetadot"].shape == (n, 6 * H)
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values())
+    assert all(np.isfinite(a).all() for a in out.values())
+    assert int(out["best"][0]) == rec["best"]["index"] == int(np.argmin(out["cost4"][:, 0]))
+    assert np.float32(out["best"][1]) == out["cost4"][rec["best"]["index"], 0]

@@ -7,7 +7,6 @@ import numpy as np
 import pytest
 
 import oracle
-from conftest import REFERENCE, has_reference
 from manipulator_mujoco_amd import cmodel, mjcf, models
 
 SCENES = {
@@ -56,10 +55,9 @@ def test_planner_constants(planner_model):
     assert m.names["site"][m.tcp_site] == "tcp"
 
 
-@pytest.mark.skipif(not has_reference(), reason="needs /root/reference MJCF")
 @pytest.mark.parametrize("name", list(SCENES))
-def test_bundle_is_current(name):
-    m = mjcf.compile_mjcf(os.path.join(REFERENCE, SCENES[name]), 0.05)
+def test_bundle_is_current(name, mjcf_scenes):
+    m = mjcf.compile_mjcf(os.path.join(mjcf_scenes, SCENES[name]), 0.05)
     assert m.to_blob() == models.load(name, 0.05).to_blob()
 
 

@@ -24,7 +24,7 @@ if [[ $STEPS == all || $STEPS == *smoke* ]]; then
   run smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
 fi
 if [[ $STEPS == all || $STEPS == *bench* ]]; then
-  run bench 600 python bench.py
+  run bench 600 python bench.py --full
   grep '^{' $OUT/bench.log > $OUT/bench_${TAG}.json || true
 fi
 if [[ $STEPS == all || $STEPS == *prof* ]]; then

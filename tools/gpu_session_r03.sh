@@ -61,10 +61,10 @@ if [[ $STEPS == *micro* ]]; then
   run micro_valu 60 /tmp/valu_rate
 fi
 if [[ $STEPS == *bench* ]]; then
-  run bench_c3 300 python bench.py
-  run bench_c2 300 python bench.py --config c2
-  run bench_c4 300 python bench.py --config c4 --no-cpu-baseline --steps 5 --warmup 1
-  run bench_c3_strong 300 python bench.py --scaling strong --no-cpu-baseline
+  run bench_c3 300 python bench.py --full
+  run bench_c2 300 python bench.py --config c2 --full
+  run bench_c4 300 python bench.py --config c4 --no-cpu-baseline --steps 5 --warmup 1 --full
+  run bench_c3_strong 300 python bench.py --scaling strong --no-cpu-baseline --full
 fi
 if [[ $STEPS == *prof* ]]; then
   run prof 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run -- python3 bench.py --no-cpu-baseline --no-contact-report --steps 10 --warmup 2

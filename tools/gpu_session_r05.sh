@@ -39,12 +39,12 @@ if has mrank; then
   run mrank 400 $PYT tests/test_gpu_bench.py
 fi
 if has bench; then
-  run bench_c3 300 python bench.py
+  run bench_c3 300 python bench.py --full
 fi
 if has benchall; then
-  run bench_c2 300 python bench.py --config c2
-  run bench_c4 300 python bench.py --config c4 --no-cpu-baseline --steps 5 --warmup 1
-  run bench_c5 300 python bench.py --config c5 --no-cpu-baseline --steps 5 --warmup 2
+  run bench_c2 300 python bench.py --config c2 --full
+  run bench_c4 300 python bench.py --config c4 --no-cpu-baseline --steps 5 --warmup 1 --full
+  run bench_c5 300 python bench.py --config c5 --no-cpu-baseline --steps 5 --warmup 2 --full
 fi
 if has phase; then  # needs libmpcr_prof.so (python tools/phase_profile.py --build, CPU container)
   N=1024 H=50 run phase_dual_1024x50 200 python tools/phase_profile.py dual_arm $OUT/phase_dual_1024x50.json

@@ -34,7 +34,7 @@ if has quick; then  # round-6 changes: ABI v3 status word, the 30-tick C5 loop
   MPCR_PARITY_LOG=$OUT/parity_quick.jsonl run quick 900 $PYT -s tests/test_gpu_planner.py::test_dual_arm_c5_thirty_ticks "tests/test_gpu_parity.py::test_two_wave_variant_is_bitwise_one_wave" tests/test_gpu_parity.py::test_two_wave_dual_arm_flush_paths_bitwise tests/test_gpu_parity.py::test_dual_arm_c4_properties tests/test_gpu_parity.py::test_dual_arm_parity_to_conditioning tests/test_lib.py
 fi
 if has c5ticks; then  # BASELINE configs[4]: 30 closed-loop ticks
-  run bench_c5_30 400 python bench.py --config c5 --no-cpu-baseline --ticks 30 --warmup 1
+  run bench_c5_30 400 python bench.py --config c5 --no-cpu-baseline --ticks 30 --warmup 1 --full
 fi
 if has c5share; then  # the C5 tick's stages at one rank's share on 8 GPUs
   run c5_share_stages 300 python tools/c5_share_stages.py
@@ -48,12 +48,12 @@ if has mrank; then
   run mrank 400 $PYT tests/test_gpu_bench.py
 fi
 if has bench; then
-  run bench_c3 300 python bench.py
+  run bench_c3 300 python bench.py --full
 fi
 if has benchall; then
-  run bench_c2 300 python bench.py --config c2
-  run bench_c4 300 python bench.py --config c4 --no-cpu-baseline --steps 5 --warmup 1
-  run bench_c5 300 python bench.py --config c5 --no-cpu-baseline --steps 5 --warmup 2
+  run bench_c2 300 python bench.py --config c2 --full
+  run bench_c4 300 python bench.py --config c4 --no-cpu-baseline --steps 5 --warmup 1 --full
+  run bench_c5 300 python bench.py --config c5 --no-cpu-baseline --steps 5 --warmup 2 --full
 fi
 if has phase; then  # needs libmpcr_prof.so (python tools/phase_profile.py --build, CPU container)
   N=1024 H=50 run phase_dual_1024x50 200 python tools/phase_profile.py dual_arm $OUT/phase_dual_1024x50.json
