@@ -20,20 +20,28 @@ CSRC = os.path.join(HERE, "csrc")
 # and is allowed to reassociate fp32 (-fassociative-math needs no signed zeros
 # and no trapping; NaN / Inf semantics stay): 2.29 -> 2.25 ms, parity unchanged.
 # The CEM TU does not get it (top-k orders -0 before +0 like the reference).
-# rollout.hip is compiled twice: MPCR_TU=1, the single-arm kernels and the
-# launch logic, with those flags; MPCR_TU=2, the dual-arm kernels, with the
-# fast-math device flags dropped (_drop_fast: IEEE division / square root, no
-# reassociation) -- the latency-bound dual arm pays ~5 % (C4 45.9 -> 48.3 ms)
-# and its rollouts keep within the fp32 restatement's drift (C4 shard
-# well-conditioned misses 22 -> 8); the VALU-bound C3 would pay 16 %.
+# The rollout kernel (rollout.hip, device code only) is built in two units that
+# include it: rollout_narrow.hip, the single-arm kernels and the launch logic,
+# with those flags; rollout_wide.hip,
+# the dual-arm kernels, precise -- the fast-math device flags dropped
+# (_drop_fast: IEEE division / square root, no reassociation): the
+# latency-bound dual arm pays ~5 % (C4 45.9 -> 48.3 ms) and its rollouts keep
+# within the fp32 restatement's drift (C4 shard well-conditioned misses
+# 22 -> 8); the VALU-bound C3 would pay 16 %.
 _ROLLOUT_FLAGS = ["-Xarch_device", "-fno-slp-vectorize", "-Xarch_device", "-fassociative-math",
                   "-Xarch_device", "-fno-signed-zeros", "-Xarch_device", "-fno-trapping-math"]
-UNITS = [(os.path.join(CSRC, "engine.hip"), []),
-         (os.path.join(CSRC, "rollout.hip"), _ROLLOUT_FLAGS + ["-DMPCR_TU=1"]),
-         (os.path.join(CSRC, "rollout.hip"), ["PRECISE"] + _ROLLOUT_FLAGS + ["-DMPCR_TU=2"])]
-SRC = sorted({u for u, _ in UNITS})
-DEPS = SRC + [os.path.join(CSRC, f) for f in ("rollout.h", "cem.hip", "comm.hip", "mpcr_device.h")] + [
-    os.path.join(os.path.dirname(HERE), "include", f) for f in ("mpcr.h", "mpcr_model.h")]
+# (source, its own flags, precise)
+UNITS = [(os.path.join(CSRC, "engine.hip"), [], False),
+         (os.path.join(CSRC, "rollout_narrow.hip"), _ROLLOUT_FLAGS, False),
+         (os.path.join(CSRC, "rollout_wide.hip"), _ROLLOUT_FLAGS, True)]
+SRC = [u[0] for u in UNITS]
+# every file of csrc/ and include/ (tests/test_lib.py checks that none is
+# missing): the rebuild check and source_hash() read this list.  The MJCF
+# library's source and ABI header are listed too, so the hash names the whole
+# native build.
+DEPS = SRC + [os.path.join(CSRC, f) for f in ("rollout.hip", "rollout.h", "cem.hip", "comm.hip",
+                                              "mpcr_device.h", "mjcf_embed.cpp")] + [
+    os.path.join(os.path.dirname(HERE), "include", f) for f in ("mpcr.h", "mpcr_model.h", "mpcr_mjcf.h")]
 OUT = os.path.join(HERE, "libmpcr.so")
 ARCH = os.environ.get("MPCR_OFFLOAD_ARCH", "gfx950")
 # fp32 '/' and sqrtf map to the 1-ulp hardware v_rcp/v_sqrt (not the ~10-op
@@ -59,7 +67,7 @@ def source_hash() -> str:
         h.update(os.path.basename(d).encode())
         with open(d, "rb") as f:
             h.update(f.read())
-    h.update(repr((FLAGS, [f for _, f in UNITS])).encode())
+    h.update(repr((FLAGS, [u[1:] for u in UNITS])).encode())
     return h.hexdigest()[:16]
 
 
@@ -70,8 +78,8 @@ def hipcc():
     raise RuntimeError("hipcc not found")
 
 
-# the fast-math device flags above, dropped by compile_lib(precise=True) for
-# accuracy experiments (tools/build_variant.py --precise)
+# the fast-math device flags above, dropped for a precise unit and, for
+# accuracy experiments, by compile_lib(precise=True) (tools/build_variant.py --precise)
 FAST_MATH = {"-freciprocal-math", "-fapprox-func", "-fassociative-math", "-fno-signed-zeros", "-fno-trapping-math"}
 
 
@@ -92,15 +100,16 @@ def _drop_fast(flags):
 
 def compile_lib(out: str, extra=(), verbose: bool = False, precise: bool = False) -> str:
     """Compile every unit (FLAGS + its own + extra) and link the shared library.
-    precise: without the fast-math device flags (IEEE division / sqrt, no
-    reassociation) -- accuracy experiments only."""
+    precise: every unit without the fast-math device flags (IEEE division /
+    sqrt, no reassociation), not only the units marked so -- accuracy
+    experiments only."""
     import tempfile
     with tempfile.TemporaryDirectory() as tmp:
         objs = []
-        for i, (src, unit_flags) in enumerate(UNITS):
-            obj = os.path.join(tmp, f"{os.path.basename(src)}.{i}.o")
-            fl = FLAGS + [f for f in unit_flags if f != "PRECISE"]
-            if precise or "PRECISE" in unit_flags:
+        for src, unit_flags, unit_precise in UNITS:
+            obj = os.path.join(tmp, os.path.basename(src) + ".o")
+            fl = FLAGS + unit_flags
+            if precise or unit_precise:
                 fl = _drop_fast(fl)
             cmd = [hipcc(), f"--offload-arch={ARCH}", "-c"] + fl + list(extra) + ["-o", obj, src]
             if verbose:

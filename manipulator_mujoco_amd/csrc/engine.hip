@@ -18,14 +18,14 @@
 #include "../../include/mpcr.h"
 #include "mpcr_device.h"
 
-// kernels: the fused rollout is its own translation unit (rollout.hip, its
-// launchers declared in rollout.h); cem.hip: the CEM distribution step
+// kernels: the fused rollout has its own translation units (rollout.hip, built through
+// rollout_narrow.hip and rollout_wide.hip; its launchers declared in rollout.h); cem.hip:
+// the CEM distribution step
 #include "rollout.h"
 
-// extra dynamic LDS per narrow-kernel block (occupancy experiments only)
 // horizon segments of dual-arm rollouts (rollout_launch): steps per segment
 // (0 = one launch) and candidate groups on their own streams.  Measured
-// (tools/seg_sweep_r04.sh; C4 shard 4096 x 100 / C5 rollout 8192 x 50, ms):
+// (round 4 sweep; C4 shard 4096 x 100 / C5 rollout 8192 x 50, ms):
 // one launch 50.6 / 48.5; 2 groups x 25 steps 47.8 / 47.4, x 13-10 46.7 /
 // 45.8, x 7 46.3 / 45.0, x 5-3 46.4-46.6 / 45.1; 3 groups 47.3-49.5; 4
 // groups 65-67 (more streams than the process's 4 hardware queues)
@@ -40,9 +40,6 @@ static int env_int_or(const char* name, int dflt) {
   const char* v = getenv(name);
   return v ? atoi(v) : dflt;
 }
-#ifndef MPCR_N_DYN_LDS
-#define MPCR_N_DYN_LDS 0
-#endif
 #include "cem.hip"
 
 namespace mpcr {
@@ -89,7 +86,7 @@ struct mpcr_engine {
   unsigned long long* d_key = nullptr;
   int* d_status = nullptr;
   int* d_idx = nullptr;
-  float* d_slot_prev = nullptr;  // max_n x nslot (variants keeping cost_c history in HBM)
+  float* d_slot_prev = nullptr;  // max_n x nslot: cost_c history of the pairs not held in registers
   float* d_jx = nullptr;         // max_n x (MAXEFC - JL) x LDJ: J rows past the LDS ones
   float* d_td = nullptr;         // (max_n + 1) x nctrl x H joint-velocity table (thetadot not requested)
   short* d_hints = nullptr;      // max_n x NHINT x 2 (dual-arm class): hull-climb starts
@@ -1108,8 +1105,7 @@ extern "C" int mpcr_engine_create(const mpcr_model* m, int device, int max_n, in
       hipMalloc(&e->d_key, sizeof(unsigned long long)) != hipSuccess ||
       hipMalloc(&e->d_status, sizeof(int) * max_n) != hipSuccess ||
       hipMalloc(&e->d_idx, sizeof(int) * max_n) != hipSuccess ||
-      // per-candidate scratch slabs: one spare row for the empty group of a
-      // two-candidate wave (narrow kernel, odd n)
+      // per-candidate scratch slabs, each with one spare row of slack
       hipMalloc(&e->d_slot_prev, sizeof(float) * ((size_t)max_n + 1) * (e->host.nslot > 0 ? e->host.nslot : 1)) !=
           hipSuccess ||
       hipMalloc(&e->d_jx, sizeof(float) * ((size_t)max_n + 1) *
@@ -1141,7 +1137,7 @@ extern "C" int mpcr_engine_create(const mpcr_model* m, int device, int max_n, in
       // a batch the device holds in one round gains nothing: its blocks all
       // start together (the one-wave variant's resident blocks per CU x CUs)
       int occ[6] = {0, 0, 0, 0, 0, 0}, ncu = 0;
-      if (rollout_occupancy(occ, MPCR_N_DYN_LDS) == hipSuccess &&
+      if (rollout_occupancy(occ) == hipSuccess &&
           hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess)
         e->seg_min_n = occ[3] * ncu;
       bool ok = hipMalloc(&e->d_seg, sizeof(float) * (size_t)max_n * SEG_STRIDE) == hipSuccess;
@@ -1253,7 +1249,7 @@ static int launch_rollout(mpcr_engine* e, const Launch& l, hipStream_t st) {
   a.seg_min_n = e->seg_min_n;
   std::memcpy(a.par, l.par, sizeof(a.par));
   if (l.key && l.reset_key) hipLaunchKernelGGL(fill_u64, dim3(1), dim3(1), 0, st, l.key, ~0ull);
-  rollout_launch(e->wide, a, (const DevModel*)e->d_model, l.n, MPCR_N_DYN_LDS, st, e->seg_groups, e->seg_stream,
+  rollout_launch(e->wide, a, (const DevModel*)e->d_model, l.n, st, e->seg_groups, e->seg_stream,
                  e->seg_event);
   HIPCHK(hipGetLastError());
   return MPCR_OK;
@@ -1277,7 +1273,7 @@ extern "C" int mpcr_engine_dispatches(const mpcr_engine* e, int n, int* out) {
 extern "C" int mpcr_rollout_occupancy(int device, int* info) {
   if (!info) return fail(MPCR_EINVAL, "null argument");
   HIPCHK(hipSetDevice(device));
-  HIPCHK(rollout_occupancy(info, MPCR_N_DYN_LDS));
+  HIPCHK(rollout_occupancy(info));
   return MPCR_OK;
 }
 
@@ -1545,7 +1541,7 @@ extern "C" int mpcr_rollout_profile(mpcr_engine* e, const float* input, int layo
   a.mslab = e->d_mslab;
   a.layout = layout; a.n = n; a.H = e->H; a.nbasis = e->nbasis;
   fill_par(a.par, nc, q0, w, ptgt, qtgt);
-  rollout_launch(e->wide, a, (const DevModel*)e->d_model, n, MPCR_N_DYN_LDS, nullptr);
+  rollout_launch(e->wide, a, (const DevModel*)e->d_model, n, nullptr);
   HIPCHK(hipDeviceSynchronize());
   HIPCHK(hipMemcpy(phases16, d_prof, 64 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
   e->dev.prof = nullptr;
@@ -1579,7 +1575,7 @@ extern "C" int mpcr_rollout_wavetime(mpcr_engine* e, const float* input, int lay
   a.mslab = e->d_mslab;
   a.layout = layout; a.n = n; a.H = e->H; a.nbasis = e->nbasis;
   fill_par(a.par, nc, q0, w, ptgt, qtgt);
-  rollout_launch(e->wide, a, (const DevModel*)e->d_model, n, MPCR_N_DYN_LDS, nullptr);
+  rollout_launch(e->wide, a, (const DevModel*)e->d_model, n, nullptr);
   HIPCHK(hipDeviceSynchronize());
   HIPCHK(hipMemcpy(out, d_prof, 6 * (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
   (void)hipFree(d_prof);

@@ -1,7 +1,8 @@
 // rollout.h -- what the host side (engine.hip) shares with the rollout
-// kernel's translation unit (rollout.hip): the launch arguments, the plant
-// state layout, the per-block LDS images (sizes for the HBM slabs), and the
-// launchers.  rollout.hip is compiled on its own, with its own flags (see
+// kernel (rollout.hip) and its two translation units (rollout_narrow.hip,
+// rollout_wide.hip): the launch arguments, the plant state layout, the
+// per-block LDS images (sizes for the HBM slabs), and the launchers.  The two
+// units are compiled on their own, each with its own flags (see
 // manipulator_mujoco_amd/build.py).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -58,7 +59,7 @@ struct RolloutArgs {
   int* status;
   float* trace_eef;    // n x H x 7 (debug)
   float* trace_slots;  // n x H x nslot (debug)
-  float* slot_prev;    // n x nslot previous slot distances (variants keeping them in HBM)
+  float* slot_prev;    // n x nslot previous slot distances (pairs past the register-held chunks, SlotHist)
   float* jx;           // n x (MAXEFC - JL) x LDJ: J rows past the LDS ones
   short* hints;        // n x NHINT x 2: hull-climb start per convex pair and side (dual-arm class)
   unsigned long long* prof;  // per-phase cycles (MPCR_PROFILE builds only)
@@ -118,8 +119,8 @@ constexpr float POLY_DEEP = 5e-3f;
 constexpr int POLY_ALLF = MPCR_POLY_ALLF > 0 ? MPCR_POLY_ALLF : 1;
 constexpr bool POLY_ALLF_ON = MPCR_POLY_ALLF > 0;
 
-template <int NVW_, int NBW_, int NGW_, int MAXEFC_ = DX_MAXEFC, int LDJ_ = NVW_ + 4, bool CPREV_GLOBAL_ = false,
-          int JL_ = MAXEFC_, int CPW_ = 1, int MAXACT_ = DX_MAXACT, bool SPLIT_ = false>
+template <int NVW_, int NBW_, int NGW_, int MAXEFC_ = DX_MAXEFC, int LDJ_ = NVW_ + 4, int JL_ = MAXEFC_,
+          int MAXACT_ = DX_MAXACT, bool SPLIT_ = false>
 struct __align__(16) SmemT {
   // SPLIT: the dynamics scratch and the contact / constraint arrays do not
   // overlay (the two-wave variant runs the dynamics and the collision phase
@@ -127,13 +128,10 @@ struct __align__(16) SmemT {
   static constexpr bool SPLIT = SPLIT_;
   static constexpr int DYN_FLOATS = NBW_ * 64 + NVW_ * 16;  // xpos .. fvec below
   static constexpr int NVW = NVW_, NBW = NBW_, NGW = NGW_, LD = NVW_ + 4;
-  // candidates per wave: CPW images per workgroup, HL = 64 / CPW lanes each
-  static constexpr int CPW = CPW_, HL = WAVE / CPW_;
   static constexpr int MAXEFC = MAXEFC_, LDJ = LDJ_;      // constraint rows kept, J row stride
   static constexpr int MAXACT = MAXACT_;                  // active contacts kept
   static constexpr int JL = JL_;  // J rows held in LDS; rows JL.. live in the block's HBM slab (RolloutArgs::jx)
   static_assert(JL <= MAXEFC && JL % 4 == 0, "J rows in LDS");
-  static constexpr bool CPREV_GLOBAL = CPREV_GLOBAL_;     // previous slot distances in HBM (L2) instead of LDS
   static constexpr int LOG_NVW = NVW_ == 32 ? 5 : 4;
   static constexpr bool WIDE = NVW_ == 32;  // dual-arm class: equalities, actuators, convex hulls
   static constexpr int NQW = WIDE ? DX_NQ : MPCR_N_NQ, NEQP = WIDE ? DX_NEQ : 1, NACT = WIDE ? DX_NU : 1;
@@ -167,7 +165,7 @@ struct __align__(16) SmemT {
   };
   alignas(16) float gxpos[NGW][4];   // gxpos+gxmat (dead during Newton) double as the
   float gxmat[NGW][12];  // Hessian solve's LDS scratch (NGW*16 >= NVW*LD)
-  float cprev[CPREV_GLOBAL ? 1 : DX_NSLOT];  // previous-step masked slot distances (cost_c)
+  float cprev_pad_;       // unused (the previous slot distances live in HBM, RolloutArgs::slot_prev); keeps the layout
   float par[PAR_N];       // q0 | w | ptgt | qtgt (normalised)
   float eqp[NEQP][2][4];  // connect anchors in world (body1, body2)
   float tenp[WIDE ? DX_NTEN : 1][2][4];  // spatial-tendon sites in world
@@ -253,20 +251,14 @@ struct PolyScratchT {
 #ifndef MPCR_N_LDJ
 #define MPCR_N_LDJ 16
 #endif
-#ifndef MPCR_N_CPREV_GLOBAL
-#define MPCR_N_CPREV_GLOBAL 1
-#endif
-#ifndef MPCR_N_CPW
-#define MPCR_N_CPW 1
-#endif
-using SmemN = SmemT<16, 16, 24, MPCR_N_MAXEFC, MPCR_N_LDJ, MPCR_N_CPREV_GLOBAL, MPCR_N_JL, MPCR_N_CPW>;
+using SmemN = SmemT<16, 16, 24, MPCR_N_MAXEFC, MPCR_N_LDJ, MPCR_N_JL>;
 #if !defined(MPCR_N_LDS_UNCHECKED)
 static_assert(sizeof(SmemN) <= 9520, "narrow LDS image must fit 16 blocks per CU (see above)");
 #endif
 // The two-wave narrow image (small batches, rollout_kernel<..., 2>): dynamics
 // scratch and contacts side by side, every J row in LDS (no HBM slab) -- at
 // most 2048 candidates = 8 blocks per CU, so LDS is not the limit
-using SmemN2 = SmemT<16, 16, 24, MPCR_N_MAXEFC, MPCR_N_LDJ, MPCR_N_CPREV_GLOBAL, MPCR_N_MAXEFC, 1, DX_MAXACT, true>;
+using SmemN2 = SmemT<16, 16, 24, MPCR_N_MAXEFC, MPCR_N_LDJ, MPCR_N_MAXEFC, DX_MAXACT, true>;
 static_assert(sizeof(SmemN2) <= 152448 / 8, "two-wave narrow image: 8 blocks per CU");
 // Dual-arm image: J rows past 44 in the HBM slab, cost history and hull-climb
 // hints in HBM (the class has no robot-masked slots), the convex-pair list
@@ -280,8 +272,8 @@ static_assert(sizeof(SmemN2) <= 152448 / 8, "two-wave narrow image: 8 blocks per
 #ifndef MPCR_W_MAXACT
 #define MPCR_W_MAXACT 48  // the polyhedron manifold's 4 contacts per face pair (40 truncated 0.5 % of a C4 shard)
 #endif
-using SmemW = SmemT<32, 32, 72, 8 + 4 * MPCR_W_MAXACT, 36, true, MPCR_W_JL, 1, MPCR_W_MAXACT>;
-// The two-wave dual-arm image (MPCR_W_WPC2 builds, small batches): the
+using SmemW = SmemT<32, 32, 72, 8 + 4 * MPCR_W_MAXACT, 36, MPCR_W_JL, MPCR_W_MAXACT>;
+// The two-wave dual-arm image (small batches): the
 // dynamics scratch beside the contact / constraint arrays
 // and, since it runs at most 4 blocks per CU (<= 1024 candidates on 256
 // CUs: 40 960 B each of the CU's 160 KB), J rows 0..103 in LDS instead of
@@ -291,7 +283,7 @@ using SmemW = SmemT<32, 32, 72, 8 + 4 * MPCR_W_MAXACT, 36, true, MPCR_W_JL, 1, M
 #ifndef MPCR_W2_JL
 #define MPCR_W2_JL 104
 #endif
-using SmemW2 = SmemT<32, 32, 72, 8 + 4 * MPCR_W_MAXACT, 36, true, MPCR_W2_JL, 1, MPCR_W_MAXACT, true>;
+using SmemW2 = SmemT<32, 32, 72, 8 + 4 * MPCR_W_MAXACT, 36, MPCR_W2_JL, MPCR_W_MAXACT, true>;
 static_assert(sizeof(SmemW2) <= 163840 / 4, "two-wave dual-arm image: 4 blocks per CU");
 static_assert(sizeof(PolyScratchT<SmemW2::PMAXW>) + 2 * WAVE * 4 <= SmemW2::DYN_FLOATS * 4,
               "the dynamics wave's manifold scratch and the flush counts inside the dynamics region");
@@ -299,14 +291,8 @@ static_assert(sizeof(PolyScratchT<SmemW2::PMAXW>) + 2 * WAVE * 4 <= SmemW2::DYN_
 // the step's list (else the dealt flush), a manifold-queue record of
 // W2_JOB_REC ints per job inside the convex-pair list, and wave 0's results
 // (4 distances, points, normals, the count) W2_JOB_OUT floats per job in the
-// dynamics region after its manifold scratch
-#ifndef MPCR_W2_LEAD
-#define MPCR_W2_LEAD 1
-#endif
-// swap mode (rollout.hip): wave 0 runs the non-convex narrow phase
-#ifndef MPCR_W2_SWAP
-#define MPCR_W2_SWAP 1
-#endif
+// dynamics region after its manifold scratch; in swap mode wave 0 runs the
+// non-convex narrow phase meanwhile
 constexpr int W2_LEAD_MAX = 56, W2_JOB_REC = 8, W2_JOB_OUT = 29;
 static_assert(W2_LEAD_MAX <= WAVE && 2 + W2_JOB_REC * W2_LEAD_MAX <= SmemW2::CVXN, "manifold queue inside the list");
 static_assert(sizeof(PolyScratchT<SmemW2::PMAXW>) + 4 * W2_JOB_OUT * W2_LEAD_MAX <= SmemW2::DYN_FLOATS * 4,
@@ -324,18 +310,17 @@ static_assert(sizeof(SmemW) <= 20448, "dual-arm LDS image must fit 8 blocks per 
 #endif
 
 
-// launchers (defined in rollout.hip): the rollout kernel variant for the
-// model class over `grid` blocks of one wave; dyn_lds extra bytes per block
-// (occupancy experiments only)
+// launchers (defined in rollout_narrow.hip): the rollout kernel variant for the
+// model class over `grid` blocks of one wave
 // Dual-arm batches of the one-wave variant with a.seg > 0 and H > a.seg run as
 // horizon segments of a.seg steps over `groups` candidate groups, group g on
 // gstream[g] (forked from st by gev[0] and joined back by gev[1 + g]); every
 // group's segments in stream order.  The launches of different groups overlap,
 // so one segment's tail is filled by the other groups' work.
-void rollout_launch(bool wide, const RolloutArgs& a, const DevModel* dm, unsigned grid, size_t dyn_lds,
-                    hipStream_t st, int groups = 0, hipStream_t* gstream = nullptr, hipEvent_t* gev = nullptr);
+void rollout_launch(bool wide, const RolloutArgs& a, const DevModel* dm, unsigned grid, hipStream_t st,
+                    int groups = 0, hipStream_t* gstream = nullptr, hipEvent_t* gev = nullptr);
 // the dual-arm kernels' launches and occupancy (their own translation unit,
-// rollout.hip built with MPCR_TU = 2): wpc 1 (one wave per candidate, block
+// rollout_wide.hip): wpc 1 (one wave per candidate, block
 // per candidate) or 2 (two waves); info[0..2] blocks per CU, LDS, VGPRs
 void rollout_wide_launch(int wpc, unsigned grid, hipStream_t st, const RolloutArgs& a, const DevModel* dm);
 hipError_t rollout_wide_occupancy(int* info);
@@ -343,7 +328,7 @@ hipError_t rollout_wide_occupancy(int* info);
 // gev given: streams)
 int rollout_dispatches(bool wide, const RolloutArgs& a, unsigned grid, int groups, bool streams);
 // resident blocks per CU, static LDS bytes, VGPRs: narrow (0..2), wide (3..5)
-hipError_t rollout_occupancy(int* info, size_t dyn_lds);
+hipError_t rollout_occupancy(int* info);
 int rollout_set_wpc2_max_n(int n);  // two waves per candidate up to n (narrow variant); returns the previous
 
 }  // namespace mpcr

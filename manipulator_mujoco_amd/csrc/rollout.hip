@@ -7,16 +7,17 @@
 // (impedance, Newton line search).  The two dense SPD solves per step
 // (M and the Newton Hessian) are done row-per-lane in registers with DPP
 // row broadcasts (nv <= 16) or v_readlane (the 32-wide dual-arm variant): no
-// LDS round trips inside the factorisation.  Built as its own translation
-// unit (flags: manipulator_mujoco_amd/build.py); host side in engine.hip.
+// LDS round trips inside the factorisation.  Device code only, not built on
+// its own: included by the two translation units that launch it,
+// rollout_narrow.hip (single-arm kernels) and rollout_wide.hip (dual-arm
+// kernels), each with its own flags (manipulator_mujoco_amd/build.py); host
+// side in engine.hip.
 //
 // Semantics restated (same definitions as oracle/mpcr_oracle.c):
 //   rollout / output timing  SBP/mjx_planner.py:251-274
 //   cost                     SBP/mjx_planner.py:276-303
 //   mjx.step                 mujoco-mjx 3.3.1 (third party)
-#include <cstdlib>
-#include <atomic>
-
+#pragma once
 #include "rollout.h"
 #include "../../include/mpcr_model.h"  // MPCR_LUT_R (the engine's hull start table)
 
@@ -68,55 +69,22 @@ namespace mpcr {
 // the step it is on in its SIMD's slot group and takes an issue priority
 // equal to the number of its SIMD mates ahead of it, so the waves sharing a
 // SIMD progress together and the SIMD drains when its total work is done.
-#ifndef MPCR_PACE
-#define MPCR_PACE 1
-#endif
-// pacing in the dual-arm kernel too: 1.7 % slower at 7 blocks per CU (2.3
+// Pacing in the dual-arm kernel too: 1.7 % slower at 7 blocks per CU (2.3
 // backfilled rounds), ~0.8 % faster at 8 (C4 4096 x 100: 33.6-34.0 vs
-// 34.1 ms; 8192 x 50: 30.35-30.45 vs 30.57-30.79 ms)
-#ifndef MPCR_W_PACE
-#define MPCR_W_PACE 1
-#endif
-// a mate counts as ahead when it is more than MPCR_PACE_LAG steps ahead
-#ifndef MPCR_PACE_LAG
-#define MPCR_PACE_LAG 0
-#endif
-// where the mates' progress read at the step start is consumed: 0 before the
-// collision phase (mid-step), 1 at the next step's start, 2 before Newton
-#ifndef MPCR_PACE_AT
-#define MPCR_PACE_AT 0
-#endif
+// 34.1 ms; 8192 x 50: 30.35-30.45 vs 30.57-30.79 ms).
+// The mates' progress read at the step start is consumed before the
+// collision phase (mid-step).
 #define PACE_SETPRIO() \
   if (pace) {  /* priority = SIMD mates ahead of this wave (0..3) */ \
-  const int ahead = __popcll(__ballot(lane < 16 && lane != pace_own && pace_v != ~0u && pace_v > (unsigned)t + MPCR_PACE_LAG)); \
+  const int ahead = __popcll(__ballot(lane < 16 && lane != pace_own && pace_v != ~0u && pace_v > (unsigned)t)); \
   if (ahead >= 3) __builtin_amdgcn_s_setprio(3); \
   else if (ahead == 2) __builtin_amdgcn_s_setprio(2); \
   else if (ahead == 1) __builtin_amdgcn_s_setprio(1); \
   else __builtin_amdgcn_s_setprio(0); \
   }
 
-// ablation builds (timing attribution only; results are wrong): skip the
-// capsule-box deepest-point search / the narrow-phase functions in the mask
-#ifndef MPCR_ABL_DEEP
-#define MPCR_ABL_DEEP 0
-#endif
 #ifndef MPCR_CB_SKIP
 #define MPCR_CB_SKIP 1  // capsule-box: skip the interior knots when no lane's minimum is inside (narrow_lane)
-#endif
-#ifndef MPCR_ABL_FUNC
-#define MPCR_ABL_FUNC 0
-#endif
-#ifndef MPCR_WPC2_MAX_N_DEFAULT
-#define MPCR_WPC2_MAX_N_DEFAULT 2048  // batches up to this size run two waves per candidate (narrow variant;
-                                      // C3 512 / 1024 / 2048: 1.38 / 1.43 / 1.52 -> 1.07 / 1.09 / 1.20 ms,
-                                      // 4096: 1.77 -> 3.03 ms, the one-wave kernel stays)
-#endif
-// wide Newton's J^T f / J^T D J on two MFMA accumulators with batched row loads
-#ifndef MPCR_W_MFMA_SPLIT
-#define MPCR_W_MFMA_SPLIT 0  // measured: C4 50.97 vs 50.90 ms (noise), results move by an ulp: not kept
-#endif
-#ifndef MPCR_TD_TABLE
-#define MPCR_TD_TABLE 1
 #endif
 // instruction-count attribution builds (-DMPCR_STOP_AFTER=k, diagnostic only):
 // the step ends right after phase stamp k, so PMC differences between k and
@@ -206,54 +174,12 @@ __device__ __forceinline__ void sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 __device__ __forceinline__ void block_sync() { __syncthreads(); }
-
-// Candidate groups: a wave may carry CPW candidates of HL = 64 / CPW lanes
-// (lanes [32 h, 32 h + 32) for candidate h when CPW = 2).  These are the
-// group-local forms of the wave primitives above; ballots keep their bits in
-// place, restricted to the own group, so lanes_below / __popcll apply as is.
-template <int CPW>
-__device__ __forceinline__ int hlane() { return threadIdx.x & (WAVE / CPW - 1); }
-template <int CPW>
-__device__ __forceinline__ int hbase() { return threadIdx.x & (WAVE - WAVE / CPW); }
-template <int CPW>
-__device__ __forceinline__ unsigned long long hmask() {
-  if constexpr (CPW == 1) return ~0ull;
-  else return threadIdx.x >= 32 ? 0xffffffff00000000ull : 0xffffffffull;
-}
-template <int CPW>
-__device__ __forceinline__ unsigned long long hballot(bool p) { return __ballot(p) & hmask<CPW>(); }
-template <int CPW>
-__device__ __forceinline__ float hrdlane(float v, int l) {
-  if constexpr (CPW == 1) return rdlane(v, l);
-  else return threadIdx.x >= 32 ? rdlane(v, 32 + l) : rdlane(v, l);
-}
-template <int CPW>
-__device__ __forceinline__ float hsum(float v) {
-  if constexpr (CPW == 1) {
-    return wsum(v);
-  } else {
-    v += dppf<0xB1>(v);
-    v += dppf<0x4E>(v);
-    v += dppf<0x124>(v);
-    v += dppf<0x128>(v);
-    v += dppf_rows<0x142, 0xA>(v);  // rows 1, 3 += rows 0, 2: group sums in lanes 31, 63
-    return threadIdx.x >= 32 ? rdlane(v, 63) : rdlane(v, 31);
-  }
-}
-template <int CPW, class T>
-__device__ __forceinline__ T hshfl(T x, int src) { return __shfl(x, src + hbase<CPW>()); }
-template <int CPW>
-__device__ __forceinline__ int hscan_excl(int v, int& total) {
-  int pre = 0, tot = 0;
-#pragma unroll
-  for (int bit = 0; bit < 3; bit++) {
-    const unsigned long long mk = hballot<CPW>((v >> bit) & 1);
-    pre += lanes_below(mk) << bit;
-    tot += __popcll(mk) << bit;
-  }
-  total = tot;
-  return pre;
-}
+// __shfl behind a forceinline wrapper, for the kinematics' ancestor reads and
+// the constraint-row count: inlined with the kernel's other helpers, ahead of
+// the optimiser (called directly there, __shfl is inlined later and the
+// source-lane mask of a lane known to be in range is no longer folded away)
+template <class T>
+__device__ __forceinline__ T wshfl(T x, int src) { return __shfl(x, src); }
 
 // ---------------------------------------------------------------------------
 // small vector math
@@ -470,17 +396,10 @@ template <int STEP>
 struct Sweep16<-1, STEP> {
   static __device__ __forceinline__ void run(const float (&)[16], float&, float) {}
 };
-// the blocked (per-tree) Cholesky for M and uncoupled Newton Hessians
-#ifndef MPCR_BLOCK_CHOL
-#define MPCR_BLOCK_CHOL 1
-#endif
-// MPCR_CHOL_LANE_LAUNDER: re-derive the lane compares inside the solves (one
-// v_cmp each) instead of letting them be hoisted into spilled SGPR pairs
-#ifndef MPCR_CHOL_LANE_LAUNDER
-#define MPCR_CHOL_LANE_LAUNDER 1
-#endif
+// The solves launder their lane argument: the lane compares inside are
+// re-derived (one v_cmp each) instead of being hoisted into spilled SGPR pairs
 __device__ __forceinline__ void chol16(float (&a)[16], float& dinv, int lane) {
-  if (MPCR_CHOL_LANE_LAUNDER) asm volatile("" : "+v"(lane));
+  asm volatile("" : "+v"(lane));
   dinv = 0.f;
   Chol16<0>::run(a, dinv, lane);
 }
@@ -544,7 +463,7 @@ template <int N, class F>
 __device__ __forceinline__ void blocked_factor(const DevModel* __restrict__ m, F&& elem, int lane, float (&a)[N],
                                                float& dinv) {
   static_assert(N == 8 || N == 16, "blocked Cholesky width");
-  if (MPCR_CHOL_LANE_LAUNDER) asm volatile("" : "+v"(lane));
+  asm volatile("" : "+v"(lane));
   const int lr = lane & 15, lb = lane & ~15;
   const int d = m->blane_dof[lane];
 #pragma unroll
@@ -558,7 +477,7 @@ __device__ __forceinline__ void blocked_factor(const DevModel* __restrict__ m, F
 template <int N>
 __device__ __forceinline__ void blocked_sweep(const DevModel* __restrict__ m, const float (&a)[N], float dinv,
                                               const float* bv, float* xv, int lane, float* Lt) {
-  if (MPCR_CHOL_LANE_LAUNDER) asm volatile("" : "+v"(lane));
+  asm volatile("" : "+v"(lane));
   const int lr = lane & 15, t = lane >> 4;
   const int d = m->blane_dof[lane];
   float acc = d >= 0 ? bv[d] : 0.f;
@@ -591,11 +510,12 @@ __device__ __forceinline__ void blocked_solve(const DevModel* __restrict__ m, F&
   blocked_factor<N>(m, elem, lane, a, dinv);
   blocked_sweep<N>(m, a, dinv, bv, xv, lane, Lt);
 }
-// the blocked path for a kernel variant of NVW dofs: 8-wide chains in the
+// the blocked (per-tree) Cholesky for M and uncoupled Newton Hessians, for a
+// kernel variant of NVW dofs: 8-wide chains in the
 // narrow kernel (trees <= 8 dofs), 16-wide in the dual-arm one (trees <= 16)
 template <int NVW>
 __device__ __forceinline__ bool blk_usable(const DevModel* __restrict__ m) {
-  return MPCR_BLOCK_CHOL && (NVW == 16 ? m->blk_n == 8 : m->blk_n != 0);
+  return NVW == 16 ? m->blk_n == 8 : m->blk_n != 0;
 }
 template <int NVW, class F>
 __device__ __forceinline__ void blk_solve(const DevModel* __restrict__ m, F&& elem, const float* bv, float* xv,
@@ -606,7 +526,7 @@ __device__ __forceinline__ void blk_solve(const DevModel* __restrict__ m, F&& el
 // x = L^-T L^-1 b (lane i: row i of L in l[]); Lt: LDS transpose scratch
 template <int LDL>
 __device__ __forceinline__ float chol16_solve(const float (&l)[16], float dinv, float b, int lane, float* Lt) {
-  if (MPCR_CHOL_LANE_LAUNDER) asm volatile("" : "+v"(lane));
+  asm volatile("" : "+v"(lane));
   if (lane < 16) {
 #pragma unroll
     for (int j = 0; j < 16; j++) Lt[j * LDL + lane] = l[j];
@@ -694,14 +614,9 @@ __device__ __forceinline__ float point_box(const float p[3], const float h[3], f
 // refinement, the same algorithm and tolerances as the oracle's mpr()
 // (libccd MPR; one penetration contact per pair)
 
-#ifndef MPCR_MPR_TOL
-#define MPCR_MPR_TOL 1e-6f  // MuJoCo's ccd_tolerance (round 3; 1e-5 before)
-#endif
-#ifndef MPCR_MPR_ITER
-#define MPCR_MPR_ITER 50
-#endif
-constexpr float kMprTol = MPCR_MPR_TOL;  // gap tolerance (oracle MPR_TOL); MuJoCo ccd_iterations cap below
-constexpr int kMprIter = MPCR_MPR_ITER;
+// gap tolerance (oracle MPR_TOL): MuJoCo's ccd_tolerance (round 3; 1e-5 before)
+constexpr float kMprTol = 1e-6f;
+constexpr int kMprIter = 50;  // MuJoCo's ccd_iterations cap
 constexpr float kMprEps = 1.1920929e-07f;
 __device__ __forceinline__ bool mpr_zero(float x) { return fabsf(x) < kMprEps; }
 
@@ -711,20 +626,11 @@ __device__ __forceinline__ bool mpr_zero(float x) { return fabsf(x) < kMprEps; }
 // component that is exactly zero in fp64), and the hull climb moves to the
 // neighbour that beats the current vertex the most (strictly; kSupBand > 0
 // would make it the first within that many metres).
-#ifndef MPCR_SUP_BAND
-#define MPCR_SUP_BAND 0.f  // MuJoCo's strict climb (round 3; 1e-5 before)
-#endif
-#ifndef MPCR_SUP_TIE
-#define MPCR_SUP_TIE 1e-6f  // < 0: MuJoCo's mju_sign (only an exact zero is a tie)
-#endif
-constexpr float kSupTie = MPCR_SUP_TIE;
+constexpr float kSupTie = 1e-6f;  // < 0: MuJoCo's mju_sign (only an exact zero is a tie)
 // hull support ties (round 6, oracle HULL_TIE): vertices within this many
 // metres of the climb's end are tied with it (hull_tie); 0 = the plain climb
-#ifndef MPCR_HULL_TIE
-#define MPCR_HULL_TIE 1e-7f
-#endif
-constexpr float kHullTie = MPCR_HULL_TIE;
-constexpr float kSupBand = MPCR_SUP_BAND;
+constexpr float kHullTie = 1e-7f;
+constexpr float kSupBand = 0.f;  // MuJoCo's strict climb (round 3; 1e-5 before)
 __device__ __forceinline__ float tie_sign(float lk, float ln) {
   if (kSupTie < 0.f) return lk > 0.f ? 1.f : (lk < 0.f ? -1.f : 0.f);
   return fabsf(lk) < kSupTie * ln ? 0.f : (lk >= 0.f ? 1.f : -1.f);
@@ -847,10 +753,7 @@ struct SupQ {
   int type, la;
 };
 // a geom's per-query constants (type, table, first hull vertex), loaded once
-// per MPR run instead of in front of every support query (MPCR_SUP_GEOMQ)
-#ifndef MPCR_SUP_GEOMQ
-#define MPCR_SUP_GEOMQ 1
-#endif
+// per MPR run instead of in front of every support query
 struct GeomQ { int type, la, h0; };
 __device__ __forceinline__ GeomQ geom_q(const DevModel* __restrict__ m, int g) {
   GeomQ q{m->geom_type[g], m->geom_lutadr[g], m->geom_hulladr[g]};
@@ -1049,12 +952,8 @@ __device__ bool mpr_lane(const DevModel* __restrict__ m, const S& s, int g1, int
   MprPt p[4], v4;
   float va[3], vb[3], dd;
   const float tol = kMprTol;
-#if MPCR_SUP_GEOMQ
   const GeomQ gqa[2] = {geom_q(m, g1), geom_q(m, g2)};
   const GeomQ* const gq = gqa;
-#else
-  const GeomQ* const gq = nullptr;
-#endif
   // point x off the plane through the origin with (unnormalised) normal c by more than kMprEps
   auto off_plane = [](float x, const float c[3]) { return fabsf(x) >= kMprEps * sqrtf(dot3(c, c)); };
 #pragma unroll
@@ -1186,10 +1085,8 @@ __device__ __forceinline__ float wmax(float v) {
   return v;
 }
 
-// inline the manifold callees (experiment): 1 polyhedron, 2 both
-#ifndef MPCR_POLY_INLINE
-#define MPCR_POLY_INLINE 2  // both inlined: 241 -> 235 VGPRs, no scratch (the contact arrays stay in registers), C4 48.6 -> 46.7 ms
-#endif
+// Both manifold callees below are inlined: 241 -> 235 VGPRs, no scratch (the
+// contact arrays stay in registers), C4 48.6 -> 46.7 ms
 // Plane-mesh manifold (MJX plane_convex / _manifold_points, the oracle's
 // col_plane_mesh), wave-cooperative: every lane calls it with the same pair
 // (mesh g, plane normal n through xp, penetration depth) and lane q receives
@@ -1199,11 +1096,7 @@ __device__ __forceinline__ float wmax(float v) {
 // of four serial per-lane scans (a 2691-vertex hull touching the table made a
 // handful of dual-arm candidates 3x slower than the rest).
 template <class S>
-#if MPCR_POLY_INLINE >= 2
 __device__ __forceinline__
-#else
-__device__ __noinline__
-#endif
 void plane_mesh_manifold_wave(const DevModel* __restrict__ m_, const S& s, int g,
                                                       const float n_[3], const float* xp_, float depth, int q, int lane,
                                                       float dist[4], float pos[4][3], float nrm[4][3], int& nsl) {
@@ -1374,11 +1267,7 @@ __device__ __forceinline__ void vert_rel(const DevModel* __restrict__ m, const S
 // image's own, or -- the second wave of a two-wave candidate in the joint
 // convex flush -- a PolyScratchT in the dead dynamics region.
 template <class S, class PS>
-#if MPCR_POLY_INLINE
 __device__ __forceinline__
-#else
-__device__ __noinline__
-#endif
 void poly_manifold_wave(const DevModel* __restrict__ m_, const S& s, PS& ps, const short* hints, int p,
                                                 const float n_[3], float depth, int q, int lane, float dist[4],
                                                 float pos[4][3], float nrm[4][3], int& nsl) {
@@ -1884,7 +1773,7 @@ __device__ __forceinline__ int narrow_lane(const DevModel* __restrict__ m, const
     };
     knot(0);
     knot(1);
-    if (!MPCR_CB_SKIP || hballot<S::CPW>(tlo == 0.f && thi == 1.f) != 0ull) {
+    if (!MPCR_CB_SKIP || __ballot(tlo == 0.f && thi == 1.f) != 0ull) {
 #pragma unroll
       for (int i = 2; i < 8; i++) knot(i);
     }
@@ -1896,7 +1785,7 @@ __device__ __forceinline__ int narrow_lane(const DevModel* __restrict__ m, const
 #pragma unroll
     for (int c = 0; c < 3; c++) pp[c] = a[c] + ts * dd[c];
     float g = point_box(pp, h, nl, q);
-    if (g <= 1e-6f && !MPCR_ABL_DEEP) {  // on or in the box (penetrating segments land on the surface): the oracle's band
+    if (g <= 1e-6f) {  // on or in the box (penetrating segments land on the surface): the oracle's band
       // deepest point of g(t) = max_k |x_k(t)| - h_k over its kinks
       float gbest = 1e30f, tbest = 0.f;
 #pragma unroll
@@ -2157,19 +2046,19 @@ __device__ __forceinline__ void box_box_wave(const DevModel* __restrict__ m, S& 
   int face_id = -1, edge_lane = -1;
 #pragma unroll
   for (int a = 0; a < 6; a++) {
-    const float v = hrdlane<S::CPW>(sep, a);
+    const float v = rdlane(sep, a);
     if (v > best_face) { best_face = v; face_id = a; }
   }
 #pragma unroll
   for (int a = 6; a < 15; a++) {
-    const float v = hrdlane<S::CPW>(sep, a);
+    const float v = rdlane(sep, a);
     if (v > -1e30f && v > best_edge) { best_edge = v; edge_lane = a; }
   }
   const float best = fmaxf(best_face, best_edge);
   if (!(best < margin)) return;
   const bool use_edge = edge_lane >= 0 && best_edge > 0.95f * best_face + 1e-5f;
   const int src = use_edge ? edge_lane : face_id;
-  float n[3] = {hrdlane<S::CPW>(L[0], src), hrdlane<S::CPW>(L[1], src), hrdlane<S::CPW>(L[2], src)};
+  float n[3] = {rdlane(L[0], src), rdlane(L[1], src), rdlane(L[2], src)};
   const float sg = dot3(t, n) >= 0.f ? 1.f : -1.f;
   n[0] *= sg; n[1] *= sg; n[2] *= sg;
   const int base = s.ncon;
@@ -2273,7 +2162,7 @@ __device__ __forceinline__ void box_box_wave(const DevModel* __restrict__ m, S& 
       inside = inside && sgn * (dot3(P, Ra) - cra) - hr[ax] <= 0.f;
     }
   }
-  if (hballot<S::CPW>(!inside) == 0ull) np = -np;  // marker: skip the clips
+  if (__ballot(!inside) == 0ull) np = -np;  // marker: skip the clips
   for (int pl = 0; pl < 4 && np > 0; pl++) {
     sync();
     const int ax = (fi + 1 + (pl >> 1)) % 3;
@@ -2293,7 +2182,7 @@ __device__ __forceinline__ void box_box_wave(const DevModel* __restrict__ m, S& 
       e1 = (dp < 0.f && dq > 0.f) || (dp > 0.f && dq < 0.f);
     }
     int tot;
-    const int o = hscan_excl<S::CPW>(e0 + e1, tot);
+    const int o = wscan_excl(e0 + e1, tot);
     if (e0) {
 #pragma unroll
       for (int k = 0; k < 3; k++) s.poly[cur ^ 1][o][k] = P[k];
@@ -2317,7 +2206,7 @@ __device__ __forceinline__ void box_box_wave(const DevModel* __restrict__ m, S& 
     depth = hrf - dot3(rel, nf);
     keep = -depth < margin;
   }
-  const unsigned long long km = hballot<S::CPW>(keep);
+  const unsigned long long km = __ballot(keep);
   const int nkeep = __popcll(km);
   if (nkeep == 0) return;
   const int rank = lanes_below(km);  // position of this lane among the kept points
@@ -2329,10 +2218,9 @@ __device__ __forceinline__ void box_box_wave(const DevModel* __restrict__ m, S& 
     float dbest = -3e38f;
 #pragma unroll
     for (int c = 0; c < 8; c++) {
-      const int cb = c + hbase<S::CPW>();  // lane c of this group
-      const float dc = hrdlane<S::CPW>(depth, c);
-      const bool kc = (km >> cb) & 1ull;
-      const int rc = __popcll(km & ((1ull << cb) - 1ull));
+      const float dc = rdlane(depth, c);
+      const bool kc = (km >> c) & 1ull;
+      const int rc = __popcll(km & ((1ull << c) - 1ull));
       if (kc && dc > dbest) { dbest = dc; d0 = rc; }
     }
     slot = -1;
@@ -2366,12 +2254,9 @@ __device__ __forceinline__ void box_box_wave(const DevModel* __restrict__ m, S& 
 // chunk k < NC keeps them in v[k][0..3] (no per-step HBM slab round trip: the
 // slab's L2 evictions were ~8.6 MB of a C3 launch's 29.7 MB HBM traffic);
 // pairs of later chunks use the slab.  The dual-arm class keeps the slab.
-#ifndef MPCR_N_CPREV_REG
-#define MPCR_N_CPREV_REG 1
-#endif
 template <class S>
 struct SlotHist {
-  static constexpr int NC = (!S::WIDE && MPCR_N_CPREV_REG) ? 128 / S::HL : 0;
+  static constexpr int NC = S::WIDE ? 0 : 128 / WAVE;
   float v[NC > 0 ? NC : 1][4];
 };
 
@@ -2421,7 +2306,7 @@ __device__ __forceinline__ void emit_contacts(const DevModel* __restrict__ m, S&
 #pragma unroll
             for (int j = 0; j < SlotHist<S>::NC; j++) sh.v[j][c] = j == k ? d : sh.v[j][c];
           } else {
-            float* cp = S::CPREV_GLOBAL ? args.slot_prev + (size_t)b * m->nslot : s.cprev;
+            float* cp = args.slot_prev + (size_t)b * m->nslot;
             if (t > 0) cost_c += fmaxf(cp[sa + c] * (1.f - 0.005f) - d, 0.f);
             cp[sa + c] = d;
           }
@@ -2436,11 +2321,11 @@ __device__ __forceinline__ void emit_contacts(const DevModel* __restrict__ m, S&
     }
   }
   int tot;
-  const int pre = hscan_excl<S::CPW>(act, tot);
+  const int pre = wscan_excl(act, tot);
   const int base = s.ncon;
   if (act) put_contacts(m, s, base + pre, p, nsl, dist, pos, nrm);
   sync();
-  if (hlane<S::CPW>() == 0) s.ncon = base + tot;
+  if ((threadIdx.x & (WAVE - 1)) == 0) s.ncon = base + tot;
   sync();
 }
 
@@ -2459,11 +2344,8 @@ __device__ __forceinline__ void emit_contacts(const DevModel* __restrict__ m, S&
 // misses of the fp32 restatement against fp64).  The row sums stay fp32.
 template <class T>
 struct LsPtT { T alpha, cost, d0, d1; bool full; };
-#ifndef MPCR_W_LS64
-#define MPCR_W_LS64 1  // 0: the dual-arm line search in fp32 (timing experiments only)
-#endif
 template <class S>
-using LsReal = typename std::conditional<S::WIDE && MPCR_W_LS64, double, float>::type;
+using LsReal = typename std::conditional<S::WIDE, double, float>::type;
 
 // elliptic rows: efc_src = (5 << 24) | (contact << 14) | (pair << 4) | side
 __device__ __forceinline__ bool ell_row(int src) { return (src >> 24) == 5; }
@@ -2480,7 +2362,7 @@ __device__ __forceinline__ bool ls_neg(float jar, float jv, T alpha) {
 template <class S, class T>
 __device__ __forceinline__ void ls_rows(const S& s, int lane, T alpha, float& q0, float& q1, float& q2) {
   q0 = q1 = q2 = 0.f;
-  for (int r = lane; r < s.nefc; r += S::HL) {
+  for (int r = lane; r < s.nefc; r += WAVE) {
     float jar = s.efc_jar[r], jv = s.efc_jv[r];
     if constexpr (S::WIDE) {
       if (ell_row(s.efc_src[r])) continue;
@@ -2509,9 +2391,9 @@ template <class S, bool Q0 = true, class T = LsReal<S>>
 __device__ __forceinline__ LsPtT<T> ls_eval(const S& s, int lane, const float qg[3], T alpha) {
   float q0, q1, q2;
   ls_rows(s, lane, alpha, q0, q1, q2);
-  q0 = Q0 ? hsum<S::CPW>(q0) + qg[0] : 0.f;
-  q1 = hsum<S::CPW>(q1) + qg[1];
-  q2 = hsum<S::CPW>(q2) + qg[2];
+  q0 = Q0 ? wsum(q0) + qg[0] : 0.f;
+  q1 = wsum(q1) + qg[1];
+  q2 = wsum(q2) + qg[2];
   LsPtT<T> p = ls_make<T>(alpha, q0, q1, q2);
   p.full = Q0;
   return p;
@@ -2520,15 +2402,15 @@ __device__ __forceinline__ LsPtT<T> ls_eval(const S& s, int lane, const float qg
 template <class S, class T>
 __device__ __forceinline__ void ls_finish(const S& s, int lane, const float qg[3], LsPtT<T>& a, LsPtT<T>& b) {
   float qa = 0.f, qb = 0.f;
-  for (int r = lane; r < s.nefc; r += S::HL) {
+  for (int r = lane; r < s.nefc; r += WAVE) {
     const float jar = s.efc_jar[r], jv = s.efc_jv[r];
     const bool eq = (s.efc_src[r] >> 24) == 1;
     const float c0 = 0.5f * s.efc_D[r] * jar * jar;
     if (eq || ls_neg(jar, jv, a.alpha)) qa += c0;
     if (eq || ls_neg(jar, jv, b.alpha)) qb += c0;
   }
-  qa = hsum<S::CPW>(qa) + qg[0];
-  qb = hsum<S::CPW>(qb) + qg[0];
+  qa = wsum(qa) + qg[0];
+  qb = wsum(qb) + qg[0];
   if (!a.full) { a.cost = a.cost + qa; a.full = true; }
   if (!b.full) { b.cost = b.cost + qb; b.full = true; }
 }
@@ -2540,7 +2422,7 @@ __device__ __forceinline__ void ls_eval3(const S& s, int lane, const float qg[3]
                                          LsPtT<T>& p0, LsPtT<T>& p1, LsPtT<T>& p2) {
   float q[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   const T al[3] = {a0, a1, a2};
-  for (int r = lane; r < s.nefc; r += S::HL) {
+  for (int r = lane; r < s.nefc; r += WAVE) {
     const float jar = s.efc_jar[r], jv = s.efc_jv[r], D = s.efc_D[r];
     const bool eq = (s.efc_src[r] >> 24) == 1;
     if constexpr (S::WIDE) {
@@ -2553,7 +2435,7 @@ __device__ __forceinline__ void ls_eval3(const S& s, int lane, const float qg[3]
     }
   }
 #pragma unroll
-  for (int k = 0; k < 9; k++) q[k] = (Q0 || k % 3) ? hsum<S::CPW>(q[k]) + qg[k % 3] : 0.f;
+  for (int k = 0; k < 9; k++) q[k] = (Q0 || k % 3) ? wsum(q[k]) + qg[k % 3] : 0.f;
   p0 = ls_make<T>(a0, q[0], q[1], q[2]);
   p1 = ls_make<T>(a1, q[3], q[4], q[5]);
   p2 = ls_make<T>(a2, q[6], q[7], q[8]);
@@ -2630,7 +2512,7 @@ __device__ __forceinline__ void ls_cones3(const S& s, const DevModel* __restrict
                                           float e[9]) {
 #pragma unroll
   for (int k = 0; k < 9; k++) e[k] = 0.f;
-  for (int r = lane; r < s.nefc; r += S::HL) {
+  for (int r = lane; r < s.nefc; r += WAVE) {
     const int src = s.efc_src[r];
     if (!ell_head(src)) continue;
     const int p = ell_pair(src);
@@ -2645,7 +2527,7 @@ __device__ __forceinline__ void ls_cones3(const S& s, const DevModel* __restrict
     }
   }
 #pragma unroll
-  for (int k = 0; k < 9; k++) e[k] = hsum<S::CPW>(e[k]);
+  for (int k = 0; k < 9; k++) e[k] = wsum(e[k]);
 }
 
 template <class T>
@@ -2673,29 +2555,9 @@ __device__ __forceinline__ void ls_add(LsPtT<T>& p, float c0, float c1, float c2
 // loop into an SGPR pair, which then spills to VGPR lanes (two v_readlane per
 // use) and keeps lane-derived addresses live across the step: 178 -> 130
 // VGPRs, i.e. 3 waves/SIMD instead of 2 once the LDS image fits (below).
-#ifndef MPCR_LANE_LAUNDER
-#define MPCR_LANE_LAUNDER 1
-#endif
+// The dual-arm kernel too: 256 -> 241 VGPRs, scratch 304 -> 144 B, C4 49.7 -> 48.6 ms.
+// (Once per step only: launders at the phase boundaries as well were not kept.)
 #define LAUNDER_LANE() asm volatile("" : "+v"(lane))
-#ifndef MPCR_W_LANE_LAUNDER
-#define MPCR_W_LANE_LAUNDER 1  // the dual-arm kernel too: 256 -> 241 VGPRs, scratch 304 -> 144 B, C4 49.7 -> 48.6 ms
-#endif
-// phase-boundary launders (-DMPCR_PHASE_LAUNDER=0 keeps only the per-step one)
-#ifndef MPCR_PHASE_LAUNDER
-#define MPCR_PHASE_LAUNDER 0
-#endif
-#if MPCR_PHASE_LAUNDER
-#define LAUNDER_PHASE() LAUNDER_MODEL()
-#elif MPCR_LANE_LAUNDER >= 2 || MPCR_W_LANE_LAUNDER >= 2
-#define LAUNDER_PHASE()                                                          \
-  do {                                                                           \
-    if constexpr (WIDE ? MPCR_W_LANE_LAUNDER >= 2 : MPCR_LANE_LAUNDER >= 2) LAUNDER_LANE(); \
-  } while (0)
-#else
-#define LAUNDER_PHASE() \
-  do {                  \
-  } while (0)
-#endif
 
 // ---------------------------------------------------------------------------
 // J row access: rows < JL in LDS, the rest in the block's HBM slab gx.  The
@@ -2726,17 +2588,8 @@ __device__ __forceinline__ void jrows(const S& s, const float* gx, int r0, int s
 // ---------------------------------------------------------------------------
 // the kernel
 
-// The narrow variant is compiled for 4 waves/SIMD (<= 128 VGPRs; its LDS image
-// fits 16 blocks per CU): at the bench's 4096 candidates = 4 per SIMD every
-// candidate is resident at once (3 waves/SIMD: 3.52 ms, 4: 2.76 ms on C3).
-#ifndef MPCR_DPP_CHOL
-#define MPCR_DPP_CHOL 1
-#endif
 // narrow variant: the Newton gradient J^T f and Hessian J^T D J on the matrix
 // core (v_mfma_f32_16x16x4_f32) instead of per-row VALU loops
-#ifndef MPCR_MFMA_HESS
-#define MPCR_MFMA_HESS 1
-#endif
 typedef float mfx4 __attribute__((ext_vector_type(4)));
 typedef float mfx16 __attribute__((ext_vector_type(16)));
 // narrow variant: the chain / subtree sums of the dynamics (CRB, body
@@ -2745,9 +2598,6 @@ typedef float mfx16 __attribute__((ext_vector_type(16)));
 // mask times per-dof / per-body rows.  v_mfma_f32_16x16x4_f32 is a k-ordered
 // fmaf chain, and the products are the loops' own (qvel x cdof, fvec x cdof),
 // so the results are bitwise the per-lane loops'
-#ifndef MPCR_MFMA_DYN
-#define MPCR_MFMA_DYN 1
-#endif
 // acc + A B over k < 16 (4 instructions): lane l supplies A[l & 15][k] =
 // af(l & 15, k) and B[k][l & 15] = bf(k, l & 15) for its k = 4 s + (l >> 4);
 // register v of lane l then holds row 4 (l >> 4) + v, column l & 15
@@ -2764,33 +2614,17 @@ __device__ __forceinline__ mfx4 mm16(AF&& af, BF&& bf, mfx4 acc, int lane) {
 // the same for the 32-wide (dual-arm) Newton on v_mfma_f32_32x32x2_f32
 // (neutral while the 32-wide readlane Cholesky dominated; with the blocked
 // per-tree solve C4 66.2 -> 65.2 ms)
-#ifndef MPCR_MFMA_HESS_W
-#define MPCR_MFMA_HESS_W 1
-#endif
-// two waves per candidate, dual-arm class: wave 1 builds each Newton
-// iteration's Hessian while wave 0 forms J^T f, the gradient and the stop test
-#ifndef MPCR_W2_HESS
-#define MPCR_W2_HESS 1
-#endif
-// ... and the implicit solve's blocked factor of M + dt D on wave 1 during Newton
-#ifndef MPCR_W2_IMPL
-#define MPCR_W2_IMPL 1
-#endif
+// Two waves per candidate, dual-arm class: wave 1 builds each Newton
+// iteration's Hessian while wave 0 forms J^T f, the gradient and the stop
+// test, and the implicit solve's blocked factor of M + dt D during Newton
+// (hess2, impl2 in the kernel).
+// The narrow variant is compiled for 4 waves/SIMD (<= 128 VGPRs; its LDS image
+// fits 16 blocks per CU): at the bench's 4096 candidates = 4 per SIMD every
+// candidate is resident at once (3 waves/SIMD: 3.52 ms, 4: 2.76 ms on C3).
 // The dual-arm variant is compiled for 2 waves/SIMD (<= 256 registers incl.
 // AGPRs; uncapped it took 274 and ran 1 wave/SIMD): with its 21.6 KB image,
 // 7 blocks per CU instead of 4 (dual arm 4096 x 50: 47.5 -> 35.8 ms).
-#ifndef MPCR_W_WAVES
-#define MPCR_W_WAVES 2
-#endif
-#ifndef MPCR_N_WAVES
-#define MPCR_N_WAVES 4
-#endif
-// occupancy experiments: -DMPCR_WAVES_PER_EU=n asks the compiler for n waves/SIMD
-#ifdef MPCR_WAVES_PER_EU
-#define MPCR_ROLLOUT_ATTR __attribute__((amdgpu_waves_per_eu(MPCR_WAVES_PER_EU, MPCR_WAVES_PER_EU)))
-#else
-#define MPCR_ROLLOUT_ATTR
-#endif
+constexpr int kWideWavesPerSimd = 2, kNarrowWavesPerSimd = 4;
 
 // 32-wide: acc += sum over constraint rows, two per v_mfma_f32_32x32x2_f32
 // (lane (gi, gq) supplies A = J[r0 + gq][gi] and B = bf(r, A)).  Rows < JL
@@ -2801,35 +2635,7 @@ __device__ __forceinline__ mfx4 mm16(AF&& af, BF&& bf, mfx4 acc, int lane) {
 template <class S, class BF>
 __device__ __forceinline__ mfx16 mfma_rows32(const S& s, const float* gx, int nefc, int gi, int gq, BF&& bf,
                                              mfx16 acc) {
-  static_assert(S::JL % (MPCR_W_MFMA_SPLIT ? 8 : 2) == 0, "a row group never straddles the LDS / slab boundary");
-#if MPCR_W_MFMA_SPLIT
-  // two accumulators (row groups alternate), four row pairs' operands loaded
-  // before their MFMAs: the dependent 32x32x2 chain and the LDS / slab loads
-  // feeding it overlap (the sum is reassociated once at the end)
-  mfx16 acc2;
-#pragma unroll
-  for (int v = 0; v < 16; v++) acc2[v] = 0.f;
-  for (int r0 = 0; r0 < nefc; r0 += 8) {
-    float a[4], bv[4];
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-      const int r = r0 + 2 * u + gq;
-      a[u] = r < nefc ? (r < S::JL ? s.J[r][gi] : gx[(r - S::JL) * S::LDJ + gi]) : 0.f;
-    }
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-      const int r = r0 + 2 * u + gq;
-      bv[u] = r < nefc ? bf(r, a[u]) : 0.f;
-    }
-#pragma unroll
-    for (int u = 0; u < 4; u += 2) {
-      if (r0 + 2 * u < nefc) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u], bv[u], acc, 0, 0, 0);
-      if (r0 + 2 * u + 2 < nefc) acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u + 1], bv[u + 1], acc2, 0, 0, 0);
-    }
-  }
-#pragma unroll
-  for (int v = 0; v < 16; v++) acc[v] += acc2[v];
-#else
+  static_assert(S::JL % 2 == 0, "a row group never straddles the LDS / slab boundary");
   const int n1 = nefc < S::JL ? nefc : S::JL;
   for (int r0 = 0; r0 < n1; r0 += 2) {
     const int r = r0 + gq;
@@ -2853,7 +2659,6 @@ __device__ __forceinline__ mfx16 mfma_rows32(const S& s, const float* gx, int ne
       }
     }
   }
-#endif
   return acc;
 }
 
@@ -2864,26 +2669,23 @@ __device__ __forceinline__ mfx16 mfma_rows32(const S& s, const float* gx, int ne
 // workgroup barriers per step (geom poses ready; contacts ready).  Same
 // instructions on the same data as WPC = 1, so the results are bitwise equal.
 template <int NVW, int NBW, int NGW, bool WIDE, int WPC = 1>
-__global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES / SmemN::CPW) MPCR_ROLLOUT_ATTR rollout_kernel(RolloutArgs args,
-                                                                        const DevModel* __restrict__ mptr) {
-  static_assert(WPC == 1 || (WPC == 2 && (WIDE || SmemN::CPW == 1)), "two waves per candidate: CPW 1");
+__global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrowWavesPerSimd)
+    rollout_kernel(RolloutArgs args, const DevModel* __restrict__ mptr) {
+  static_assert(WPC == 1 || WPC == 2, "waves per candidate");
   using S = typename std::conditional<WIDE, typename std::conditional<WPC == 2, SmemW2, SmemW>::type,
                                       typename std::conditional<WPC == 2, SmemN2, SmemN>::type>::type;
   const int wv = WPC == 2 ? (int)(threadIdx.x >> 6) : 0;
   const bool run_main = WPC == 1 || wv == 0, run_coll = WPC == 1 || wv == 1;
   static_assert(S::NVW == NVW && S::NBW == NBW && S::NGW == NGW, "variant widths");
-  __shared__ S sm[S::CPW];  // one LDS image per candidate of the wave
-  S& s = sm[S::CPW == 1 ? 0 : (int)(threadIdx.x >> 5)];
+  __shared__ S s;  // the candidate's LDS image
   const DevModel* __restrict__ const m0 = mptr;
   const DevModel* __restrict__ m = m0;
-  int lane = hlane<S::CPW>();  // lane within the candidate's group; laundered per step (LAUNDER_LANE)
-  const int b = blockIdx.x * S::CPW + (S::CPW == 1 ? 0 : (int)(threadIdx.x >> 5));
-  const bool live = b < args.n;  // the last wave's second group may be empty
-  if (S::CPW == 1 && !live) return;
-  const int bi = live ? b : args.n - 1;  // an empty group replays a real candidate, writes nothing
+  int lane = threadIdx.x & (WAVE - 1);  // laundered per step (LAUNDER_LANE)
+  const int b = blockIdx.x;
+  if (b >= args.n) return;
   const int H = args.H;
   // horizon segment of this launch (dual-arm one-wave variant only)
-  constexpr bool SEG = WIDE && WPC == 1 && S::CPW == 1;
+  constexpr bool SEG = WIDE && WPC == 1;
   const int t_begin = SEG ? args.t0 : 0, t_end = SEG ? args.t1 : H;
   const bool resume = SEG && t_begin > 0, suspend = SEG && t_end < H;
   float* const segs = SEG ? args.seg_state + (size_t)b * SEG_STRIDE : nullptr;
@@ -2958,14 +2760,13 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
   // as LDS rows.  Wave 0's Newton step, or -- two waves, dual-arm class --
   // wave 1's, while wave 0 forms J^T f, the gradient and the stop test.
   auto newton_hessian = [&](int nefc, float* Hs) {
-    constexpr bool MFMA_HESS_W = NVW == 32 && S::CPW == 1 && MPCR_MFMA_HESS_W;
-    constexpr int RPW = S::HL / NVW;
+    constexpr int RPW = WAVE / NVW;
     constexpr int QPL = NVW / 4 / RPW;
     const int gi = lane & (NVW - 1), gq = lane >> S::LOG_NVW;
     float4 hq[QPL];
 #pragma unroll
     for (int k = 0; k < QPL; k++) hq[k] = m_quad(gi, gq + RPW * k);
-    if constexpr (MFMA_HESS_W) {
+    if constexpr (NVW == 32) {  // (the narrow kernel builds H with its gradient, in the Newton loop)
       // J^T D J on v_mfma_f32_32x32x2_f32: accumulator register 4k + e of
       // lane (gi, gq) is H[gi][4 (gq + 2k) + e] in the transposed view --
       // exactly hq[k].e, the VALU build's ownership, and the same products
@@ -2978,16 +2779,6 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
       acc = mfma_rows32(s, gx, nefc, gi, gq, [&](int r, float a) { return s.efc_Da[r] * a; }, acc);
 #pragma unroll
       for (int k = 0; k < QPL; k++) hq[k] = make_float4(acc[4 * k], acc[4 * k + 1], acc[4 * k + 2], acc[4 * k + 3]);
-    } else {
-      jrows(s, gx, 0, 1, nefc, [&](const float* J, int r) {
-        const float c = s.efc_Da[r] * J[gi];
-#pragma unroll
-        for (int k = 0; k < QPL; k++) {
-          const float4 v = reinterpret_cast<const float4*>(J)[gq + RPW * k];
-          hq[k].x = fmaf(c, v.x, hq[k].x); hq[k].y = fmaf(c, v.y, hq[k].y);
-          hq[k].z = fmaf(c, v.z, hq[k].z); hq[k].w = fmaf(c, v.w, hq[k].w);
-        }
-      });
     }
     if constexpr (S::WIDE) {  // cone Hessian blocks J_c^T H_c J_c (wave-uniform loop)
       if (m->cone == 1)
@@ -3035,18 +2826,18 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
     // steps (reset by mpcr_plant_set_state), so k plant steps = a k-step rollout
     if (!from_state && !resume) {
       int* h = reinterpret_cast<int*>(args.hints + (size_t)b * S::NHINT * 2);
-      for (int i = lane; i < S::NHINT; i += S::HL) h[i] = -1;  // both sides -1
+      for (int i = lane; i < S::NHINT; i += WAVE) h[i] = -1;  // both sides -1
     }
   }
   if (resume) {  // a later horizon segment: the state the previous one saved
-    for (int i = lane; i < S::NQW; i += S::HL) s.qpos[i] = i < DX_NQ ? segs[SEG_QPOS + i] : 0.f;
+    for (int i = lane; i < S::NQW; i += WAVE) s.qpos[i] = i < DX_NQ ? segs[SEG_QPOS + i] : 0.f;
     if (lane < NVW) {
       s.qvel[lane] = segs[SEG_QVEL + lane];
       s.qws[lane] = segs[SEG_QWS + lane];
       s.qacc[lane] = 0.f;
     }
   } else {
-  for (int i = lane; i < S::NQW; i += S::HL)
+  for (int i = lane; i < S::NQW; i += WAVE)
     s.qpos[i] = i < m->nq ? (from_state ? args.state[ST_QPOS + i] : m->qpos_init[i]) : 0.f;
   if (lane < NVW) {
     const bool v = lane < nv;
@@ -3067,18 +2858,17 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
   }
   if constexpr (WPC == 2) block_sync();
 
-#if MPCR_TD_TABLE
   // the candidate's joint velocities for the whole horizon, computed up front
   // by all lanes (theta_dot = A_thetadot xi, SBP/mjx_planner.py:348) into the
   // thetadot output (or a scratch row); each step then reads its value with a
   // load issued one step ahead, so no per-step basis latency is exposed
   const float* tdp;
   if (args.layout == 0) {
-    float* tdw = (args.thetadot && live ? args.thetadot : args.tdscratch) + (size_t)b * nc * H;
-    for (int idx = lane; run_main && !resume && idx < nc * H; idx += S::HL) {
+    float* tdw = (args.thetadot ? args.thetadot : args.tdscratch) + (size_t)b * nc * H;
+    for (int idx = lane; run_main && !resume && idx < nc * H; idx += WAVE) {
       const int j = idx / H, tt = idx - j * H;
       const float* pd = args.pdot + (size_t)tt * args.nbasis;
-      const float* xj = args.input + ((size_t)bi * nc + j) * args.nbasis;
+      const float* xj = args.input + ((size_t)b * nc + j) * args.nbasis;
       float v = 0.f;
 #pragma unroll
       for (int k = 0; k < 12; k++)
@@ -3090,18 +2880,9 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
     if constexpr (WPC == 2) block_sync();
     tdp = tdw;
   } else {
-    tdp = args.input + (size_t)bi * nc * H;
+    tdp = args.input + (size_t)b * nc * H;
   }
   float vnext = lane < nc ? tdp[lane * H + t_begin] : 0.f;
-#else
-  // lane j < nctrl keeps joint j's Bernstein coefficients in registers for
-  // the whole horizon (nbasis <= 12, checked by the engine)
-  float xir[12];
-#pragma unroll
-  for (int k = 0; k < 12; k++)
-    xir[k] = (args.layout == 0 && lane < nc && k < args.nbasis)
-                 ? args.input[((size_t)bi * nc + lane) * args.nbasis + k] : 0.f;
-#endif
   float cost_g = 0.f, cost_r = 0.f, cost_c = 0.f;
   SlotHist<S> shist;
 #pragma unroll
@@ -3119,11 +2900,10 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
   // every step; the per-step model launder would otherwise reload them)
   const int ctrl_qa = lane < nc ? m->ctrl_qposadr[lane] : 0, ctrl_da = lane < nc ? m->ctrl_dofadr[lane] : 0;
   PROF_DECL
-#if MPCR_PACE
   unsigned* pace = nullptr;
   int pace_own = 0;
   unsigned pace_v = ~0u;
-  if ((!WIDE || MPCR_W_PACE) && S::CPW == 1 && WPC == 1 && args.pace) {
+  if (WPC == 1 && args.pace) {
     const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | 4);  // HW_ID
     const unsigned xcc = __builtin_amdgcn_s_getreg((3 << 11) | 20);  // XCC_ID[3:0]
     const unsigned grp = ((((xcc & 7u) * 8u + ((hw >> 13) & 7u)) * 2u + ((hw >> 12) & 1u)) * 16u + ((hw >> 8) & 15u)) *
@@ -3131,7 +2911,6 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
     pace = args.pace + grp * 16u;
     pace_own = (int)(hw & 15u);
   }
-#endif
 #ifdef MPCR_WAVETIME
   // diagnostic build: per-wave start / end (constant 100 MHz clock), shader
   // cycles and the hardware slot the wave ran on (load-balance study)
@@ -3187,11 +2966,7 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
     // all live across the whole step (244 VGPRs + SGPR spills).  The loads
     // stay in their phases and hit L1/L2.
     LAUNDER_MODEL();
-    if constexpr ((!WIDE || MPCR_W_LANE_LAUNDER) && MPCR_LANE_LAUNDER) LAUNDER_LANE();
-#if MPCR_PACE && MPCR_PACE_AT == 1
-    PACE_SETPRIO();  // the previous step's read, against this step
-#endif
-#if MPCR_PACE
+    LAUNDER_LANE();
     if (pace) {  // post this step, read the SIMD mates' (consumed mid-step)
       // a plain store keeps the line in this XCD's L2 (agent scope would drop
       // it: every mate's next load then missed L2 -- the launch's largest
@@ -3200,37 +2975,18 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
       if (lane == pace_own) __hip_atomic_store(pace + lane, (unsigned)t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       if (lane < 16) pace_v = __hip_atomic_load(pace + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-#endif
     if (run_main) {  // ---- wave 0 (WPC = 2): joint velocities .. geom poses, eef
     // ---- qvel[:nctrl] = thetadot_t ----------------------------------------------
-#if MPCR_TD_TABLE
     if (lane < nc) {
       const float v = vnext;
       if (t + 1 < H) vnext = tdp[lane * H + t + 1];  // next step's, in flight during this one
       s.qvel[ctrl_da] = v;
-      if (args.layout != 0 && args.thetadot && live) args.thetadot[(size_t)b * nc * H + lane * H + t] = v;
+      if (args.layout != 0 && args.thetadot) args.thetadot[(size_t)b * nc * H + lane * H + t] = v;
     }
-#else
-    if (lane < nc) {
-      float v;
-      if (args.layout == 0) {
-        v = 0.f;
-        const float* pd = args.pdot + (size_t)t * args.nbasis;
-#pragma unroll
-        for (int k = 0; k < 12; k++)
-          if (k < args.nbasis) v = fmaf(pd[k], xir[k], v);
-      } else {
-        v = args.input[(size_t)bi * nc * H + lane * H + t];
-      }
-      s.qvel[ctrl_da] = v;
-      if (args.thetadot && live) args.thetadot[(size_t)b * nc * H + lane * H + t] = v;
-    }
-#endif
     sync();
 
     STAMP(0);
     STOP_AT(0)
-    LAUNDER_PHASE();  // phase boundary: no cross-phase model-load CSE
     // ---- kinematics: local pose per body, then pointer jumping ----------------
     {
       float q[4] = {1.f, 0.f, 0.f, 0.f}, p[3] = {0.f, 0.f, 0.f};
@@ -3276,10 +3032,10 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
       for (int r = 0; r < m->jump_rounds; r++) {
         const int src = anc >= 0 ? anc : lane;
         float aq[4], ap[3];
-        aq[0] = hshfl<S::CPW>(q[0], src); aq[1] = hshfl<S::CPW>(q[1], src);
-        aq[2] = hshfl<S::CPW>(q[2], src); aq[3] = hshfl<S::CPW>(q[3], src);
-        ap[0] = hshfl<S::CPW>(p[0], src); ap[1] = hshfl<S::CPW>(p[1], src); ap[2] = hshfl<S::CPW>(p[2], src);
-        const int aanc = hshfl<S::CPW>(anc, src);
+        aq[0] = wshfl(q[0], src); aq[1] = wshfl(q[1], src);
+        aq[2] = wshfl(q[2], src); aq[3] = wshfl(q[3], src);
+        ap[0] = wshfl(p[0], src); ap[1] = wshfl(p[1], src); ap[2] = wshfl(p[2], src);
+        const int aanc = wshfl(anc, src);
         if (anc >= 0) {
           float R[9], w[3];
           q2m(R, aq);
@@ -3306,7 +3062,6 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
 
     STAMP(1);
     STOP_AT(1)
-    LAUNDER_PHASE();  // phase boundary: no cross-phase model-load CSE
     // ---- geom poses, tree COMs ------------------------------------------------
     if (lane < m->ngeom) {
       const int gb = m->geom_body[lane];
@@ -3365,9 +3120,9 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
     }
     for (int tr = 0; tr < m->ntree; tr++) {
       float mm = (lane < nb && m->body_tree[lane] == tr) ? m->body_mass[lane] : 0.f;
-      float cx = hsum<S::CPW>(mm * (lane < nb ? s.xipos[lane][0] : 0.f));
-      float cy = hsum<S::CPW>(mm * (lane < nb ? s.xipos[lane][1] : 0.f));
-      float cz = hsum<S::CPW>(mm * (lane < nb ? s.xipos[lane][2] : 0.f));
+      float cx = wsum(mm * (lane < nb ? s.xipos[lane][0] : 0.f));
+      float cy = wsum(mm * (lane < nb ? s.xipos[lane][1] : 0.f));
+      float cz = wsum(mm * (lane < nb ? s.xipos[lane][2] : 0.f));
       if (lane == 0) {
         float tm = m->tree_mass[tr];
         s.com[tr][0] = cx / tm; s.com[tr][1] = cy / tm; s.com[tr][2] = cz / tm;
@@ -3397,11 +3152,11 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
       float qn = sqrtf(eq[0] * eq[0] + eq[1] * eq[1] + eq[2] * eq[2] + eq[3] * eq[3]);
       float dq = fabsf((eq[0] * qt[0] + eq[1] * qt[1] + eq[2] * qt[2] + eq[3] * qt[3]) / qn);
       cost_r += 2.f * acosf(clampf(dq, -1.f, 1.f));
-      if (args.trace_eef && live) {
+      if (args.trace_eef) {
         float* e = args.trace_eef + ((size_t)b * H + t) * 7;
         e[0] = ep[0]; e[1] = ep[1]; e[2] = ep[2]; e[3] = eq[0]; e[4] = eq[1]; e[5] = eq[2]; e[6] = eq[3];
       }
-      if (args.plant && t == H - 1 && live) {
+      if (args.plant && t == H - 1) {
         float* e = args.state + ST_EEF;
         e[0] = ep[0]; e[1] = ep[1]; e[2] = ep[2]; e[3] = eq[0]; e[4] = eq[1]; e[5] = eq[2]; e[6] = eq[3];
       }
@@ -3416,7 +3171,6 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
 
     STAMP(2);
     STOP_AT(2)
-    LAUNDER_PHASE();  // phase boundary: no cross-phase model-load CSE
     if (run_main) {  // ---- wave 0: the dynamics (cinert .. M^-1 qfrc_smooth)
     // ---- cinert, cdof (+ actuator forces) -------------------------------------
     if constexpr (S::WIDE) {
@@ -3471,9 +3225,8 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
 
     STAMP(3);
     STOP_AT(3)
-    LAUNDER_PHASE();  // phase boundary: no cross-phase model-load CSE
     // ---- CRB, velocity, RNE + gravcomp (subtree sums by bitmask) -----------
-    constexpr bool MFMA_DYN = NVW == 16 && NBW == 16 && S::CPW == 1 && MPCR_MFMA_DYN;
+    constexpr bool MFMA_DYN = NVW == 16 && NBW == 16;
     float* dscr = &s.xquat[0][0];  // xquat + xmat (256 floats) are dead after the cdof phase
     if constexpr (MFMA_DYN) {
       const int mr = lane & 15, kq = lane >> 4;
@@ -3531,7 +3284,7 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
           if (mr < 6) dscr[128 + (4 * kq + v) * 8 + mr] = a4[v];
       }
     } else {
-    for (int idx = lane; idx < nb * 10; idx += S::HL) {
+    for (int idx = lane; idx < nb * 10; idx += WAVE) {
       const int bb = idx / 10, k = idx - bb * 10;
       uint32_t sm = m->body_submask[bb];
       float acc = 0.f;
@@ -3626,7 +3379,6 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
     sync();
     STAMP(4);
     STOP_AT(4)
-    LAUNDER_PHASE();  // phase boundary: no cross-phase model-load CSE
     // mass matrix entries (chain-masked) + bias forces
     if constexpr (MFMA_DYN) {
       // P = fvec cdof^T (K = 6 in two instructions); M[i][j] = P[i][j] for j on
@@ -3659,7 +3411,7 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
         if (mr < 6) dscr[(4 * kq + v) * 8 + mr] = fb[v];
       sync();
     } else {
-    for (int idx = lane; idx < NVW * NVW; idx += S::HL) {
+    for (int idx = lane; idx < NVW * NVW; idx += WAVE) {
       const int i = idx >> S::LOG_NVW, j = idx & (NVW - 1);
       float v = 0.f;
       if (i < nv && j < nv) {
@@ -3710,9 +3462,8 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
 
     STAMP(5);
     STOP_AT(5)
-    LAUNDER_PHASE();  // phase boundary: no cross-phase model-load CSE
     // ---- qacc_smooth = M^-1 qfrc_smooth (row-per-lane Cholesky) -------------
-    if (S::CPW == 1 && blk_usable<NVW>(m)) {
+    if (blk_usable<NVW>(m)) {
       // M is block diagonal by kinematic tree: one chain for all trees
       if (lane >= nv && lane < NVW) s.qas[lane] = 0.f;
       blk_solve<NVW>(m, [&](int i, int j) { return m_get(i, j); }, s.qfs, s.qas, lane, &s.xpos[0][0]);
@@ -3722,7 +3473,7 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
       for (int j = 0; j < NVW; j++) Lm[j] = lane < NVW ? m_get(lane, j) : 0.f;
       // the dynamics region (xpos..fvec) is dead once M is assembled
       float x;
-      if constexpr (NVW == 16 && MPCR_DPP_CHOL) {
+      if constexpr (NVW == 16) {
         float dinv;
         chol16(Lm, dinv, lane);
         x = chol16_solve<S::LD>(Lm, dinv, lane < NVW ? s.qfs[lane] : 0.f, lane, &s.xpos[0][0]);
@@ -3737,10 +3488,7 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
 
     STAMP(6);
     STOP_AT(6)
-#if MPCR_PACE && MPCR_PACE_AT == 0
     PACE_SETPRIO();
-#endif
-    LAUNDER_PHASE();  // phase boundary: no cross-phase model-load CSE
     // Swap mode (two waves, dual-arm class without cost slots, round 5): the
     // collision wave only culls the pairs and lists the convex ones, posts
     // the list (an LDS step token, no barrier) and goes on to their MPRs (the
@@ -3749,7 +3497,7 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
     // contacts keep the one-wave order (these pairs' first, chunk by chunk,
     // then the convex ones).  With more convex pairs than the lead flush
     // takes, the collision wave runs that narrow phase itself, as before.
-    const bool swapm = WPC == 2 && S::WIDE && MPCR_W2_SWAP && MPCR_W2_LEAD && m->cvx_joint && m->nslot == 0;
+    const bool swapm = WPC == 2 && S::WIDE && m->cvx_joint && m->nslot == 0;
     for (int pass = 0; pass < 2 && (run_coll || swapm); pass++) {
     bool do_list = false, do_narrow = false;
     if (run_coll) {
@@ -3778,9 +3526,9 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
     }
     // (the general-convex pairs are sorted last, from DevModel::cvx_base: a
     // list-only pass starts at their chunk, a narrow-only pass ends there)
-    const int k_lo = do_narrow ? 0 : m->cvx_base / S::HL, p_hi = do_list ? m->npair : min(m->npair, m->cvx_base);
-    for (int k = k_lo; k * S::HL < p_hi; k++) {
-      const int p = lane + k * S::HL;
+    const int k_lo = do_narrow ? 0 : m->cvx_base / WAVE, p_hi = do_list ? m->npair : min(m->npair, m->cvx_base);
+    for (int k = k_lo; k * WAVE < p_hi; k++) {
+      const int p = lane + k * WAVE;
       const bool valid = p < m->npair;
       const int func = valid ? m->pair_func[p] : -1;
       const bool defer = S::WIDE && func >= 9;  // general convex: the list
@@ -3824,9 +3572,9 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
       if (!do_narrow) continue;
       float dist[4] = {1e30f, 1e30f, 1e30f, 1e30f}, pos[4][3] = {}, nrm[4][3] = {};
       int nsl = 0;
-      if (run && func != 4 && !defer && !(MPCR_ABL_FUNC & (1 << func))) nsl = narrow_lane(m, s, hx, p, dist, pos, nrm);
+      if (run && func != 4 && !defer) nsl = narrow_lane(m, s, hx, p, dist, pos, nrm);
       STAMP(11);
-      const unsigned long long bbm = hballot<S::CPW>(run && func == 4 && !(MPCR_ABL_FUNC & 16));
+      const unsigned long long bbm = __ballot(run && func == 4);
       emit_contacts(m, s, args, b, t, H, valid && func != 4 && !defer, p, nsl, dist, pos, nrm, cost_c, shist, k);
       STAMP(12);
       if (bbm && !(m->disableflags & 16)) {
@@ -3834,7 +3582,7 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
         while (mm) {
           const int q = __builtin_ctzll(mm);
           mm &= mm - 1;
-          box_box_wave(m, s, k * S::HL + q - hbase<S::CPW>(), lane);
+          box_box_wave(m, s, k * WAVE + q, lane);
         }
       }
       STAMP(16);
@@ -3885,7 +3633,7 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
       float* const mbox = reinterpret_cast<float*>(jcnt);  // wave 0's manifold results, W2_JOB_OUT floats per job
       int lpc = 0, ljob = 0, lsl = 0;
       float ld[4] = {1e30f, 1e30f, 1e30f, 1e30f}, lp[4][3] = {}, ln[4][3] = {};
-      if (MPCR_W2_LEAD && split && wv == 1 && s.ncvx <= m->w2_lead_max) {
+      if (split && wv == 1 && s.ncvx <= m->w2_lead_max) {
         const bool v = lane < s.ncvx;
         lpc = v ? s.cvx[lane] : 0;
         lsl = v ? narrow_lane(m, s, hx, lpc, ld, lp, ln, (args.dbg && b == 0 && t == H - 1) ? args.dbg : nullptr)
@@ -3915,7 +3663,7 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
       }
       if constexpr (WPC == 2) block_sync();  // the list is complete; the dynamics are done
       const int ncv = s.ncvx, rstep = split ? 2 * WAVE : WAVE;
-      const bool lead = MPCR_W2_LEAD && split && ncv <= m->w2_lead_max;
+      const bool lead = split && ncv <= m->w2_lead_max;
       int ncon_w = s.ncon;
       if (lead) {
         STAMP(16);  // (profile build: wave 0's wait for the queue)
@@ -4038,15 +3786,15 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
     // the barrier that follows; same values in the same places as one wave
     const bool rows_j = WPC == 2 && S::WIDE && !rows_c;
     // ... and wave 1 then builds the Newton Hessians (round 5)
-    const bool hess2 = MPCR_W2_HESS && rows_j && NVW == 32 && S::CPW == 1;
+    const bool hess2 = rows_j && NVW == 32;
     // ... and factors the implicit solve's M + dt D (blocked path) for wave 0
     // to sweep after Newton: the factor needs only M, wave 1 is otherwise
     // idle then, and its element gather was most of the solve's time
-    const bool impl2 = MPCR_W2_IMPL && hess2 && S::WIDE && m->integrator == 3 && !m->impl_cross && blk_usable<NVW>(m);
+    const bool impl2 = hess2 && S::WIDE && m->integrator == 3 && !m->impl_cross && blk_usable<NVW>(m);
     constexpr int BLK_N = NVW == 16 ? 8 : 16;
     static_assert(!S::SPLIT || (BLK_N + 1) * WAVE <= S::DYN_FLOATS, "the implicit factor inside the dynamics region");
     float* const implf = &s.xpos[0][0];  // the factor: BLK_N + 1 floats per lane (dynamics region, dead until Euler)
-    const int rl0 = rows_j ? wv * S::HL : 0, rls = rows_j ? 2 * S::HL : S::HL;
+    const int rl0 = rows_j ? wv * WAVE : 0, rls = rows_j ? 2 * WAVE : WAVE;
     if constexpr (WPC == 2) {
       if (!rows_c) {
         block_sync();  // the contact list is ready; wave 1 waits for the next step's geom poses
@@ -4056,7 +3804,6 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
 
     STAMP(7);
     STOP_AT(7)
-    LAUNDER_PHASE();  // phase boundary: no cross-phase model-load CSE
     // ---- constraint rows: equality, limits, contacts ------------------------
     bool coupled = true;  // a constraint row spans two kinematic trees (Newton's H not block diagonal)
     if (WPC == 1 || rows_j || (rows_c ? run_coll : run_main)) {
@@ -4070,7 +3817,7 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
         if (m->jnt_range[lane][1] - q < m->jnt_margin[lane]) { nlim_l++; lsides |= 2; }
       }
       int nlim;
-      const int lim_pre = hscan_excl<S::CPW>(nlim_l, nlim);
+      const int lim_pre = wscan_excl(nlim_l, nlim);
       // spatial-tendon limit rows after the joint limits (wave-uniform)
       int ntr = 0, tsides = 0;
       if constexpr (S::WIDE) {
@@ -4088,14 +3835,14 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
       int ncr = 0;
       if (lane < ncon) ncr = m->pair_condim[s.con_pair[lane]] == 1 ? 1 : (ell ? 3 : 4);
       int ncrow;
-      const int con_pre = hscan_excl<S::CPW>(ncr, ncrow);
+      const int con_pre = wscan_excl(ncr, ncrow);
       int nefc = neq + nlim + ntr + ncrow;
       int keep_con = ncon;
       if (nefc > S::MAXEFC) {  // keep the longest prefix of contacts that fits
         const int room = S::MAXEFC - neq - nlim - ntr;
-        const unsigned long long fit = hballot<S::CPW>(lane < ncon && con_pre + ncr <= room);
+        const unsigned long long fit = __ballot(lane < ncon && con_pre + ncr <= room);
         keep_con = __popcll(fit);
-        nefc = neq + nlim + ntr + (keep_con > 0 ? hshfl<S::CPW>(con_pre + ncr, keep_con - 1) : 0);
+        nefc = neq + nlim + ntr + (keep_con > 0 ? wshfl(con_pre + ncr, keep_con - 1) : 0);
         status |= 1;
       }
       // equality rows: joint (side 0) or connect component side - 1
@@ -4130,7 +3877,7 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
           const int4 ji = m->pair_jinfo[s.con_pair[lane]];
           cross = ji.x != 0 && ji.y != 0 && ji.z != ji.w;
         }
-        coupled = m->eq_cross || hballot<S::CPW>(cross) != 0ull;
+        coupled = m->eq_cross || __ballot(cross) != 0ull;
       }
       if (lane == 0) s.nefc = nefc;
       sync();
@@ -4386,10 +4133,6 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
 
     STAMP(8);
     STOP_AT(8)
-#if MPCR_PACE && MPCR_PACE_AT == 2
-    PACE_SETPRIO();
-#endif
-    LAUNDER_PHASE();  // phase boundary: no cross-phase model-load CSE
     // ---- Newton solver (primal), MJX-style line search ------------------------
     {
       const int nefc = s.nefc;
@@ -4401,7 +4144,7 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
           const float maw = lane < nv ? m_dot(lane, s.qws) : 0.f;
           const float gw = lane < nv ? (maw - s.qfs[lane]) * (s.qws[lane] - s.qas[lane]) : 0.f;
           float cw = 0.f, cs = 0.f;
-          for (int r = lane; r < nefc; r += S::HL) {
+          for (int r = lane; r < nefc; r += WAVE) {
             const float jw = jdot(s, gx, r, s.qws) - s.efc_aref[r];
             const float js = jdot(s, gx, r, s.qas) - s.efc_aref[r];
             const bool eq = (s.efc_src[r] >> 24) == 1;
@@ -4425,8 +4168,8 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
             if (eq || jw < 0.f) cw += s.efc_D[r] * jw * jw;
             if (eq || js < 0.f) cs += s.efc_D[r] * js * js;
           }
-          const float costw = 0.5f * hsum<S::CPW>(gw) + 0.5f * hsum<S::CPW>(cw);
-          const float costs = 0.5f * hsum<S::CPW>(cs);
+          const float costw = 0.5f * wsum(gw) + 0.5f * wsum(cw);
+          const float costs = 0.5f * wsum(cs);
           if (costw < costs && lane < NVW) qacc_l = s.qws[lane];
           if (args.dbg && b == 0 && t == H - 1 && lane == 0) {
             args.dbg[DBG_INFO + 0] = costw < costs ? 1.f : 0.f;
@@ -4453,7 +4196,7 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
           // Ma, jar, cost at the current qacc; per-row force and active D
           const float ma = lane < nv ? m_dot(lane, s.qacc) : 0.f;
           float cc = 0.f;
-          for (int r = lane; r < nefc; r += S::HL) {
+          for (int r = lane; r < nefc; r += WAVE) {
             const float jar = jdot(s, gx, r, s.qacc) - s.efc_aref[r];
             bool act = ((s.efc_src[r] >> 24) == 1) || jar < 0.f;
             if constexpr (S::WIDE) act = act && !ell_row(s.efc_src[r]);  // cone pass below
@@ -4466,7 +4209,7 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
           if constexpr (S::WIDE) {  // elliptic contacts: cone cost and forces
             if (m->cone == 1) {
               sync();
-              for (int r = lane; r < nefc; r += S::HL) {
+              for (int r = lane; r < nefc; r += WAVE) {
                 const int src = s.efc_src[r];
                 if (!ell_head(src)) continue;
                 const int p = ell_pair(src);
@@ -4478,14 +4221,12 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
               }
             }
           }
-          const float gauss = hsum<S::CPW>(lane < nv ? (ma - s.qfs[lane]) * (s.qacc[lane] - s.qas[lane]) : 0.f);
-          const float cost = 0.5f * gauss + 0.5f * hsum<S::CPW>(cc);
+          const float gauss = wsum(lane < nv ? (ma - s.qfs[lane]) * (s.qacc[lane] - s.qas[lane]) : 0.f);
+          const float cost = 0.5f * gauss + 0.5f * wsum(cc);
           sync();
           if (hess2) block_sync();  // this iteration's active set, to wave 1
           STAMP(29);
-          constexpr bool MFMA_HESS = NVW == 16 && S::CPW == 1 && MPCR_MFMA_HESS;
-          constexpr bool MFMA_HESS_W = NVW == 32 && S::CPW == 1 && MPCR_MFMA_HESS_W;
-          constexpr int RPW = S::HL / NVW;
+          constexpr bool MFMA_HESS = NVW == 16;  // else the 32-wide MFMA gradient, and newton_hessian
           const int gi = lane & (NVW - 1), gq = lane >> S::LOG_NVW;
           float* Hs = &s.gxpos[0][0];  // geom poses are dead during Newton
           float grad;
@@ -4515,7 +4256,7 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
             if (gi == 0) reinterpret_cast<float4*>(qcs)[gq] = make_float4(gacc[0], gacc[1], gacc[2], gacc[3]);
             sync();
             grad = lane < nv ? ma - s.qfs[lane] - qcs[gi] : 0.f;
-          } else if constexpr (MFMA_HESS_W) {
+          } else {
             // 32-wide: J^T f on v_mfma_f32_32x32x2_f32, 2 rows per instruction
             // (lane: A = J[r0 + gq][gi], B = f[r0 + gq]); accumulator register
             // v of lane l holds (J^T f)[(v & 3) + 8 (v >> 2) + 4 gq]
@@ -4533,17 +4274,9 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
             sync();
             grad = lane < nv ? ma - s.qfs[lane] - qcs[gi] : 0.f;
             sync();  // qcs (srch) is rewritten below
-          } else {
-            // grad = Ma - qfrc_smooth - J^T f: lane (dof i, row group q); RPW
-            // lanes share a dof (4 at NVW 16, 2 at NVW 32)
-            float qc = 0.f;
-            jrows(s, gx, gq, RPW, nefc, [&](const float* J, int r) { qc = fmaf(J[gi], s.efc_f[r], qc); });
-#pragma unroll
-            for (int o = NVW; o < S::HL; o <<= 1) qc += __shfl_xor(qc, o);
-            grad = lane < nv ? ma - s.qfs[lane] - qc : 0.f;
           }
           STAMP(30);
-          const float gn = sqrtf(hsum<S::CPW>(grad * grad));
+          const float gn = sqrtf(wsum(grad * grad));
           // MuJoCo's stop test, plus its fp32 floor: an improvement within ~8 ulp
           // of the cost is rounding noise (without it fp32 iterates on noise
           // where the fp64 solve has converged: 3.9 vs 1.9 iterations per
@@ -4560,7 +4293,7 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
           }
           STAMP(31);
           float mg;
-          if (S::CPW == 1 && !coupled && blk_usable<NVW>(m)) {
+          if (!coupled && blk_usable<NVW>(m)) {
             // no row couples two trees: H is block diagonal like M
             if (lane < NVW) s.srch[lane] = lane < nv ? grad : 0.f;
             sync();
@@ -4578,7 +4311,7 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
                 h[4 * q] = v.x; h[4 * q + 1] = v.y; h[4 * q + 2] = v.z; h[4 * q + 3] = v.w;
               }
             }
-            if constexpr (NVW == 16 && MPCR_DPP_CHOL) {
+            if constexpr (NVW == 16) {
               float dinv;
               chol16(h, dinv, lane);
               mg = chol16_solve<S::LD>(h, dinv, lane < nv ? grad : 0.f, lane, &s.gxpos[0][0]);
@@ -4597,13 +4330,13 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
           sync();
           // Mv, jv, quadratic coefficients
           const float mvv = lane < nv ? m_dot(lane, s.srch) : 0.f;
-          for (int r = lane; r < nefc; r += S::HL) s.efc_jv[r] = jdot(s, gx, r, s.srch);
-          const float sn = sqrtf(hsum<S::CPW>(search * search));
+          for (int r = lane; r < nefc; r += WAVE) s.efc_jv[r] = jdot(s, gx, r, s.srch);
+          const float sn = sqrtf(wsum(search * search));
           const float gtol = m->tolerance * m->ls_tolerance * sn * m->meaninertia * (float)(nv > 1 ? nv : 1);
           float qg[3];
           qg[0] = 0.5f * gauss;
-          qg[1] = hsum<S::CPW>(lane < nv ? search * (ma - s.qfs[lane]) : 0.f);
-          qg[2] = 0.5f * hsum<S::CPW>(search * mvv);
+          qg[1] = wsum(lane < nv ? search * (ma - s.qfs[lane]) : 0.f);
+          qg[2] = 0.5f * wsum(search * mvv);
           sync();
           using LT = LsReal<S>;
           using LsPt = LsPtT<LT>;
@@ -4689,7 +4422,6 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
     if (args.dbg && b == 0 && t == H - 1 && lane < NVW) args.dbg[DBG_QACC + lane] = s.qacc[lane];
     STAMP(9);
     STOP_AT(9)
-    LAUNDER_PHASE();  // phase boundary: no cross-phase model-load CSE
     // ---- implicitfast (dual-arm class): (M + dt D) a = qfrc_smooth + J^T f at
     //      the final qacc; the velocity update uses a, the warm start qacc --
     bool implicit = false;
@@ -4697,7 +4429,7 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
       if (m->integrator == 3) {
         implicit = true;
         const int nefc = s.nefc;
-        for (int r = lane; r < nefc; r += S::HL) {
+        for (int r = lane; r < nefc; r += WAVE) {
           const float jar = jdot(s, gx, r, s.qacc) - s.efc_aref[r];
           const bool act = ((s.efc_src[r] >> 24) == 1) || jar < 0.f;
           s.efc_f[r] = act ? -s.efc_D[r] * jar : 0.f;
@@ -4705,7 +4437,7 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
         }
         sync();
         if (m->cone == 1) {  // elliptic contacts: cone forces at the final qacc
-          for (int r = lane; r < nefc; r += S::HL) {
+          for (int r = lane; r < nefc; r += WAVE) {
             const int src = s.efc_src[r];
             if (!ell_head(src)) continue;
             const int p = ell_pair(src);
@@ -4717,14 +4449,14 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
           }
           sync();
         }
-        constexpr int RPW = S::HL / NVW;
+        constexpr int RPW = WAVE / NVW;
         const int gi = lane & (NVW - 1), gq = lane >> S::LOG_NVW;
         float qc = 0.f;
         jrows(s, gx, gq, RPW, nefc, [&](const float* J, int r) { qc = fmaf(J[gi], s.efc_f[r], qc); });
 #pragma unroll
-        for (int o = NVW; o < S::HL; o <<= 1) qc += __shfl_xor(qc, o);
+        for (int o = NVW; o < WAVE; o <<= 1) qc += __shfl_xor(qc, o);
         const float dt = m->timestep;
-        if (S::CPW == 1 && !m->impl_cross && blk_usable<NVW>(m)) {  // M + dt D block diagonal by tree
+        if (!m->impl_cross && blk_usable<NVW>(m)) {  // M + dt D block diagonal by tree
           if (lane < NVW) s.srch[lane] = lane < nv ? s.qfs[lane] + qc : 0.f;
           sync();
           if (impl2) {  // wave 1's factor
@@ -4780,13 +4512,13 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
         }
       }
       sync();
-      if (lane < nc && args.theta && live) args.theta[(size_t)b * nc * H + lane * H + t] = s.qpos[ctrl_qa];
+      if (lane < nc && args.theta) args.theta[(size_t)b * nc * H + lane * H + t] = s.qpos[ctrl_qa];
     }
   }
 
   STAMP(10);
   PROF_FLUSH
-  if (args.plant && live && run_main) {  // single-environment plant: qacc of the last step, state back
+  if (args.plant && run_main) {  // single-environment plant: qacc of the last step, state back
     if (lane < nv) args.state[ST_QACC + lane] = s.qacc[lane];
     if (args.plant & 2) {
       if (lane < m->nq) args.state[ST_QPOS + lane] = s.qpos[lane];
@@ -4797,7 +4529,7 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
     }
   }
   if (suspend) {  // not the last segment: save the state and the accumulators, no outputs
-    for (int i = lane; i < DX_NQ; i += S::HL) segs[SEG_QPOS + i] = i < S::NQW ? s.qpos[i] : 0.f;
+    for (int i = lane; i < DX_NQ; i += WAVE) segs[SEG_QPOS + i] = i < S::NQW ? s.qpos[i] : 0.f;
     if (lane < NVW) {
       segs[SEG_QVEL + lane] = s.qvel[lane];
       segs[SEG_QWS + lane] = s.qws[lane];
@@ -4808,13 +4540,11 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
       sc[0] = cost_g; sc[1] = cost_r;
       sc[2] = __int_as_float(status); sc[3] = __int_as_float(nefc_sum); sc[4] = __int_as_float(nefc_max);
     }
-#if MPCR_PACE
     if (pace && lane == pace_own) __hip_atomic_store(pace + lane, ~0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#endif
     return;
   }
   // ---- final reductions, outputs ----------------------------------------------
-  cost_c = hsum<S::CPW>(cost_c);
+  cost_c = wsum(cost_c);
   if constexpr (WPC == 2) {  // the collision wave's cost_c and truncation flag
     block_sync();  // wave 0's last step is done with the image (srch)
     if (wv == 1 && lane == 0) { s.srch[0] = cost_c; s.pad_ = status; }
@@ -4825,9 +4555,9 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
   }
   bool finite = true;
   if (lane < m->nq) finite = isfinite(s.qpos[lane]);
-  finite = hballot<S::CPW>(!finite) == 0;
+  finite = __ballot(!finite) == 0;
   if (!finite) status |= 2;
-  if (lane == 0 && live) {
+  if (lane == 0) {
     // a lost two-wave handshake (MPCR_STATUS_SYNC) voids the rollout: +inf
     // keeps it out of the argmin and the elites (a NaN would win the argmin)
     const float cost = (status & (1 << 10)) ? __builtin_inff()
@@ -4844,11 +4574,9 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
       atomicMin(args.best_key, k64);
     }
   }
-#if MPCR_PACE
   if (pace && lane == pace_own) __hip_atomic_store(pace + lane, ~0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#endif
 #ifdef MPCR_WAVETIME
-  if (lane == 0 && live && args.prof) {
+  if (lane == 0 && args.prof) {
     const unsigned long long c1 = __builtin_amdgcn_s_memtime(), t1 = __builtin_amdgcn_s_memrealtime();
     const unsigned hwid = __builtin_amdgcn_s_getreg((31 << 11) | 4), xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20);
     args.prof[4 * (size_t)b + 0] = wt_t0;
@@ -4860,195 +4588,5 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? MPCR_W_WAVES : MPCR_N_WAVES
   }
 #endif
 }
-
-
-// ---------------------------------------------------------------------------
-// launchers (the host side lives in another translation unit)
-//
-// This file is compiled twice (manipulator_mujoco_amd/build.py): MPCR_TU = 1
-// holds the single-arm kernels and the launch logic, with the fast-math
-// device flags (C3 is VALU-bound: 1.60 ms, 1.86 ms without them); MPCR_TU = 2
-// holds the dual-arm kernels, compiled without them (IEEE division / square
-// root, no reassociation): the latency-bound dual arm pays ~5 % and its fp32
-// rollouts stay within the scalar fp32 restatement's drift (C4 shard
-// well-conditioned misses 22 -> 8, worst 4.8e-3 -> 7.8e-4).
-// MPCR_TU undefined (0): everything in one unit.
-#ifndef MPCR_TU
-#define MPCR_TU 0
-#endif
-
-// Dual-arm batches up to min(this, the narrow threshold below) run two waves
-// per candidate too (rollout_kernel<32, 32, 72, true, 2>: collision, the MPR
-// flush and the manifolds beside the dynamics).  Its 29 KB image and 235
-// VGPRs leave 4 blocks per CU, so the default is 4 x 256 CUs: every candidate
-// resident in one round (measured on MI355X, H = 100: 1024 candidates 22.6 ->
-// 21.2 ms; 2048 would take two rounds, 24.5 -> 46.3 ms).  Bitwise the one-wave
-// results.  MPCR_WPC2W_MAX_N overrides.
-#ifndef MPCR_W_WPC2
-#define MPCR_W_WPC2 1
-#endif
-// extra dynamic LDS per one-wave dual-arm block (occupancy experiments only)
-#ifndef MPCR_W_DYN_LDS
-#define MPCR_W_DYN_LDS 0
-#endif
-
-#if MPCR_TU != 1
-// the dual-arm kernels' launches (rollout_launch's wide branch calls these)
-void rollout_wide_launch(int wpc, unsigned grid, hipStream_t st, const RolloutArgs& a, const DevModel* dm) {
-  if (wpc == 2)
-    hipLaunchKernelGGL((rollout_kernel<32, 32, 72, true, 2>), dim3(grid), dim3(2 * WAVE), 0, st, a, dm);
-  else
-    hipLaunchKernelGGL((rollout_kernel<32, 32, 72, true>), dim3(grid), dim3(WAVE), MPCR_W_DYN_LDS, st, a, dm);
-}
-hipError_t rollout_wide_occupancy(int* info) {
-  const void* k = reinterpret_cast<const void*>(&rollout_kernel<32, 32, 72, true>);
-  int blocks = 0;
-  hipFuncAttributes fa;
-  hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k, WAVE, MPCR_W_DYN_LDS);
-  if (e != hipSuccess) return e;
-  e = hipFuncGetAttributes(&fa, k);
-  if (e != hipSuccess) return e;
-  info[0] = blocks;
-  info[1] = (int)fa.sharedSizeBytes;
-  info[2] = fa.numRegs;
-  return hipSuccess;
-}
-#endif
-
-#if MPCR_TU != 2
-// batches up to this many candidates run the narrow variant with two waves
-// per candidate (MPCR_WPC2_MAX_N overrides; 0 disables): below one
-// candidate per SIMD pair the second wave of a SIMD is otherwise idle
-// (process-wide, atomic: read by every engine's launches, initialised once
-// from the environment when the library loads)
-static int env_int(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
-static std::atomic<int> g_wpc2_max_n{env_int("MPCR_WPC2_MAX_N", MPCR_WPC2_MAX_N_DEFAULT)};
-#ifdef MPCR_STOP_AFTER
-// attribution builds stop a wave mid-step; the two-wave kernels would leave
-// its partner at an unmatched barrier, so these builds run one wave only
-static int wpc2_max_n() { return 0; }
-#else
-static int wpc2_max_n() { return g_wpc2_max_n.load(std::memory_order_relaxed); }
-#endif
-int rollout_set_wpc2_max_n(int n) {
-  return n >= 0 ? g_wpc2_max_n.exchange(n) : wpc2_max_n();
-}
-#if MPCR_W_WPC2
-static const int g_wpc2w_max_n = env_int("MPCR_WPC2W_MAX_N", 1024);
-static int wpc2w_max_n() { return min(g_wpc2w_max_n, wpc2_max_n()); }
-#endif
-
-// RolloutArgs of candidates [off, off + n) of a launch: the per-candidate
-// pointers advanced by off (the kernel indexes them by its block)
-static RolloutArgs group_args(const RolloutArgs& a, int off, int n) {
-  RolloutArgs g = a;
-  const size_t o = (size_t)off;
-  g.n = n;
-  g.index_base = a.index_base + off;
-  const size_t in_row = a.layout == 0 ? (size_t)a.nctrl * a.nbasis : (size_t)a.nctrl * a.H;
-  g.input = a.input + o * in_row;
-  g.cost4 = a.cost4 + 4 * o;
-  const size_t th_row = (size_t)a.nctrl * a.H;
-  if (a.theta) g.theta = a.theta + o * th_row;
-  if (a.thetadot) g.thetadot = a.thetadot + o * th_row;
-  if (a.status) g.status = a.status + o;
-  if (a.trace_eef) g.trace_eef = a.trace_eef + o * a.H * 7;
-  if (a.trace_slots) g.trace_slots = a.trace_slots + o * a.H * a.nslot;
-  g.jx = a.jx + o * (SmemW::MAXEFC - SmemW::JL) * SmemW::LDJ;
-  g.hints = a.hints + o * SmemW::NHINT * 2;
-  g.mslab = a.mslab + o * SmemW::NVW * SmemW::LD;
-  g.tdscratch = a.tdscratch + o * th_row;
-  g.slot_prev = a.slot_prev + o * (a.nslot > 0 ? a.nslot : 1);
-  g.seg_state = a.seg_state + o * SEG_STRIDE;
-  return g;
-}
-
-// whether rollout_launch runs a batch as horizon segments, and over how many
-// candidate groups (*G)
-static bool seg_plan(bool wide, const RolloutArgs& a, unsigned grid, int groups, bool streams, int* G) {
-  if (!wide) return false;
-#if MPCR_W_WPC2
-  if ((int)grid <= wpc2w_max_n()) return false;
-#endif
-  if (!(a.seg > 0 && a.seg < a.H && a.seg_state && !a.plant && !a.dbg && (int)grid > a.seg_min_n)) return false;
-  *G = groups > 1 && streams && (int)grid >= 2 * groups ? groups : 1;
-  return true;
-}
-
-int rollout_dispatches(bool wide, const RolloutArgs& a, unsigned grid, int groups, bool streams) {
-  int G = 1;
-  if (grid == 0) return 0;
-  if (!seg_plan(wide, a, grid, groups, streams, &G)) return 1;
-  return G * ((a.H + a.seg - 1) / a.seg);
-}
-
-void rollout_launch(bool wide, const RolloutArgs& a0, const DevModel* dm, unsigned grid, size_t dyn_lds,
-                    hipStream_t st, int groups, hipStream_t* gstream, hipEvent_t* gev) {
-  RolloutArgs a = a0;
-  a.t0 = 0;
-  a.t1 = a.H;
-  int G = 1;
-#if MPCR_W_WPC2
-  if (wide && (int)grid <= wpc2w_max_n())
-    rollout_wide_launch(2, grid, st, a, dm);
-  else
-#endif
-  if (wide) {
-    if (seg_plan(wide, a, grid, groups, gstream && gev, &G)) {
-      // horizon segments over candidate groups on their own streams: each
-      // group's segments in its stream's order, the groups overlapping
-      if (G > 1) {
-        (void)hipEventRecord(gev[0], st);
-        for (int g = 0; g < G; g++) (void)hipStreamWaitEvent(gstream[g], gev[0], 0);
-      }
-      const int per = ((int)grid + G - 1) / G;
-      for (int g = 0; g < G; g++) {
-        const int off = g * per, ng = min(per, (int)grid - off);
-        if (ng <= 0) break;
-        RolloutArgs ga = G > 1 ? group_args(a, off, ng) : a;
-        hipStream_t gs = G > 1 ? gstream[g] : st;
-        for (int t0 = 0; t0 < a.H; t0 += a.seg) {
-          ga.t0 = t0;
-          ga.t1 = min(a.H, t0 + a.seg);
-          rollout_wide_launch(1, ng, gs, ga, dm);
-        }
-      }
-      if (G > 1)
-        for (int g = 0; g < G; g++) {
-          (void)hipEventRecord(gev[1 + g], gstream[g]);
-          (void)hipStreamWaitEvent(st, gev[1 + g], 0);
-        }
-    } else {
-      rollout_wide_launch(1, grid, st, a, dm);
-    }
-  } else {
-    if constexpr (SmemN::CPW == 1) {
-      if ((int)grid <= wpc2_max_n()) {
-        hipLaunchKernelGGL((rollout_kernel<16, 16, 24, false, 2>), dim3(grid), dim3(2 * WAVE), 0, st, a, dm);
-        return;
-      }
-    }
-    hipLaunchKernelGGL((rollout_kernel<16, 16, 24, false>), dim3((grid + SmemN::CPW - 1) / SmemN::CPW), dim3(WAVE),
-                       dyn_lds, st, a, dm);
-  }
-}
-
-hipError_t rollout_occupancy(int* info, size_t dyn_lds) {
-  const void* k = reinterpret_cast<const void*>(&rollout_kernel<16, 16, 24, false>);
-  int blocks = 0;
-  hipFuncAttributes fa;
-  hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k, WAVE, dyn_lds);
-  if (e != hipSuccess) return e;
-  e = hipFuncGetAttributes(&fa, k);
-  if (e != hipSuccess) return e;
-  info[0] = blocks;
-  info[1] = (int)fa.sharedSizeBytes;
-  info[2] = fa.numRegs;
-  return rollout_wide_occupancy(info + 3);
-}
-#endif  // MPCR_TU != 2
 
 }  // namespace mpcr

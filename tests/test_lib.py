@@ -152,3 +152,15 @@ def test_comm_entry_points_fail_cleanly():
     rc = lib.mpcr_comm_unique_id(uid)
     assert rc == 0 or (rc == -3 and lib.mpcr_last_error())
     lib.mpcr_comm_free(None)
+
+
+def test_build_deps_list_every_native_source():
+    """A source or header missing from build.DEPS would leave a stale
+    libmpcr.so after an edit (the rebuild check) and a stale source_hash()."""
+    from manipulator_mujoco_amd import build
+    deps = {os.path.realpath(d) for d in build.DEPS}
+    for d in (build.CSRC, os.path.join(ROOT, "include")):
+        for dirpath, _, files in os.walk(d):
+            for f in files:
+                assert os.path.realpath(os.path.join(dirpath, f)) in deps, os.path.join(dirpath, f)
+    assert all(os.path.exists(d) for d in build.DEPS)

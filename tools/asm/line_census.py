@@ -1,9 +1,10 @@
 """Static instruction census of rollout_kernel by source region (diagnostic).
 
 Compile the device code with line tables, e.g.
-    hipcc --offload-arch=gfx950 --cuda-device-only -S -O3 -gline-tables-only <FLAGS> -o ship.s csrc/rollout.hip
+    hipcc --offload-arch=gfx950 --cuda-device-only -S -O3 -gline-tables-only <FLAGS> -o ship.s csrc/rollout_narrow.hip
     python tools/asm/line_census.py ship.s [narrow|wide]
-Each instruction is charged to the last rollout.hip line (.loc file 0) seen
+(csrc/rollout_wide.hip for the wide kernels.)
+Each instruction is charged to the last rollout.hip line (.loc of its .file number) seen
 before it; lines are grouped into the enclosing __device__ helper, or, inside
 the kernel body, into the phase between two STAMP(k) markers.  Loop bodies
 count once (static), so multiply by trip counts when reading.
@@ -46,6 +47,7 @@ def region(line):
 
 
 lines = open(path).read().splitlines()
+kfile = next(l.split()[1] for l in lines if l.strip().startswith(".file") and "/rollout.hip" in l)
 start = next(i for i, l in enumerate(lines) if l.startswith("_ZN4mpcr14rollout_kernel" + tag) and ":" in l)
 end = next(i for i in range(start, len(lines)) if lines[i].strip().startswith(".Lfunc_end"))
 cur = 0
@@ -54,7 +56,7 @@ for l in lines[start:end]:
     s = l.strip()
     if s.startswith(".loc"):
         f = s.split()
-        if f[1] == "0":
+        if f[1] == kfile:
             cur = int(f[2])
         continue
     if not s or s.startswith(";") or s.startswith(".") or s.endswith(":"):

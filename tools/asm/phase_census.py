@@ -2,7 +2,7 @@
 stamps (s_memtime).  Diagnostic: tells which code a phase's dynamic count
 comes from (loops are counted once).
 
-    hipcc --offload-arch=gfx950 --cuda-device-only -S -O3 ... -DMPCR_PROFILE -o prof.s rollout.hip
+    hipcc --offload-arch=gfx950 --cuda-device-only -S -O3 ... -DMPCR_PROFILE -o prof.s rollout_narrow.hip (or rollout_wide.hip)
     python tools/asm/phase_census.py prof.s [narrow|wide]
 """
 import re

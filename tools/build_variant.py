@@ -1,5 +1,5 @@
 """Build libmpcr.so with extra compiler flags into build_variants/<name>.so
-(for tools/ab_session.sh interleaved timing).
+(timed with tools/ab_time.py, compared with tools/lib_bitwise.py).
 
     python tools/build_variant.py NAME [--precise] [extra hipcc flags...]
 --precise drops the fast-math device flags (IEEE division / sqrt, no reassociation).

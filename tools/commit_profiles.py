@@ -3,7 +3,7 @@ profiles/ and record, in profiles/<tag>_pmc_manifest.json, the libmpcr.so
 source hash of the build they were taken from (manipulator_mujoco_amd.build
 .source_hash) -- bench.py attaches committed counters only to a run of that
 same build.  The hash is the one the session itself recorded
-(gpurun_out/<tag>/source_hash.txt, tools/gpu_session_r05.sh); the script
+(source_hash.txt in that directory); the script
 refuses to commit when the checkout no longer hashes to it (an
 edit between the session and this script would attach the counters to a
 build they were not taken from).
