@@ -56,7 +56,10 @@ extern "C" {
    table, which the engine builds (mpcr_model_hull_starts).  3: bit 10 reports a lost two-wave handshake
    (MPCR_STATUS_SYNC), so rows-summed moved to bit 11.  2 (round 4): the
    max-rows field widened to 8 bits (version 1: 6 bits << 2, sum << 8).
-   Decode with the accessors below, not raw shifts. */
+   Decode with the accessors below, not raw shifts.
+   The multi-problem entry points (mpcr_rollout_cost_multi, mpcr_topk_multi,
+   mpcr_cem_set_problems, mpcr_cem_*_multi) are backward-compatible additions:
+   no existing signature, layout or result changed, so the version stays 4. */
 #define MPCR_ABI_VERSION 4
 
 /* the per-candidate status word of mpcr_rollout_cost / _dp */
@@ -185,6 +188,21 @@ int mpcr_rollout_cost_dp(mpcr_engine* e, const float* input, int layout, int n, 
                          float* cost4, float* theta, float* thetadot, uint64_t* best_key, int index_base,
                          int* status, int flags, void* stream);
 
+/* Several independent problems in one call: problem p of nprob owns
+   candidates [p n_per, (p + 1) n_per) of every per-candidate array (input,
+   cost4, theta, thetadot, status: nprob n_per rows), reads its own block
+   params + 20 p (the mpcr_rollout_cost_dp layout) and reduces into
+   best_keys[p] (nullable) with the low word index_base + (index within the
+   problem), so each key decodes like a single call's.  Bitwise what nprob
+   mpcr_rollout_cost_dp calls on the slices compute, in one grid:
+   compute_cem's rollout (mjx_planner.py:348-354, 395) for nprob start states
+   / targets / weight triples at once.  Device pointers only
+   (MPCR_F_DEVICE_PTRS); nprob, n_per >= 1 and nprob n_per <= max_n;
+   MPCR_F_RESET_BEST resets all nprob keys.  Graph-capturable. */
+int mpcr_rollout_cost_multi(mpcr_engine* e, const float* input, int layout, int nprob, int n_per,
+                            const float* params, float* cost4, float* theta, float* thetadot, uint64_t* best_keys,
+                            int index_base, int* status, int flags, void* stream);
+
 /* Closed-loop plant: one environment of the model, stepped by the rollout
    kernel (fp32 state resident on the device).  Created at the template
    state (qpos_init, qvel_init, zero warm start). */
@@ -217,6 +235,14 @@ void mpcr_best_key_decode(uint64_t key, int* idx, float* cost);
    k <= min(n, 4096).  Host pointers: n <= max_n and stride <= 4. */
 int mpcr_topk(mpcr_engine* e, const float* cost, int stride, int n, int k, int* idx_out, int flags,
               void* stream);
+
+/* mpcr_topk for nprob problems in one launch (one workgroup each): problem p
+   selects among cost[(p n_per + i) stride], i < n_per, and writes its k
+   indices, local to the problem, to idx_out + p k (compute_ellite_samples,
+   mjx_planner.py:305-310, per problem).  Device pointers only;
+   k <= min(n_per, 4096), nprob n_per <= max_n. */
+int mpcr_topk_multi(mpcr_engine* e, const float* cost, int stride, int nprob, int n_per, int k, int* idx_out,
+                    int flags, void* stream);
 
 /* ---- the CEM distribution step (device pointers only: MPCR_F_DEVICE_PTRS) ----
    num_dof <= 8 joints, nbasis = 11 (order-10 Bernstein), P/Pdot/Pddot
@@ -256,6 +282,35 @@ int mpcr_project(mpcr_cem* c, const float* xi, const float* b_eq, int beq_stride
 int mpcr_cem_update(mpcr_cem* c, const float* xi, int n, const float* cost, int stride, const int* elite_idx, int k,
                     float lamda, float alpha_mean, float alpha_cov, float reg, float* mean, float* cov, int flags,
                     void* stream);
+
+/* ---- several problems per call: one workgroup (factor, update) or one grid
+   row (sample/project) per problem, each bitwise the single-problem call on
+   its slice.  Problem p owns rows [p n_per, (p + 1) n_per) of xi / cost. ----
+   Room for nprob Cholesky factors in the context (1 after mpcr_cem_create).
+   Allocates, so call it outside a graph capture; it voids earlier factors. */
+int mpcr_cem_set_problems(mpcr_cem* c, int nprob);
+/* mpcr_cem_factor of cov + p nv^2 for every p < nprob (<= the set_problems
+   count): the Cholesky of jax.random.multivariate_normal, mjx_planner.py:312-316 */
+int mpcr_cem_factor_multi(mpcr_cem* c, const float* cov, int nprob, float reg, int flags, void* stream);
+/* mpcr_cem_sample_project for nprob problems of n_per candidates: problem p
+   samples around mean + p nv (NULL: reads xi_in) with factor p, Philox key
+   seed + p seed_step and counter word 0 = index_base + (index within the
+   problem) -- the draws of a single call with that seed; seed_step = 0 gives
+   every problem the same draws -- and projects with its own boundary row
+   b_eq + 5 nd p, shared by its candidates (compute_xi_samples +
+   compute_projection_filter, mjx_planner.py:312-316, 180-249).  Sampling
+   needs a mpcr_cem_factor_multi call that covered nprob problems. */
+int mpcr_cem_sample_project_multi(mpcr_cem* c, int nprob, int n_per, const float* mean, uint64_t seed,
+                                  uint64_t seed_step, uint64_t counter, int index_base, const float* xi_in,
+                                  float* xi_samples, const float* b_eq, int maxiter, const float* bounds, float rho,
+                                  float* xi_out, int flags, void* stream);
+/* mpcr_cem_update per problem: elite_idx + p k holds problem p's k indices
+   local to the problem (mpcr_topk_multi); mean + p nv and cov + p nv^2 are
+   updated in place (compute_mean_cov / comp_prod, mjx_planner.py:318-335).
+   k <= min(n_per, 4096). */
+int mpcr_cem_update_multi(mpcr_cem* c, const float* xi, int nprob, int n_per, const float* cost, int stride,
+                          const int* elite_idx, int k, float lamda, float alpha_mean, float alpha_cov, float reg,
+                          float* mean, float* cov, int flags, void* stream);
 
 /* ---- multi-GPU exchange over RCCL / xGMI (SURVEY.md §8b "later":
    mpcr_comm_init; §8e).  One process (or host thread) per GPU, candidates

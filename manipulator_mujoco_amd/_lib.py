@@ -30,6 +30,11 @@ EXPORTS = (
     "mpcr_rollout_occupancy", "mpcr_set_two_wave_max_n", "mpcr_engine_dispatches", "mpcr_comm_unique_id", "mpcr_comm_init", "mpcr_comm_free", "mpcr_comm_allreduce_key",
     "mpcr_comm_allgather", "mpcr_comm_gather_elites", "mpcr_model_hull_starts", "mpcr_set_hull_start_scramble",
 )
+# the multi-problem additions: a library built before them (MPCR_LIB, A/B runs
+# against an older build) still loads; calling one there raises AttributeError
+_MULTI = ("mpcr_rollout_cost_multi", "mpcr_topk_multi", "mpcr_cem_set_problems", "mpcr_cem_factor_multi",
+          "mpcr_cem_sample_project_multi", "mpcr_cem_update_multi")
+EXPORTS += _MULTI
 _VOID = ("mpcr_last_error", "mpcr_model_free", "mpcr_engine_free", "mpcr_best_key_decode", "mpcr_cem_free",
          "mpcr_plant_free", "mpcr_comm_free")
 
@@ -104,7 +109,21 @@ def load():
     lib.mpcr_comm_gather_elites.argtypes = [vp, vp, vp, i, i, i, vp, vp, vp]
     lib.mpcr_model_hull_starts.argtypes = [vp, i, P(ctypes.c_int32), P(ctypes.c_int32), P(ctypes.c_uint8), ctypes.c_int64]
     lib.mpcr_set_hull_start_scramble.argtypes = [u64]
+    multi = {
+        "mpcr_rollout_cost_multi": [vp, vp, i, i, i, vp, vp, vp, vp, vp, i, vp, i, vp],
+        "mpcr_topk_multi": [vp, vp, i, i, i, i, vp, i, vp],
+        "mpcr_cem_set_problems": [vp, i],
+        "mpcr_cem_factor_multi": [vp, vp, i, f, i, vp],
+        "mpcr_cem_sample_project_multi": [vp, i, i, vp, u64, u64, u64, i, vp, vp, vp, i, P(f), f, vp, i, vp],
+        "mpcr_cem_update_multi": [vp, vp, i, i, vp, i, vp, i, f, f, f, f, vp, vp, i, vp],
+    }
+    have_multi = hasattr(lib, _MULTI[0])
+    for name, at in multi.items():
+        if have_multi:
+            getattr(lib, name).argtypes = at
     for name in EXPORTS + ("mpcr_rollout_trace", "mpcr_plant_step_debug", "mpcr_plant_dbg_size"):
+        if name in _MULTI and not have_multi:
+            continue
         if name not in _VOID:
             getattr(lib, name).restype = i
     lib.mpcr_model_hull_starts.restype = ctypes.c_int64

@@ -41,7 +41,8 @@ class CemContext:
     """Projection tables (basis rows, KKT inverse) + the Cholesky factor for
     one (num_dof, horizon) planner on one device."""
 
-    def __init__(self, P, Pdot, Pddot, num_dof: int, max_n: int, device: int = 0, qinv=None):
+    def __init__(self, P, Pdot, Pddot, num_dof: int, max_n: int, device: int = 0, qinv=None,
+                 num_problems: int = 1):
         lib = _lib.load()
         P, Pdot, Pddot = (np.ascontiguousarray(x, dtype=np.float64) for x in (P, Pdot, Pddot))
         if P.shape[1] != NBASIS:
@@ -62,6 +63,9 @@ class CemContext:
                                   Pddot.ctypes.data, q.ctypes.data if q is not None else None, self.max_n,
                                   ctypes.byref(h)))
         self.handle = h
+        self.num_problems = int(num_problems)
+        if self.num_problems != 1:  # room for one Cholesky factor per problem (the *_multi calls)
+            check(lib.mpcr_cem_set_problems(self.handle, self.num_problems))
 
     def __del__(self):
         try:
@@ -123,6 +127,82 @@ class CemContext:
                                           self._stream(xi, stream)))
 
 
+    # ---- several problems per call: leading problem axis on every tensor ----
+    def factor_multi(self, cov, reg: float = 0.003, stream=None):
+        """One Cholesky factor per problem: cov is (nprob, nvar, nvar)."""
+        import torch
+        _dev(cov, torch.float32, "cov")
+        if cov.dim() != 3:
+            raise ValueError("cov must be (nprob, nvar, nvar)")
+        check(_lib.load().mpcr_cem_factor_multi(self.handle, _ptr(cov), int(cov.shape[0]), float(reg),
+                                                MPCR_F_DEVICE_PTRS, self._stream(cov, stream)))
+
+    def sample_project_multi(self, nprob, n_per, mean, seed, counter, b_eq, maxiter, bounds, rho=1.0, seed_step=0,
+                             xi_samples=None, out=None, xi_in=None, index_base=0, stream=None):
+        """``sample_project`` for nprob problems of n_per candidates in one
+        launch: mean (nprob, nvar) or None with xi_in (nprob, n_per, nvar),
+        b_eq (nprob, 5 num_dof); problem p draws with the Philox key
+        ``seed + p * seed_step``.  Returns the projected (nprob, n_per, nvar)
+        tensor, bitwise the single calls on the slices."""
+        import torch
+        ref = mean if mean is not None else xi_in
+        if ref is None:
+            raise ValueError("need mean or xi_in")
+        if out is None:
+            out = torch.empty((nprob, n_per, self.nvar), dtype=torch.float32, device=ref.device)
+        for name, t in (("mean", mean), ("xi_in", xi_in), ("xi_samples", xi_samples), ("out", out),
+                        ("b_eq", b_eq)):
+            if t is not None:
+                _dev(t, torch.float32, name)
+        for name, t, numel in (("mean", mean, nprob * self.nvar), ("b_eq", b_eq, nprob * 5 * self.num_dof),
+                               ("xi_in", xi_in, nprob * n_per * self.nvar), ("out", out, nprob * n_per * self.nvar),
+                               ("xi_samples", xi_samples, nprob * n_per * self.nvar)):
+            if t is not None and t.numel() != numel:
+                raise ValueError(f"{name} has {t.numel()} elements, expected {numel}")
+        bnd = (ctypes.c_float * 3)(*[float(b) for b in bounds])
+        u64 = lambda v: ctypes.c_uint64(int(v) & (2**64 - 1))  # noqa: E731
+        check(_lib.load().mpcr_cem_sample_project_multi(
+            self.handle, int(nprob), int(n_per), _ptr(mean), u64(seed), u64(seed_step), u64(counter), int(index_base),
+            _ptr(xi_in), _ptr(xi_samples), _ptr(b_eq), int(maxiter), bnd, float(rho), _ptr(out), MPCR_F_DEVICE_PTRS,
+            self._stream(ref, stream)))
+        return out
+
+    def update_multi(self, xi, cost, stride, elite_idx, lamda, alpha_mean, alpha_cov, mean, cov, reg=1e-4,
+                     stream=None):
+        """``update`` per problem, in place: xi (nprob, n_per, nvar), cost
+        (nprob, n_per[, stride]), elite_idx (nprob, k) local indices
+        (``topk_multi``), mean (nprob, nvar), cov (nprob, nvar, nvar)."""
+        import torch
+        _dev(xi, torch.float32, "xi"); _dev(cost, torch.float32, "cost")
+        _dev(elite_idx, torch.int32, "elite_idx"); _dev(mean, torch.float32, "mean"); _dev(cov, torch.float32, "cov")
+        if xi.dim() != 3 or elite_idx.dim() != 2 or elite_idx.shape[0] != xi.shape[0]:
+            raise ValueError("xi must be (nprob, n_per, nvar) and elite_idx (nprob, k)")
+        nprob = int(xi.shape[0])
+        if mean.numel() != nprob * self.nvar or cov.numel() != nprob * self.nvar * self.nvar:
+            raise ValueError("mean must be (nprob, nvar) and cov (nprob, nvar, nvar)")
+        check(_lib.load().mpcr_cem_update_multi(self.handle, _ptr(xi), nprob, int(xi.shape[1]), _ptr(cost),
+                                                int(stride), _ptr(elite_idx), int(elite_idx.shape[1]), float(lamda),
+                                                float(alpha_mean), float(alpha_cov), float(reg), _ptr(mean), _ptr(cov),
+                                                MPCR_F_DEVICE_PTRS, self._stream(xi, stream)))
+
+
+def topk_multi(engine, cost, nprob, k, stride=1, out=None, stream=None):
+    """``topk`` for nprob problems in one launch: cost holds nprob * n_per
+    entries of ``stride`` floats, problem p owning entries [p n_per,
+    (p + 1) n_per); returns (nprob, k) int32 indices local to each problem."""
+    import torch
+    _dev(cost, torch.float32, "cost")
+    n = cost.numel() // stride
+    if nprob < 1 or n % nprob:
+        raise ValueError(f"{n} costs do not split evenly over nprob={nprob} problems")
+    if out is None:
+        out = torch.empty((nprob, k), dtype=torch.int32, device=cost.device)
+    st = stream if stream is not None else torch.cuda.current_stream(cost.device).cuda_stream
+    check(_lib.load().mpcr_topk_multi(engine.handle, _ptr(cost), int(stride), int(nprob), n // nprob, int(k),
+                                      _ptr(out), MPCR_F_DEVICE_PTRS, ctypes.c_void_p(st)))
+    return out
+
+
 def topk(engine, cost, k, stride=1, out=None, stream=None):
     """Indices of the k smallest of cost[i*stride] in stable-argsort order
     (NaN last) through ``mpcr_topk`` on ``engine``'s device."""
@@ -137,4 +217,4 @@ def topk(engine, cost, k, stride=1, out=None, stream=None):
     return out
 
 
-__all__ = ["CemContext", "topk", "NBASIS"]
+__all__ = ["CemContext", "topk", "topk_multi", "NBASIS"]

@@ -47,6 +47,13 @@ struct ProjArgs {
   unsigned long long seed, counter;
   int n, nd, H, maxiter, beq_stride;
   int index_base;         // global index of candidate 0 (Philox counter word 0)
+  // several problems (mpcr_cem_sample_project_multi): blockIdx.y = problem p
+  // of n candidates each -- rows p n + i of xi_in / xi_samples / xi_out, its
+  // own mean + p nv, L + p LD^2 and beq + p beq_pstride, Philox key
+  // seed + p seed_step and counter word 0 index_base + i.  A single call has
+  // one problem (gridDim.y = 1, every offset 0).
+  unsigned long long seed_step;
+  int beq_pstride;
   float bound[3];         // v_max, a_max, p_max
   float rho;
 };
@@ -93,8 +100,11 @@ __global__ void __launch_bounds__(64 * PJ_MAXD) sample_project_kernel(ProjArgs a
   const int lane = threadIdx.x & 63;
   const int j = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform joint
   const int cl = lane & (PJ_CPW - 1), part = lane / PJ_CPW;  // candidate in the workgroup, row part
-  const int cand = blockIdx.x * PJ_CPW + cl;
+  const int cand = blockIdx.x * PJ_CPW + cl;  // index within the problem
   const bool live = cand < a.n;
+  const int prob = blockIdx.y;  // wave-uniform: the tables' loads below stay scalar
+  const size_t grow = (size_t)prob * a.n + cand;  // the candidate's row
+  const unsigned long long seed = a.seed + prob * a.seed_step;
   float* row = pj_smem + cl * RS;  // this candidate's padded vector (rhs / z)
   const int jb = j * PJ_BLK;
   // the constraint rows X (identical for every joint, candidate and ADMM
@@ -110,7 +120,7 @@ __global__ void __launch_bounds__(64 * PJ_MAXD) sample_project_kernel(ProjArgs a
 #pragma unroll
     for (int q = 0; q < 3; q++) {
       uint32_t c[4] = {(uint32_t)(cand + a.index_base), (uint32_t)(j * 3 + q), (uint32_t)a.counter, (uint32_t)(a.counter >> 32)};
-      philox4(c, (uint32_t)a.seed, (uint32_t)(a.seed >> 32));
+      philox4(c, (uint32_t)seed, (uint32_t)(seed >> 32));
       box_muller(c[0], c[1], z[4 * q + 0], z[4 * q + 1]);
       box_muller(c[2], c[3], z[4 * q + 2], z[4 * q + 3]);
     }
@@ -123,12 +133,14 @@ __global__ void __launch_bounds__(64 * PJ_MAXD) sample_project_kernel(ProjArgs a
     // xi[r] = mean[r] + sum_{c <= r} L[r][c] z[c]; L is stored transposed
     // (LT[c][r]) so the 11 coefficients of one c are contiguous and uniform.
     const int LD = nd * PJ_BLK;
+    const float* const mean = a.mean + (size_t)prob * NV;
+    const float* const Lp = a.L + (size_t)prob * LD * LD;
 #pragma unroll
-    for (int r = 0; r < PJ_NB; r++) xi[r] = a.mean[j * PJ_NB + r];
+    for (int r = 0; r < PJ_NB; r++) xi[r] = mean[j * PJ_NB + r];
     for (int j2 = 0; j2 <= j; j2++) {
       for (int c = 0; c < PJ_NB; c++) {
         const float zc = row[j2 * PJ_BLK + c];
-        const float* lt = a.L + (size_t)(j2 * PJ_BLK + c) * LD + jb;
+        const float* lt = Lp + (size_t)(j2 * PJ_BLK + c) * LD + jb;
 #pragma unroll
         for (int r = 0; r < PJ_NB; r++) xi[r] = fmaf(lt[r], zc, xi[r]);
       }
@@ -136,7 +148,7 @@ __global__ void __launch_bounds__(64 * PJ_MAXD) sample_project_kernel(ProjArgs a
     __syncthreads();  // row[] is reused for the right-hand side below
   } else {
 #pragma unroll
-    for (int r = 0; r < PJ_NB; r++) xi[r] = live ? a.xi_in[(size_t)cand * NV + j * PJ_NB + r] : 0.f;
+    for (int r = 0; r < PJ_NB; r++) xi[r] = live ? a.xi_in[grow * NV + j * PJ_NB + r] : 0.f;
   }
 
   float p[PJ_NB];
@@ -147,7 +159,7 @@ __global__ void __launch_bounds__(64 * PJ_MAXD) sample_project_kernel(ProjArgs a
     float qb[PJ_NB];
 #pragma unroll
     for (int r = 0; r < PJ_NB; r++) qb[r] = 0.f;
-    const float* be = a.beq + (live ? (size_t)cand * a.beq_stride : 0);
+    const float* be = a.beq + (size_t)prob * a.beq_pstride + (live ? (size_t)cand * a.beq_stride : 0);
     for (int m = 0; m < 5 * nd; m++) {
       const float bm = be[m];
       const float* qt = a.QbT + (size_t)m * nd * PJ_BLK + jb;
@@ -258,10 +270,10 @@ __global__ void __launch_bounds__(64 * PJ_MAXD) sample_project_kernel(ProjArgs a
   if (live && part == 0) {
     if (a.mean && a.xi_samples) {
 #pragma unroll
-      for (int r = 0; r < PJ_NB; r++) a.xi_samples[(size_t)cand * NV + j * PJ_NB + r] = xi[r];
+      for (int r = 0; r < PJ_NB; r++) a.xi_samples[grow * NV + j * PJ_NB + r] = xi[r];
     }
 #pragma unroll
-    for (int r = 0; r < PJ_NB; r++) a.xi_out[(size_t)cand * NV + j * PJ_NB + r] = p[r];
+    for (int r = 0; r < PJ_NB; r++) a.xi_out[grow * NV + j * PJ_NB + r] = p[r];
   }
 }
 
@@ -269,11 +281,14 @@ __global__ void __launch_bounds__(64 * PJ_MAXD) sample_project_kernel(ProjArgs a
 // Cholesky of cov + reg I (nv x nv, fp32, right-looking in LDS, one block),
 // written transposed and padded for sample_project_kernel: LT[c][r] = L[r][c]
 // at padded indices.  A non-PD input yields NaN like jnp.linalg.cholesky.
+// One workgroup per problem: block p factors cov + p nv^2 into LT + p LD^2.
 __global__ void __launch_bounds__(256) cholesky_kernel(const float* __restrict__ cov, int nd, float reg,
                                                         float* __restrict__ LT) {
   __shared__ float A[PJ_MAXD * PJ_NB][PJ_MAXD * PJ_NB + 1];
   __shared__ float Ld[PJ_MAXD * PJ_NB];  // the factor's diagonal (A's diagonal is never overwritten)
   const int nv = nd * PJ_NB, LD = nd * PJ_BLK;
+  cov += (size_t)blockIdx.x * nv * nv;
+  LT += (size_t)blockIdx.x * LD * LD;
   for (int i = threadIdx.x; i < nv * nv; i += blockDim.x) {
     const int r = i / nv, c = i % nv;
     A[r][c] = cov[i] + (r == c ? reg : 0.f);
@@ -308,7 +323,9 @@ __global__ void __launch_bounds__(256) cholesky_kernel(const float* __restrict__
 // ties by index, NaN last; -0 == +0).  One 1024-thread block: 4 radix-select
 // passes on the order-preserving 32-bit key find the k-th key T, ties at T are
 // taken lowest-index first by a block scan in index order, and the k winners
-// are bitonic-sorted on (key << 32 | index) in LDS.
+// are bitonic-sorted on (key << 32 | index) in LDS.  One workgroup per problem:
+// block p selects among cost rows [p n, (p + 1) n) and writes k indices local
+// to its problem at idx_out + p k.
 __device__ __forceinline__ uint32_t ord_key_nanlast(float c) {
   if (isnan(c)) return 0xFFFFFFFFu;
   const uint32_t u = __float_as_uint(c + 0.0f);  // -0 -> +0
@@ -322,6 +339,8 @@ __global__ void __launch_bounds__(1024) topk_kernel(const float* __restrict__ co
   __shared__ uint32_t wtot[16];
   __shared__ uint32_t s_prefix, s_krem, s_cnt;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  cost += (size_t)blockIdx.x * n * stride;
+  idx_out += (size_t)blockIdx.x * k;
   if (tid == 0) { s_prefix = 0; s_krem = (uint32_t)k; s_cnt = 0; }
   for (int pass = 0; pass < 4; pass++) {
     const int shift = 24 - 8 * pass;
@@ -391,10 +410,12 @@ __global__ void __launch_bounds__(1024) topk_kernel(const float* __restrict__ co
 
 // ---------------------------------------------------------------------------
 // weighted mean / covariance of the elites (compute_mean_cov, :325-335), one
-// 1024-thread block; mean and cov are updated in place.
+// 1024-thread block per problem; mean and cov are updated in place.  Block p
+// reads rows [p n, (p + 1) n) of xi and cost through its k local elite indices
+// at idx + p k and updates mean + p nv, cov + p nv^2.
 constexpr int CU_CHUNK = 64;
 
-__global__ void __launch_bounds__(1024) cem_update_kernel(const float* __restrict__ xi, int nv,
+__global__ void __launch_bounds__(1024) cem_update_kernel(const float* __restrict__ xi, int n, int nv,
                                                            const float* __restrict__ cost, int stride,
                                                            const int* __restrict__ idx, int k, float lamda,
                                                            float alpha_mean, float alpha_cov, float reg,
@@ -406,6 +427,11 @@ __global__ void __launch_bounds__(1024) cem_update_kernel(const float* __restric
   __shared__ float mnew[PJ_MAXD * PJ_NB];
   __shared__ float s_cmin, s_sw;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  xi += (size_t)blockIdx.x * n * nv;
+  cost += (size_t)blockIdx.x * n * stride;
+  idx += (size_t)blockIdx.x * k;
+  mean += (size_t)blockIdx.x * nv;
+  cov += (size_t)blockIdx.x * nv * nv;
   // c_min = jnp.min(cost_ellite): NaN propagates
   float cm = INFINITY;
   bool nan = false;

@@ -62,7 +62,7 @@ __global__ void __launch_bounds__(256) argmin_kernel(const float* __restrict__ c
   if ((threadIdx.x & 63) == 0) atomicMin(key, best);
 }
 
-__global__ void fill_u64(unsigned long long* p, unsigned long long v) { *p = v; }
+__global__ void fill_u64(unsigned long long* p, unsigned long long v) { p[blockIdx.x] = v; }  // one block per word
 
 }  // namespace mpcr
 
@@ -1212,6 +1212,7 @@ struct Launch {
   int* status = nullptr;
   float* dbg = nullptr;
   bool reset_key = false;
+  int nprob = 1, prob_n = 0;  // mpcr_rollout_cost_multi: problems of prob_n candidates (0: one problem)
 };
 
 static int launch_rollout(mpcr_engine* e, const Launch& l, hipStream_t st) {
@@ -1247,8 +1248,10 @@ static int launch_rollout(mpcr_engine* e, const Launch& l, hipStream_t st) {
   a.seg_state = e->d_seg;
   a.seg = e->d_seg ? e->seg_steps : 0;
   a.seg_min_n = e->seg_min_n;
+  a.prob_n = l.prob_n;
+  a.prob_off = 0;
   std::memcpy(a.par, l.par, sizeof(a.par));
-  if (l.key && l.reset_key) hipLaunchKernelGGL(fill_u64, dim3(1), dim3(1), 0, st, l.key, ~0ull);
+  if (l.key && l.reset_key) hipLaunchKernelGGL(fill_u64, dim3(l.nprob), dim3(1), 0, st, l.key, ~0ull);
   rollout_launch(e->wide, a, (const DevModel*)e->d_model, l.n, st, e->seg_groups, e->seg_stream,
                  e->seg_event);
   HIPCHK(hipGetLastError());
@@ -1334,6 +1337,30 @@ extern "C" int mpcr_rollout_cost_dp(mpcr_engine* e, const float* input, int layo
   l.layout = layout; l.n = n; l.index_base = index_base; l.dpar = params;
   l.in = input; l.cost4 = cost4; l.theta = theta; l.thetadot = thetadot;
   l.key = reinterpret_cast<unsigned long long*>(best_key); l.status = status;
+  l.reset_key = (flags & MPCR_F_RESET_BEST) != 0;
+  int rc = launch_rollout(e, l, st);
+  if (rc) return rc;
+  if (flags & MPCR_F_SYNC) HIPCHK(hipStreamSynchronize(st));
+  return MPCR_OK;
+}
+
+extern "C" int mpcr_rollout_cost_multi(mpcr_engine* e, const float* input, int layout, int nprob, int n_per,
+                                       const float* params, float* cost4, float* theta, float* thetadot,
+                                       uint64_t* best_keys, int index_base, int* status, int flags, void* stream) {
+  if (!e) return fail(MPCR_EINVAL, "null argument");
+  if (!(flags & MPCR_F_DEVICE_PTRS)) return fail(MPCR_EINVAL, "mpcr_rollout_cost_multi takes device pointers");
+  if (nprob < 1 || n_per < 1) return fail(MPCR_EINVAL, "nprob=%d, n_per=%d: both must be >= 1", nprob, n_per);
+  if ((long long)nprob * n_per > e->max_n)
+    return fail(MPCR_EINVAL, "nprob=%d x n_per=%d exceeds max_n=%d", nprob, n_per, e->max_n);
+  if (layout != MPCR_LAYOUT_XI && layout != MPCR_LAYOUT_THETADOT) return fail(MPCR_EINVAL, "bad layout %d", layout);
+  if (!input || !params || !cost4) return fail(MPCR_EINVAL, "null argument");
+  HIPCHK(hipSetDevice(e->device));
+  hipStream_t st = (hipStream_t)stream;
+  Launch l;
+  l.layout = layout; l.n = nprob * n_per; l.index_base = index_base; l.dpar = params;
+  l.nprob = nprob; l.prob_n = n_per;
+  l.in = input; l.cost4 = cost4; l.theta = theta; l.thetadot = thetadot;
+  l.key = reinterpret_cast<unsigned long long*>(best_keys); l.status = status;
   l.reset_key = (flags & MPCR_F_RESET_BEST) != 0;
   int rc = launch_rollout(e, l, st);
   if (rc) return rc;
@@ -1650,11 +1677,31 @@ extern "C" int mpcr_topk(mpcr_engine* e, const float* cost, int stride, int n, i
   return MPCR_OK;
 }
 
+extern "C" int mpcr_topk_multi(mpcr_engine* e, const float* cost, int stride, int nprob, int n_per, int k,
+                               int* idx_out, int flags, void* stream) {
+  if (!e || !cost || !idx_out || stride <= 0) return fail(MPCR_EINVAL, "bad topk arguments");
+  if (!(flags & MPCR_F_DEVICE_PTRS)) return fail(MPCR_EINVAL, "mpcr_topk_multi takes device pointers");
+  if (nprob < 1 || n_per < 1) return fail(MPCR_EINVAL, "nprob=%d, n_per=%d: both must be >= 1", nprob, n_per);
+  if ((long long)nprob * n_per > e->max_n)
+    return fail(MPCR_EINVAL, "nprob=%d x n_per=%d exceeds max_n=%d", nprob, n_per, e->max_n);
+  if (k < 0 || k > n_per || k > TOPK_MAX)
+    return fail(MPCR_EINVAL, "k=%d outside [0, min(n_per=%d, %d)]", k, n_per, TOPK_MAX);
+  if (k == 0) return MPCR_OK;
+  HIPCHK(hipSetDevice(e->device));
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(topk_kernel, dim3(nprob), dim3(1024), 0, st, cost, stride, n_per, k, idx_out);
+  HIPCHK(hipGetLastError());
+  if (flags & MPCR_F_SYNC) HIPCHK(hipStreamSynchronize(st));
+  return MPCR_OK;
+}
+
 // ---------------------------------------------------------------------------
 // CEM context (cem.hip kernels)
 
 struct mpcr_cem {
   int device = 0, nd = 0, H = 0, max_n = 0;
+  int nprob = 1;      // Cholesky factors d_LT holds (mpcr_cem_set_problems)
+  int factored_n = 0; // problems the last factor call covered
   float* d_X = nullptr;    // 3 x H x 12: Pdot, Pddot, P
   float* d_QT = nullptr;   // LD x LD
   float* d_QbT = nullptr;  // 5nd x LD
@@ -1797,9 +1844,55 @@ extern "C" int mpcr_cem_factor(mpcr_cem* c, const float* cov, float reg, int fla
   hipLaunchKernelGGL(cholesky_kernel, dim3(1), dim3(256), 0, st, cov, c->nd, reg, c->d_LT);
   HIPCHK(hipGetLastError());
   c->factored = true;
+  c->factored_n = 1;
   if (flags & MPCR_F_SYNC) HIPCHK(hipStreamSynchronize(st));
   return MPCR_OK;
 }
+
+// Room for nprob Cholesky factors (the multi-problem entry points).  An
+// explicit call, never lazy: a tick's launches stay graph-capturable.
+extern "C" int mpcr_cem_set_problems(mpcr_cem* c, int nprob) {
+  if (!c) return fail(MPCR_EINVAL, "null argument");
+  if (nprob < 1 || nprob > c->max_n) return fail(MPCR_EINVAL, "nprob=%d outside [1, max_n=%d]", nprob, c->max_n);
+  if (nprob == c->nprob) return MPCR_OK;
+  HIPCHK(hipSetDevice(c->device));
+  const size_t LD = (size_t)c->nd * PJ_BLK, bytes = sizeof(float) * LD * LD * nprob;
+  float* lt = nullptr;
+  HIPCHK(hipDeviceSynchronize());  // launches that still read the old factors
+  if (hipMalloc(&lt, bytes) != hipSuccess) return fail(MPCR_ENOMEM, "device allocation failed");
+  if (hipMemset(lt, 0, bytes) != hipSuccess) {
+    (void)hipFree(lt);
+    return fail(MPCR_EHIP, "factor storage initialisation failed");
+  }
+  (void)hipFree(c->d_LT);
+  c->d_LT = lt;
+  c->nprob = nprob;
+  c->factored = false;
+  c->factored_n = 0;
+  return MPCR_OK;
+}
+
+extern "C" int mpcr_cem_factor_multi(mpcr_cem* c, const float* cov, int nprob, float reg, int flags, void* stream) {
+  if (!c || !cov) return fail(MPCR_EINVAL, "null argument");
+  if (!(flags & MPCR_F_DEVICE_PTRS)) return fail(MPCR_EINVAL, "mpcr_cem_factor_multi takes device pointers");
+  if (nprob < 1 || nprob > c->nprob)
+    return fail(MPCR_EINVAL, "nprob=%d outside [1, %d] (mpcr_cem_set_problems)", nprob, c->nprob);
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(cholesky_kernel, dim3(nprob), dim3(256), 0, st, cov, c->nd, reg, c->d_LT);
+  HIPCHK(hipGetLastError());
+  c->factored = true;
+  c->factored_n = nprob;
+  if (flags & MPCR_F_SYNC) HIPCHK(hipStreamSynchronize(st));
+  return MPCR_OK;
+}
+
+// mpcr_cem_sample_project (nprob = 1, n candidates) and _multi (nprob
+// problems of n candidates each): one launch, the problem on the grid's y
+static int sample_project_launch(mpcr_cem* c, int nprob, int n, const float* mean, uint64_t seed, uint64_t seed_step,
+                                 uint64_t counter, int index_base, const float* xi_in, float* xi_samples,
+                                 const float* b_eq, int beq_stride, int beq_pstride, int maxiter, const float* bounds,
+                                 float rho, float* xi_out, int flags, hipStream_t st);
 
 extern "C" int mpcr_cem_sample_project(mpcr_cem* c, int n, const float* mean, uint64_t seed, uint64_t counter,
                                        int index_base, const float* xi_in, float* xi_samples, const float* b_eq, int beq_stride,
@@ -1814,7 +1907,35 @@ extern "C" int mpcr_cem_sample_project(mpcr_cem* c, int n, const float* mean, ui
     return fail(MPCR_EINVAL, "projection needs b_eq, bounds and maxiter >= 0");
   if (n == 0) return MPCR_OK;
   HIPCHK(hipSetDevice(c->device));
-  hipStream_t st = (hipStream_t)stream;
+  return sample_project_launch(c, 1, n, mean, seed, 0, counter, index_base, xi_in, xi_samples, b_eq, beq_stride, 0,
+                               maxiter, bounds, rho, xi_out, flags, (hipStream_t)stream);
+}
+
+extern "C" int mpcr_cem_sample_project_multi(mpcr_cem* c, int nprob, int n_per, const float* mean, uint64_t seed,
+                                             uint64_t seed_step, uint64_t counter, int index_base, const float* xi_in,
+                                             float* xi_samples, const float* b_eq, int maxiter, const float* bounds,
+                                             float rho, float* xi_out, int flags, void* stream) {
+  if (!c || !xi_out) return fail(MPCR_EINVAL, "null argument");
+  if (!(flags & MPCR_F_DEVICE_PTRS)) return fail(MPCR_EINVAL, "mpcr_cem_sample_project_multi takes device pointers");
+  if (nprob < 1 || n_per < 1) return fail(MPCR_EINVAL, "nprob=%d, n_per=%d: both must be >= 1", nprob, n_per);
+  if ((long long)nprob * n_per > c->max_n)
+    return fail(MPCR_EINVAL, "nprob=%d x n_per=%d exceeds max_n=%d", nprob, n_per, c->max_n);
+  if (nprob > 65535) return fail(MPCR_EINVAL, "nprob=%d exceeds the grid's 65535", nprob);
+  if (!mean && !xi_in) return fail(MPCR_EINVAL, "need mean (sampling) or xi_in");
+  if (mean && c->factored_n < nprob)
+    return fail(MPCR_EINVAL, "sampling %d problems after a factor call that covered %d (mpcr_cem_factor_multi)", nprob,
+                c->factored_n);
+  if (maxiter < 0 || (maxiter > 0 && (!b_eq || !bounds)))
+    return fail(MPCR_EINVAL, "projection needs b_eq, bounds and maxiter >= 0");
+  HIPCHK(hipSetDevice(c->device));
+  return sample_project_launch(c, nprob, n_per, mean, seed, seed_step, counter, index_base, xi_in, xi_samples, b_eq, 0,
+                               5 * c->nd, maxiter, bounds, rho, xi_out, flags, (hipStream_t)stream);
+}
+
+static int sample_project_launch(mpcr_cem* c, int nprob, int n, const float* mean, uint64_t seed, uint64_t seed_step,
+                                 uint64_t counter, int index_base, const float* xi_in, float* xi_samples,
+                                 const float* b_eq, int beq_stride, int beq_pstride, int maxiter, const float* bounds,
+                                 float rho, float* xi_out, int flags, hipStream_t st) {
   ProjArgs a;
   std::memset(&a, 0, sizeof(a));
   a.xi_in = xi_in;
@@ -1834,15 +1955,19 @@ extern "C" int mpcr_cem_sample_project(mpcr_cem* c, int n, const float* mean, ui
   a.H = c->H;
   a.maxiter = maxiter;
   a.beq_stride = beq_stride;
+  a.seed_step = seed_step;
+  a.beq_pstride = beq_pstride;
   for (int k = 0; k < 3; k++) a.bound[k] = bounds ? bounds[k] : 0.f;
   a.rho = rho;
-  // the candidates' padded rows and the constraint rows X (3 x H x 12) in LDS
-  const int cpw = n >= PJ_CPW_SWITCH ? PJ_CPW_LARGE : PJ_CPW_SMALL;
+  // the candidates' padded rows and the constraint rows X (3 x H x 12) in LDS;
+  // a workgroup never straddles two problems (each has its own ragged tail)
+  const int cpw = (long long)nprob * n >= PJ_CPW_SWITCH ? PJ_CPW_LARGE : PJ_CPW_SMALL;
   const size_t lds = sizeof(float) * (cpw * (c->nd * PJ_BLK + 4) + 3 * (size_t)c->H * PJ_BLK);
+  const dim3 grid((n + cpw - 1) / cpw, nprob);
   if (cpw == PJ_CPW_LARGE)
-    hipLaunchKernelGGL(sample_project_kernel<PJ_CPW_LARGE>, dim3((n + cpw - 1) / cpw), dim3(64 * c->nd), lds, st, a);
+    hipLaunchKernelGGL(sample_project_kernel<PJ_CPW_LARGE>, grid, dim3(64 * c->nd), lds, st, a);
   else
-    hipLaunchKernelGGL(sample_project_kernel<PJ_CPW_SMALL>, dim3((n + cpw - 1) / cpw), dim3(64 * c->nd), lds, st, a);
+    hipLaunchKernelGGL(sample_project_kernel<PJ_CPW_SMALL>, grid, dim3(64 * c->nd), lds, st, a);
   HIPCHK(hipGetLastError());
   if (flags & MPCR_F_SYNC) HIPCHK(hipStreamSynchronize(st));
   return MPCR_OK;
@@ -1863,8 +1988,27 @@ extern "C" int mpcr_cem_update(mpcr_cem* c, const float* xi, int n, const float*
   if (k <= 0 || k > n || k > TOPK_MAX) return fail(MPCR_EINVAL, "k=%d outside [1, min(n=%d, %d)]", k, n, TOPK_MAX);
   HIPCHK(hipSetDevice(c->device));
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(cem_update_kernel, dim3(1), dim3(1024), 0, st, xi, c->nd * PJ_NB, cost, stride, elite_idx, k,
+  hipLaunchKernelGGL(cem_update_kernel, dim3(1), dim3(1024), 0, st, xi, n, c->nd * PJ_NB, cost, stride, elite_idx, k,
                      lamda, alpha_mean, alpha_cov, reg, mean, cov);
+  HIPCHK(hipGetLastError());
+  if (flags & MPCR_F_SYNC) HIPCHK(hipStreamSynchronize(st));
+  return MPCR_OK;
+}
+
+extern "C" int mpcr_cem_update_multi(mpcr_cem* c, const float* xi, int nprob, int n_per, const float* cost, int stride,
+                                     const int* elite_idx, int k, float lamda, float alpha_mean, float alpha_cov,
+                                     float reg, float* mean, float* cov, int flags, void* stream) {
+  if (!c || !xi || !cost || !elite_idx || !mean || !cov || stride <= 0) return fail(MPCR_EINVAL, "null argument");
+  if (!(flags & MPCR_F_DEVICE_PTRS)) return fail(MPCR_EINVAL, "mpcr_cem_update_multi takes device pointers");
+  if (nprob < 1 || n_per < 1) return fail(MPCR_EINVAL, "nprob=%d, n_per=%d: both must be >= 1", nprob, n_per);
+  if ((long long)nprob * n_per > c->max_n)
+    return fail(MPCR_EINVAL, "nprob=%d x n_per=%d exceeds max_n=%d", nprob, n_per, c->max_n);
+  if (k <= 0 || k > n_per || k > TOPK_MAX)
+    return fail(MPCR_EINVAL, "k=%d outside [1, min(n_per=%d, %d)]", k, n_per, TOPK_MAX);
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(cem_update_kernel, dim3(nprob), dim3(1024), 0, st, xi, n_per, c->nd * PJ_NB, cost, stride,
+                     elite_idx, k, lamda, alpha_mean, alpha_cov, reg, mean, cov);
   HIPCHK(hipGetLastError());
   if (flags & MPCR_F_SYNC) HIPCHK(hipStreamSynchronize(st));
   return MPCR_OK;

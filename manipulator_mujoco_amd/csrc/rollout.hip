@@ -2668,7 +2668,12 @@ __device__ __forceinline__ mfx16 mfma_rows32(const S& s, const float* gx, int ne
 // are independent given the step's kinematics -- and meets wave 0 at two
 // workgroup barriers per step (geom poses ready; contacts ready).  Same
 // instructions on the same data as WPC = 1, so the results are bitwise equal.
-template <int NVW, int NBW, int NGW, bool WIDE, int WPC = 1>
+// MULTI: several problems in one call (RolloutArgs::prob_n > 0) -- the
+// parameter block and the best key of the candidate's problem.  Its own
+// instantiation, so the one-problem kernels compile from the source they had
+// (the extra scalar values moved the register allocation of the whole
+// kernel: C3 +0.5 % when the one kernel served both).
+template <int NVW, int NBW, int NGW, bool WIDE, int WPC = 1, bool MULTI = false>
 __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrowWavesPerSimd)
     rollout_kernel(RolloutArgs args, const DevModel* __restrict__ mptr) {
   static_assert(WPC == 1 || WPC == 2, "waves per candidate");
@@ -2818,7 +2823,14 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
   //      (plant mode: the caller's state, no init_pos override)
   const bool from_state = (args.plant & 1) != 0;
   if (run_main) {  // (WPC = 2: wave 0 sets the image up, wave 1 waits at the barrier below)
-  if (lane < PAR_N) s.par[lane] = args.dpar ? args.dpar[lane] : args.par[lane];
+  if constexpr (MULTI) {
+    // the candidate's problem (mpcr_rollout_cost_multi): wave-uniform, scalar
+    const int pr = args.prob_n ? (args.prob_off + b) / args.prob_n : 0;
+    const float* dp = args.dpar + (size_t)pr * PAR_N;
+    if (lane < PAR_N) s.par[lane] = dp[lane];
+  } else {
+    if (lane < PAR_N) s.par[lane] = args.dpar ? args.dpar[lane] : args.par[lane];
+  }
   if constexpr (S::SPLIT)
     if (lane == 0) s.ctok_[0] = 0;  // no step's pair cull posted yet
   if constexpr (S::WIDE) {
@@ -4570,8 +4582,15 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
     if (args.best_key) {
       const uint32_t u = __float_as_uint(cost);
       uint32_t key = isnan(cost) ? 0u : ((u & 0x80000000u) ? ~u : (u | 0x80000000u));
-      const unsigned long long k64 = ((unsigned long long)key << 32) | (uint32_t)(args.index_base + b);
-      atomicMin(args.best_key, k64);
+      if constexpr (MULTI) {  // problem pr's key, the index within the problem
+        const int gi = args.prob_off + b, pr = args.prob_n ? gi / args.prob_n : 0;
+        const int li = args.prob_n ? gi - pr * args.prob_n : gi;
+        const unsigned long long k64 = ((unsigned long long)key << 32) | (uint32_t)(args.index_base + li);
+        atomicMin(args.best_key + pr, k64);
+      } else {
+        const unsigned long long k64 = ((unsigned long long)key << 32) | (uint32_t)(args.index_base + b);
+        atomicMin(args.best_key, k64);
+      }
     }
   }
   if (pace && lane == pace_own) __hip_atomic_store(pace + lane, ~0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);

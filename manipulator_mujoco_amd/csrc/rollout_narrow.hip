@@ -50,7 +50,13 @@ static RolloutArgs group_args(const RolloutArgs& a, int off, int n) {
   RolloutArgs g = a;
   const size_t o = (size_t)off;
   g.n = n;
-  g.index_base = a.index_base + off;
+  if (a.prob_n) {
+    // several problems: the kernel derives problem and local index from the
+    // candidate's place in the call (a group need not start at a problem)
+    g.prob_off = a.prob_off + off;
+  } else {
+    g.index_base = a.index_base + off;
+  }
   const size_t in_row = a.layout == 0 ? (size_t)a.nctrl * a.nbasis : (size_t)a.nctrl * a.H;
   g.input = a.input + o * in_row;
   g.cost4 = a.cost4 + 4 * o;
@@ -123,8 +129,13 @@ void rollout_launch(bool wide, const RolloutArgs& a0, const DevModel* dm, unsign
       rollout_wide_launch(1, grid, st, a, dm);
     }
   } else {
-    if ((int)grid <= wpc2_max_n())
+    const bool multi = a.prob_n > 0;  // several problems: the MULTI instantiations
+    if ((int)grid <= wpc2_max_n() && multi)
+      hipLaunchKernelGGL((rollout_kernel<16, 16, 24, false, 2, true>), dim3(grid), dim3(2 * WAVE), 0, st, a, dm);
+    else if ((int)grid <= wpc2_max_n())
       hipLaunchKernelGGL((rollout_kernel<16, 16, 24, false, 2>), dim3(grid), dim3(2 * WAVE), 0, st, a, dm);
+    else if (multi)
+      hipLaunchKernelGGL((rollout_kernel<16, 16, 24, false, 1, true>), dim3(grid), dim3(WAVE), 0, st, a, dm);
     else
       hipLaunchKernelGGL((rollout_kernel<16, 16, 24, false>), dim3(grid), dim3(WAVE), 0, st, a, dm);
   }

@@ -175,6 +175,33 @@ class Engine:
                                                int(index_base), ptr(status), flags, ctypes.c_void_p(st)))
         return cost4
 
+    def rollout_cost_multi(self, inp, layout: int, params, nprob: int, cost4, theta=None, thetadot=None,
+                           best_keys=None, index_base: int = 0, status=None, reset_best: bool = True, stream=None):
+        """``nprob`` independent problems in one launch (``mpcr_rollout_cost_multi``):
+        ``inp`` holds nprob * n_per rows, problem p owning rows [p n_per,
+        (p + 1) n_per); ``params`` is (nprob, 20), one ``Engine.params`` block
+        per problem; ``best_keys`` an int64 tensor of nprob elements whose key
+        p carries ``index_base`` + the index within problem p.  Bitwise the
+        ``rollout_cost_dp`` calls on the slices.  Graph-capturable."""
+        import torch
+        for name, t in (("input", inp), ("params", params), ("cost4", cost4)):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous float32 CUDA tensor")
+        nprob = int(nprob)
+        if nprob < 1 or inp.shape[0] % nprob:
+            raise ValueError(f"input rows ({inp.shape[0]}) must split evenly over nprob={nprob} problems")
+        if params.numel() < 20 * nprob:
+            raise ValueError("params needs nprob x 20 floats")
+        if best_keys is not None and best_keys.numel() < nprob:
+            raise ValueError("best_keys needs nprob elements")
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        st = stream if stream is not None else torch.cuda.current_stream(inp.device).cuda_stream
+        flags = MPCR_F_DEVICE_PTRS | (MPCR_F_RESET_BEST if reset_best else 0)
+        check(_lib.load().mpcr_rollout_cost_multi(self.handle, ptr(inp), layout, nprob, int(inp.shape[0]) // nprob,
+                                                  ptr(params), ptr(cost4), ptr(theta), ptr(thetadot), ptr(best_keys),
+                                                  int(index_base), ptr(status), flags, ctypes.c_void_p(st)))
+        return cost4
+
     def trace(self, inp, layout: int, q0, w, ptgt, qtgt):
         """Debug/parity run (host arrays): cost4, theta, per-step eef pose, masked slot distances."""
         lib = _lib.load()

@@ -22,6 +22,11 @@ the best candidate is one 8-byte MIN all-reduce.  With
 ``graph=True`` the per-iteration kernel sequences are captured in HIP graphs
 on the first call (per-tick inputs live in static device buffers).
 
+With ``num_problems=B``, ``compute_cem_batch`` plans B independent problems
+(own start state, target, weights, distribution and best key) in one tick:
+the same five kernels per iteration, each launched once over all problems
+(the ``*_multi`` entry points), bitwise what B one-problem planners compute.
+
 Reference behaviours kept on purpose, each behind a flag:
   * elites are gathered from the *unprojected* samples (``elite_from_filtered=False``)
   * the sampling key is not advanced across calls (fixed ``seed`` per call)
@@ -40,7 +45,7 @@ import time
 import numpy as np
 
 from . import _lib, basis, models
-from .cem import CemContext, topk
+from .cem import CemContext, topk, topk_multi
 from .engine import MPCR_LAYOUT_XI, Engine
 from .mjcf import load_model
 
@@ -78,12 +83,20 @@ class cem_planner:  # noqa: N801 (reference name)
                         all-gathers in the tick's graph (default); False
                         captures each iteration's device segment and runs the
                         exchange eagerly between the replays (as with gloo)
+    num_problems        independent problems planned per ``compute_cem_batch``
+                        tick (own start state, target, weights, distribution
+                        and best key each); ``num_batch`` stays the candidates
+                        per problem.  One rank only
+    seed_step           problem p draws with the Philox key seed + p seed_step
+                        (0: every problem the same draws), i.e. what a
+                        planner built with that seed draws
     """
 
     def __init__(self, num_dof=None, num_batch=None, num_steps=None, timestep=None, maxiter_cem=None,
                  num_elite=None, w_pos=None, w_rot=None, w_col=None, maxiter_projection=None, *,
                  model_path=None, device=None, seed=0, elite_from_filtered=False, graph=False, group=None,
-                 gather_rollouts=False, return_rollouts=True, capture_exchange=True, verbose=True):
+                 gather_rollouts=False, return_rollouts=True, capture_exchange=True, verbose=True,
+                 num_problems=1, seed_step=0):
         import torch
         import torch.distributed as tdist
 
@@ -117,6 +130,13 @@ class cem_planner:  # noqa: N801 (reference name)
         if self.num_batch % self.world:
             raise ValueError(f"num_batch={self.num_batch} must split evenly over {self.world} ranks")
         self.n_local = self.num_batch // self.world
+        self.num_problems = int(num_problems)
+        self.seed_step = int(seed_step)
+        if self.num_problems < 1:
+            raise ValueError(f"num_problems={self.num_problems} must be at least 1")
+        if self.num_problems > 1 and self.world > 1:
+            raise ValueError(f"num_problems={self.num_problems} with {self.world} ranks: sharded multi-problem "
+                             "planning is not supported")
         self.exchange = self.world > 1  # elites through gather_elites (forced on one rank in tests)
         self.index_base = self.rank * self.n_local
 
@@ -135,24 +155,28 @@ class cem_planner:  # noqa: N801 (reference name)
         self.hande_id = self.model.hande_body
         self.tcp_id = self.model.tcp_site
         n = self.n_local
-        self.engine = Engine(self.model, self.num, n, self.Pdot, device=dev)
-        self.cem = CemContext(self.P, self.Pdot, self.Pddot, self.num_dof, n, device=dev)
+        B = self.num_problems
+        self.engine = Engine(self.model, self.num, B * n, self.Pdot, device=dev)
+        self.cem = CemContext(self.P, self.Pdot, self.Pddot, self.num_dof, B * n, device=dev, num_problems=B)
         f32 = dict(dtype=torch.float32, device=self.device)
         H, it_n = self.num, self.maxiter_cem
-        self._key = torch.empty(1, dtype=torch.int64, device=self.device)
+        pb = (B,) if B > 1 else ()  # the leading problem axis of every device buffer (none for one problem)
+        self._key = torch.empty(B, dtype=torch.int64, device=self.device)
         self._eye10 = 10.0 * torch.eye(self.nvar, **f32)  # xi_cov (:386)
-        self._mean = torch.empty(self.nvar, **f32)
-        self._cov = torch.empty((self.nvar, self.nvar), **f32)
-        self._xs = torch.empty((n, self.nvar), **f32)  # xi_samples
-        self._xf = torch.empty((n, self.nvar), **f32)  # xi_filtered
-        self._idx = torch.empty(max(self.ellite_num, 1), dtype=torch.int32, device=self.device)
-        self._beq = torch.empty(5 * self.num_dof, **f32)
-        self._par = torch.zeros(20, **f32)  # init_pos | weights | target (Engine.params)
-        self._thetadot = torch.empty((it_n, n, self.num_dof * H), **f32)
-        self._theta = torch.empty((it_n, n, self.num_dof * H), **f32)
-        self._costs = torch.empty((it_n, n, 4), **f32)
-        self._mean_in = torch.empty(self.nvar, **f32)
+        self._mean = torch.empty(pb + (self.nvar,), **f32)
+        self._cov = torch.empty(pb + (self.nvar, self.nvar), **f32)
+        self._xs = torch.empty(pb + (n, self.nvar), **f32)  # xi_samples
+        self._xf = torch.empty(pb + (n, self.nvar), **f32)  # xi_filtered
+        self._idx = torch.empty(pb + (max(self.ellite_num, 1),), dtype=torch.int32, device=self.device)
+        self._beq = torch.empty(pb + (5 * self.num_dof,), **f32)
+        self._par = torch.zeros(pb + (20,), **f32)  # init_pos | weights | target (Engine.params)
+        self._thetadot = torch.empty((it_n,) + pb + (n, self.num_dof * H), **f32)
+        self._theta = torch.empty((it_n,) + pb + (n, self.num_dof * H), **f32)
+        self._costs = torch.empty((it_n,) + pb + (n, 4), **f32)
+        self._mean_in = torch.empty(pb + (self.nvar,), **f32)
         self._graphs = None
+        self._multi = False         # compute_cem_batch: the segments below run the multi-problem kernels
+        self._graphs_multi = None   # ... and replay their own captured tick
         if verbose and self.rank == 0:
             self.print_info()
 
@@ -172,11 +196,21 @@ class cem_planner:  # noqa: N801 (reference name)
         bounds = (self.v_max, self.a_max, self.p_max)
         if it == 0:
             self._mean.copy_(self._mean_in)
-            self._cov.copy_(self._eye10)
+            self._cov.copy_(self._eye10)  # (broadcast over the problems)
+        last = it == self.maxiter_cem - 1
+        if self._multi:
+            # the same kernels, one workgroup / grid row per problem
+            B, n = self.num_problems, self.n_local
+            self.cem.factor_multi(self._cov.view(B, self.nvar, self.nvar), 0.003)
+            self.cem.sample_project_multi(B, n, self._mean, self.seed, it, self._beq, self.maxiter_projection, bounds,
+                                          rho=1.0, seed_step=self.seed_step, xi_samples=self._xs, out=self._xf)
+            self.engine.rollout_cost_multi(self._xf.view(B * n, self.nvar), MPCR_LAYOUT_XI, self._par, B,
+                                           self._costs[it], theta=self._theta[it], thetadot=self._thetadot[it],
+                                           best_keys=self._key if last else None)
+            return
         self.cem.factor(self._cov, 0.003)
         self.cem.sample_project(self.n_local, self._mean, self.seed, it, self._beq, self.maxiter_projection, bounds,
                                 rho=1.0, xi_samples=self._xs, out=self._xf, index_base=self.index_base)
-        last = it == self.maxiter_cem - 1
         self.engine.rollout_cost_dp(self._xf, MPCR_LAYOUT_XI, self._par, self._costs[it], theta=self._theta[it],
                                     thetadot=self._thetadot[it], best_key=self._key if last else None,
                                     index_base=self.index_base)
@@ -184,6 +218,13 @@ class cem_planner:  # noqa: N801 (reference name)
     def _seg_local_update(self, it):
         """compute_ellite_samples + compute_mean_cov on one rank (:355-360)."""
         src = self._xf if self.elite_from_filtered else self._xs
+        if self._multi:
+            B, n = self.num_problems, self.n_local
+            idx = self._idx.view(B, self.ellite_num)
+            topk_multi(self.engine, self._costs[it], B, self.ellite_num, stride=4, out=idx)
+            self.cem.update_multi(src.view(B, n, self.nvar), self._costs[it], 4, idx, self.lamda, self.alpha_mean,
+                                  self.alpha_cov, self._mean, self._cov, reg=1e-4)
+            return
         topk(self.engine, self._costs[it], self.ellite_num, stride=4, out=self._idx)
         self.cem.update(src, self._costs[it], 4, self._idx, self.lamda, self.alpha_mean, self.alpha_cov,
                         self._mean, self._cov, reg=1e-4)
@@ -266,6 +307,9 @@ class cem_planner:  # noqa: N801 (reference name)
 
         from . import dist as mdist
 
+        if self.num_problems > 1:
+            raise ValueError(f"this planner was built with num_problems={self.num_problems}: "
+                             "use compute_cem_batch (compute_cem plans one problem)")
         d = self.num_dof
         H = self.num
         init_pos = np.asarray(init_pos, np.float64)[:d]
@@ -306,6 +350,74 @@ class cem_planner:  # noqa: N801 (reference name)
         best_traj = best[4 + d * H:].reshape(d, H).T
         out = (cost_min, best[1], best[2], best[3], best_vels, best_traj, self._mean, thetadot, theta)
         return tuple(o.cpu().numpy() if isinstance(o, torch.Tensor) else o for o in out)
+
+    def compute_cem_batch(self, xi_mean, init_pos, init_vel=None, init_acc=None, target_pos=None, target_rot=None,
+                          weights=None):
+        """One MPC tick of ``num_problems`` independent CEM problems in one
+        batched sequence of launches (each kernel of ``compute_cem`` once,
+        over every problem): xi_mean (B, nvar), init_pos / init_vel /
+        init_acc (B, num_dof), target_pos (B, 3), target_rot (B, 4), weights
+        (B, 3) (w_pos, w_rot, w_col; default the constructor's for every
+        problem).  Returns the 9 entries of ``compute_cem``, each stacked
+        over the problems on a new leading axis: ``out[j][p]`` is bitwise
+        entry j of ``compute_cem`` on a planner with seed ``seed + p
+        seed_step`` given problem p's arguments."""
+        import torch
+
+        B, d, H, n, it_n = self.num_problems, self.num_dof, self.num, self.n_local, self.maxiter_cem
+        if self.world > 1:
+            raise ValueError("compute_cem_batch runs on one rank")
+        if self.ellite_num < 1:
+            raise ValueError("num_elite * num_batch must select at least one elite")
+
+        def rows(x, cols, name, dtype=np.float64):
+            a = np.zeros((B, cols), dtype) if x is None else np.asarray(x, dtype)
+            if a.ndim != 2 or a.shape[0] != B or a.shape[1] < cols:
+                raise ValueError(f"{name} must be ({B}, {cols}), got {a.shape}")
+            return a[:, :cols]
+
+        xi_mean = rows(xi_mean, self.nvar, "xi_mean", np.float32)
+        init_pos = rows(init_pos, d, "init_pos")
+        init_vel, init_acc = rows(init_vel, d, "init_vel"), rows(init_acc, d, "init_acc")
+        target_pos, target_rot = rows(target_pos, 3, "target_pos"), rows(target_rot, 4, "target_rot")
+        if weights is None:
+            weights = [[self.cost_weights["w_pos"], self.cost_weights["w_rot"], self.cost_weights["w_col"]]] * B
+        weights = rows(weights, 3, "weights", np.float32)
+
+        # per-tick inputs into the static device buffers the (captured) kernels read
+        self._mean_in.copy_(torch.as_tensor(np.ascontiguousarray(xi_mean)).view(self._mean_in.shape))
+        z = np.zeros((B, d))
+        st = np.stack([init_pos, init_vel, init_acc, z, z], axis=2)  # state_term per problem (:374-384)
+        self._beq.copy_(torch.as_tensor(st.reshape(B, 5 * d).astype(np.float32)).view(self._beq.shape))
+        par = np.stack([Engine.params(init_pos[p], weights[p], target_pos[p], target_rot[p]) for p in range(B)])
+        self._par.copy_(torch.as_tensor(par).view(self._par.shape))
+        self._multi, single = True, self._graphs
+        self._graphs = self._graphs_multi
+        try:
+            self._run_iterations()
+        finally:
+            self._graphs_multi, self._graphs, self._multi = self._graphs, single, False
+
+        # each problem's best candidate of the last iteration: the low word of
+        # its key is the index within the problem; one gather, one transfer
+        costs = self._costs.view(it_n, B, n, 4)
+        theta, thetadot = self._theta.view(it_n, B, n, d * H), self._thetadot.view(it_n, B, n, d * H)
+        li = self._key & 0xFFFFFFFF
+        flat = li + n * torch.arange(B, dtype=torch.int64, device=self.device)
+        packed = torch.cat([torch.amin(costs[..., 0], dim=2).T,
+                            costs[-1].reshape(B * n, 4).index_select(0, flat),
+                            thetadot[-1].reshape(B * n, d * H).index_select(0, flat),
+                            theta[-1].reshape(B * n, d * H).index_select(0, flat),
+                            self._mean.view(B, self.nvar)], dim=1).cpu().numpy()
+        o = it_n
+        cost_min, best = packed[:, :o], packed[:, o:o + 4]
+        best_vels = packed[:, o + 4:o + 4 + d * H].reshape(B, d, H).transpose(0, 2, 1)
+        best_traj = packed[:, o + 4 + d * H:o + 4 + 2 * d * H].reshape(B, d, H).transpose(0, 2, 1)
+        mean = packed[:, o + 4 + 2 * d * H:]
+        td = th = None
+        if self.return_rollouts:
+            td, th = (x.permute(1, 0, 2, 3).cpu().numpy() for x in (thetadot, theta))
+        return (cost_min, best[:, 1], best[:, 2], best[:, 3], best_vels, best_traj, mean, td, th)
 
     def _gather_all(self, x):
         from .dist import all_gather
