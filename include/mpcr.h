@@ -198,7 +198,12 @@ int mpcr_rollout_cost_dp(mpcr_engine* e, const float* input, int layout, int n, 
    compute_cem's rollout (mjx_planner.py:348-354, 395) for nprob start states
    / targets / weight triples at once.  Device pointers only
    (MPCR_F_DEVICE_PTRS); nprob, n_per >= 1 and nprob n_per <= max_n;
-   MPCR_F_RESET_BEST resets all nprob keys.  Graph-capturable. */
+   MPCR_F_RESET_BEST resets all nprob keys.  Graph-capturable.
+   Here and for every *_multi call below, the one-problem call is the
+   nprob = 1 case of the same implementation (same launch, same kernel), and
+   calling the *_multi entry with nprob = 1 runs exactly what it runs.  The
+   one-problem entries alone keep their host-pointer modes, an empty batch
+   (n = 0) as a no-op and mpcr_cem_sample_project's beq_stride. */
 int mpcr_rollout_cost_multi(mpcr_engine* e, const float* input, int layout, int nprob, int n_per,
                             const float* params, float* cost4, float* theta, float* thetadot, uint64_t* best_keys,
                             int index_base, int* status, int flags, void* stream);

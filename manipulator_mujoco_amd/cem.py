@@ -80,12 +80,62 @@ class CemContext:
         import torch
         return ctypes.c_void_p(stream if stream is not None else torch.cuda.current_stream(t.device).cuda_stream)
 
-    def factor(self, cov, reg: float = 0.003, stream=None):
-        """L = chol(cov + reg I) for the next ``sample_project``."""
+    # Each stage has one body, which both of its public calls go through.  The
+    # one-problem call is the nprob = 1 case without the leading problem axis
+    # on its tensors; it keeps its own C entry for what only that entry takes
+    # (per-candidate b_eq rows, an empty batch, elites gathered from more
+    # candidates than max_n).
+
+    def _factor(self, multi, cov, reg, stream):
         import torch
         _dev(cov, torch.float32, "cov")
-        check(_lib.load().mpcr_cem_factor(self.handle, _ptr(cov), float(reg), MPCR_F_DEVICE_PTRS,
-                                          self._stream(cov, stream)))
+        if multi and cov.dim() != 3:
+            raise ValueError("cov must be (nprob, nvar, nvar)")
+        lib = _lib.load()
+        fn, nprob = (lib.mpcr_cem_factor_multi, (int(cov.shape[0]),)) if multi else (lib.mpcr_cem_factor, ())
+        check(fn(self.handle, _ptr(cov), *nprob, float(reg), MPCR_F_DEVICE_PTRS, self._stream(cov, stream)))
+
+    def factor(self, cov, reg: float = 0.003, stream=None):
+        """L = chol(cov + reg I) for the next ``sample_project``."""
+        self._factor(False, cov, reg, stream)
+
+    def factor_multi(self, cov, reg: float = 0.003, stream=None):
+        """One Cholesky factor per problem: cov is (nprob, nvar, nvar)."""
+        self._factor(True, cov, reg, stream)
+
+    def _sample_project(self, nprob, n, mean, seed, counter, b_eq, maxiter, bounds, rho, xi_samples, out, xi_in,
+                        index_base, stream, beq_shared=True, seed_step=0):
+        """nprob None: ``sample_project``; else ``sample_project_multi``."""
+        import torch
+        ref = mean if mean is not None else xi_in
+        if ref is None:
+            raise ValueError("need mean or xi_in")
+        if out is None:
+            shape = (n, self.nvar) if nprob is None else (nprob, n, self.nvar)
+            out = torch.empty(shape, dtype=torch.float32, device=ref.device)
+        for name, t in (("mean", mean), ("xi_in", xi_in), ("xi_samples", xi_samples), ("out", out),
+                        ("b_eq", b_eq)):
+            if t is not None:
+                _dev(t, torch.float32, name)
+        bnd = (ctypes.c_float * 3)(*[float(b) for b in bounds])
+        u64 = lambda v: ctypes.c_uint64(int(v) & (2**64 - 1))  # noqa: E731
+        lib, st = _lib.load(), self._stream(ref, stream)
+        if nprob is None:
+            check(lib.mpcr_cem_sample_project(
+                self.handle, int(n), _ptr(mean), u64(seed), u64(counter), int(index_base), _ptr(xi_in),
+                _ptr(xi_samples), _ptr(b_eq), 0 if beq_shared else 5 * self.num_dof, int(maxiter), bnd, float(rho),
+                _ptr(out), MPCR_F_DEVICE_PTRS, st))
+            return out
+        for name, t, numel in (("mean", mean, nprob * self.nvar), ("b_eq", b_eq, nprob * 5 * self.num_dof),
+                               ("xi_in", xi_in, nprob * n * self.nvar), ("out", out, nprob * n * self.nvar),
+                               ("xi_samples", xi_samples, nprob * n * self.nvar)):
+            if t is not None and t.numel() != numel:
+                raise ValueError(f"{name} has {t.numel()} elements, expected {numel}")
+        check(lib.mpcr_cem_sample_project_multi(
+            self.handle, int(nprob), int(n), _ptr(mean), u64(seed), u64(seed_step), u64(counter), int(index_base),
+            _ptr(xi_in), _ptr(xi_samples), _ptr(b_eq), int(maxiter), bnd, float(rho), _ptr(out), MPCR_F_DEVICE_PTRS,
+            st))
+        return out
 
     def sample_project(self, n, mean, seed, counter, b_eq, maxiter, bounds, rho=1.0, xi_samples=None, out=None,
                        xi_in=None, beq_shared=True, index_base=0, stream=None):
@@ -93,49 +143,8 @@ class CemContext:
         as global candidate ``index_base + i``); or ``xi_in`` when mean is
         None; then ``maxiter`` ADMM iterations.  Returns the projected
         (n, nvar) tensor."""
-        import torch
-        ref = mean if mean is not None else xi_in
-        if ref is None:
-            raise ValueError("need mean or xi_in")
-        f32 = dict(dtype=torch.float32, device=ref.device)
-        if out is None:
-            out = torch.empty((n, self.nvar), **f32)
-        for name, t in (("mean", mean), ("xi_in", xi_in), ("xi_samples", xi_samples), ("out", out),
-                        ("b_eq", b_eq)):
-            if t is not None:
-                _dev(t, torch.float32, name)
-        bnd = (ctypes.c_float * 3)(*[float(b) for b in bounds])
-        stride = 0 if beq_shared else 5 * self.num_dof
-        check(_lib.load().mpcr_cem_sample_project(
-            self.handle, int(n), _ptr(mean), ctypes.c_uint64(int(seed) & (2**64 - 1)),
-            ctypes.c_uint64(int(counter) & (2**64 - 1)), int(index_base), _ptr(xi_in), _ptr(xi_samples), _ptr(b_eq), stride,
-            int(maxiter), bnd, float(rho), _ptr(out), MPCR_F_DEVICE_PTRS, self._stream(ref, stream)))
-        return out
-
-    def project(self, xi, b_eq, maxiter, bounds, rho=1.0, out=None, beq_shared=True, stream=None):
-        return self.sample_project(xi.shape[0], None, 0, 0, b_eq, maxiter, bounds, rho, out=out, xi_in=xi,
-                                   beq_shared=beq_shared, stream=stream)
-
-    def update(self, xi, cost, stride, elite_idx, lamda, alpha_mean, alpha_cov, mean, cov, reg=1e-4, stream=None):
-        """In-place weighted elite mean/cov update (compute_mean_cov)."""
-        import torch
-        _dev(xi, torch.float32, "xi"); _dev(cost, torch.float32, "cost")
-        _dev(elite_idx, torch.int32, "elite_idx"); _dev(mean, torch.float32, "mean"); _dev(cov, torch.float32, "cov")
-        check(_lib.load().mpcr_cem_update(self.handle, _ptr(xi), int(xi.shape[0]), _ptr(cost), int(stride),
-                                          _ptr(elite_idx), int(elite_idx.shape[0]), float(lamda), float(alpha_mean),
-                                          float(alpha_cov), float(reg), _ptr(mean), _ptr(cov), MPCR_F_DEVICE_PTRS,
-                                          self._stream(xi, stream)))
-
-
-    # ---- several problems per call: leading problem axis on every tensor ----
-    def factor_multi(self, cov, reg: float = 0.003, stream=None):
-        """One Cholesky factor per problem: cov is (nprob, nvar, nvar)."""
-        import torch
-        _dev(cov, torch.float32, "cov")
-        if cov.dim() != 3:
-            raise ValueError("cov must be (nprob, nvar, nvar)")
-        check(_lib.load().mpcr_cem_factor_multi(self.handle, _ptr(cov), int(cov.shape[0]), float(reg),
-                                                MPCR_F_DEVICE_PTRS, self._stream(cov, stream)))
+        return self._sample_project(None, n, mean, seed, counter, b_eq, maxiter, bounds, rho, xi_samples, out, xi_in,
+                                    index_base, stream, beq_shared=beq_shared)
 
     def sample_project_multi(self, nprob, n_per, mean, seed, counter, b_eq, maxiter, bounds, rho=1.0, seed_step=0,
                              xi_samples=None, out=None, xi_in=None, index_base=0, stream=None):
@@ -144,77 +153,71 @@ class CemContext:
         b_eq (nprob, 5 num_dof); problem p draws with the Philox key
         ``seed + p * seed_step``.  Returns the projected (nprob, n_per, nvar)
         tensor, bitwise the single calls on the slices."""
+        return self._sample_project(int(nprob), n_per, mean, seed, counter, b_eq, maxiter, bounds, rho, xi_samples,
+                                    out, xi_in, index_base, stream, seed_step=seed_step)
+
+    def project(self, xi, b_eq, maxiter, bounds, rho=1.0, out=None, beq_shared=True, stream=None):
+        return self.sample_project(xi.shape[0], None, 0, 0, b_eq, maxiter, bounds, rho, out=out, xi_in=xi,
+                                   beq_shared=beq_shared, stream=stream)
+
+    def _update(self, multi, xi, cost, stride, elite_idx, lamda, alpha_mean, alpha_cov, mean, cov, reg, stream):
         import torch
-        ref = mean if mean is not None else xi_in
-        if ref is None:
-            raise ValueError("need mean or xi_in")
-        if out is None:
-            out = torch.empty((nprob, n_per, self.nvar), dtype=torch.float32, device=ref.device)
-        for name, t in (("mean", mean), ("xi_in", xi_in), ("xi_samples", xi_samples), ("out", out),
-                        ("b_eq", b_eq)):
-            if t is not None:
-                _dev(t, torch.float32, name)
-        for name, t, numel in (("mean", mean, nprob * self.nvar), ("b_eq", b_eq, nprob * 5 * self.num_dof),
-                               ("xi_in", xi_in, nprob * n_per * self.nvar), ("out", out, nprob * n_per * self.nvar),
-                               ("xi_samples", xi_samples, nprob * n_per * self.nvar)):
-            if t is not None and t.numel() != numel:
-                raise ValueError(f"{name} has {t.numel()} elements, expected {numel}")
-        bnd = (ctypes.c_float * 3)(*[float(b) for b in bounds])
-        u64 = lambda v: ctypes.c_uint64(int(v) & (2**64 - 1))  # noqa: E731
-        check(_lib.load().mpcr_cem_sample_project_multi(
-            self.handle, int(nprob), int(n_per), _ptr(mean), u64(seed), u64(seed_step), u64(counter), int(index_base),
-            _ptr(xi_in), _ptr(xi_samples), _ptr(b_eq), int(maxiter), bnd, float(rho), _ptr(out), MPCR_F_DEVICE_PTRS,
-            self._stream(ref, stream)))
-        return out
+        _dev(xi, torch.float32, "xi"); _dev(cost, torch.float32, "cost")
+        _dev(elite_idx, torch.int32, "elite_idx"); _dev(mean, torch.float32, "mean"); _dev(cov, torch.float32, "cov")
+        lib = _lib.load()
+        fn = lib.mpcr_cem_update
+        if multi:
+            if xi.dim() != 3 or elite_idx.dim() != 2 or elite_idx.shape[0] != xi.shape[0]:
+                raise ValueError("xi must be (nprob, n_per, nvar) and elite_idx (nprob, k)")
+            if mean.numel() != xi.shape[0] * self.nvar or cov.numel() != xi.shape[0] * self.nvar * self.nvar:
+                raise ValueError("mean must be (nprob, nvar) and cov (nprob, nvar, nvar)")
+            fn = lib.mpcr_cem_update_multi
+        # xi's leading axes are the call's n or nprob, n_per; elite_idx's last is k
+        check(fn(self.handle, _ptr(xi), *map(int, xi.shape[:2 if multi else 1]), _ptr(cost), int(stride),
+                 _ptr(elite_idx), int(elite_idx.shape[-1]), float(lamda), float(alpha_mean), float(alpha_cov),
+                 float(reg), _ptr(mean), _ptr(cov), MPCR_F_DEVICE_PTRS, self._stream(xi, stream)))
+
+    def update(self, xi, cost, stride, elite_idx, lamda, alpha_mean, alpha_cov, mean, cov, reg=1e-4, stream=None):
+        """In-place weighted elite mean/cov update (compute_mean_cov)."""
+        self._update(False, xi, cost, stride, elite_idx, lamda, alpha_mean, alpha_cov, mean, cov, reg, stream)
 
     def update_multi(self, xi, cost, stride, elite_idx, lamda, alpha_mean, alpha_cov, mean, cov, reg=1e-4,
                      stream=None):
         """``update`` per problem, in place: xi (nprob, n_per, nvar), cost
         (nprob, n_per[, stride]), elite_idx (nprob, k) local indices
         (``topk_multi``), mean (nprob, nvar), cov (nprob, nvar, nvar)."""
-        import torch
-        _dev(xi, torch.float32, "xi"); _dev(cost, torch.float32, "cost")
-        _dev(elite_idx, torch.int32, "elite_idx"); _dev(mean, torch.float32, "mean"); _dev(cov, torch.float32, "cov")
-        if xi.dim() != 3 or elite_idx.dim() != 2 or elite_idx.shape[0] != xi.shape[0]:
-            raise ValueError("xi must be (nprob, n_per, nvar) and elite_idx (nprob, k)")
-        nprob = int(xi.shape[0])
-        if mean.numel() != nprob * self.nvar or cov.numel() != nprob * self.nvar * self.nvar:
-            raise ValueError("mean must be (nprob, nvar) and cov (nprob, nvar, nvar)")
-        check(_lib.load().mpcr_cem_update_multi(self.handle, _ptr(xi), nprob, int(xi.shape[1]), _ptr(cost),
-                                                int(stride), _ptr(elite_idx), int(elite_idx.shape[1]), float(lamda),
-                                                float(alpha_mean), float(alpha_cov), float(reg), _ptr(mean), _ptr(cov),
-                                                MPCR_F_DEVICE_PTRS, self._stream(xi, stream)))
+        self._update(True, xi, cost, stride, elite_idx, lamda, alpha_mean, alpha_cov, mean, cov, reg, stream)
+
+
+def _topk(engine, cost, nprob, k, stride, out, stream):
+    """nprob None: ``topk``; else ``topk_multi``."""
+    import torch
+    _dev(cost, torch.float32, "cost")
+    n = cost.numel() // stride
+    if nprob is not None and (nprob < 1 or n % nprob):
+        raise ValueError(f"{n} costs do not split evenly over nprob={nprob} problems")
+    if out is None:
+        out = torch.empty(k if nprob is None else (nprob, k), dtype=torch.int32, device=cost.device)
+    st = stream if stream is not None else torch.cuda.current_stream(cost.device).cuda_stream
+    lib = _lib.load()
+    fn, shape = (lib.mpcr_topk, (n,)) if nprob is None else (lib.mpcr_topk_multi, (int(nprob), n // nprob))
+    check(fn(engine.handle, _ptr(cost), int(stride), *shape, int(k), _ptr(out), MPCR_F_DEVICE_PTRS,
+             ctypes.c_void_p(st)))
+    return out
 
 
 def topk_multi(engine, cost, nprob, k, stride=1, out=None, stream=None):
     """``topk`` for nprob problems in one launch: cost holds nprob * n_per
     entries of ``stride`` floats, problem p owning entries [p n_per,
     (p + 1) n_per); returns (nprob, k) int32 indices local to each problem."""
-    import torch
-    _dev(cost, torch.float32, "cost")
-    n = cost.numel() // stride
-    if nprob < 1 or n % nprob:
-        raise ValueError(f"{n} costs do not split evenly over nprob={nprob} problems")
-    if out is None:
-        out = torch.empty((nprob, k), dtype=torch.int32, device=cost.device)
-    st = stream if stream is not None else torch.cuda.current_stream(cost.device).cuda_stream
-    check(_lib.load().mpcr_topk_multi(engine.handle, _ptr(cost), int(stride), int(nprob), n // nprob, int(k),
-                                      _ptr(out), MPCR_F_DEVICE_PTRS, ctypes.c_void_p(st)))
-    return out
+    return _topk(engine, cost, int(nprob), k, stride, out, stream)
 
 
 def topk(engine, cost, k, stride=1, out=None, stream=None):
     """Indices of the k smallest of cost[i*stride] in stable-argsort order
     (NaN last) through ``mpcr_topk`` on ``engine``'s device."""
-    import torch
-    _dev(cost, torch.float32, "cost")
-    n = cost.numel() // stride
-    if out is None:
-        out = torch.empty(k, dtype=torch.int32, device=cost.device)
-    st = stream if stream is not None else torch.cuda.current_stream(cost.device).cuda_stream
-    check(_lib.load().mpcr_topk(engine.handle, _ptr(cost), int(stride), int(n), int(k), _ptr(out),
-                                MPCR_F_DEVICE_PTRS, ctypes.c_void_p(st)))
-    return out
+    return _topk(engine, cost, None, k, stride, out, stream)
 
 
 __all__ = ["CemContext", "topk", "topk_multi", "NBASIS"]
+

@@ -1212,7 +1212,7 @@ struct Launch {
   int* status = nullptr;
   float* dbg = nullptr;
   bool reset_key = false;
-  int nprob = 1, prob_n = 0;  // mpcr_rollout_cost_multi: problems of prob_n candidates (0: one problem)
+  int nprob = 1, prob_n = 0;  // nprob > 1: problems of prob_n candidates each (0: one problem)
 };
 
 static int launch_rollout(mpcr_engine* e, const Launch& l, hipStream_t st) {
@@ -1323,42 +1323,29 @@ extern "C" int mpcr_rollout_cost(mpcr_engine* e, const float* input, int layout,
   return MPCR_OK;
 }
 
-extern "C" int mpcr_rollout_cost_dp(mpcr_engine* e, const float* input, int layout, int n, const float* params,
-                                    float* cost4, float* theta, float* thetadot, uint64_t* best_key, int index_base,
-                                    int* status, int flags, void* stream) {
-  if (!e) return fail(MPCR_EINVAL, "null argument");
-  if (n < 0 || n > e->max_n) return fail(MPCR_EINVAL, "n=%d outside [0, max_n=%d]", n, e->max_n);
-  if (layout != MPCR_LAYOUT_XI && layout != MPCR_LAYOUT_THETADOT) return fail(MPCR_EINVAL, "bad layout %d", layout);
-  if (n == 0) return MPCR_OK;  // an empty batch: the buffers may be null
-  if (!input || !params || !cost4) return fail(MPCR_EINVAL, "null argument");
-  HIPCHK(hipSetDevice(e->device));
-  hipStream_t st = (hipStream_t)stream;
-  Launch l;
-  l.layout = layout; l.n = n; l.index_base = index_base; l.dpar = params;
-  l.in = input; l.cost4 = cost4; l.theta = theta; l.thetadot = thetadot;
-  l.key = reinterpret_cast<unsigned long long*>(best_key); l.status = status;
-  l.reset_key = (flags & MPCR_F_RESET_BEST) != 0;
-  int rc = launch_rollout(e, l, st);
-  if (rc) return rc;
-  if (flags & MPCR_F_SYNC) HIPCHK(hipStreamSynchronize(st));
+// The shape a *_multi entry accepts: at least one problem of one candidate,
+// all of them within the handle's max_n.
+static int check_multi(int nprob, int n_per, int max_n) {
+  if (nprob < 1 || n_per < 1) return fail(MPCR_EINVAL, "nprob=%d, n_per=%d: both must be >= 1", nprob, n_per);
+  if ((long long)nprob * n_per > max_n)
+    return fail(MPCR_EINVAL, "nprob=%d x n_per=%d exceeds max_n=%d", nprob, n_per, max_n);
   return MPCR_OK;
 }
 
-extern "C" int mpcr_rollout_cost_multi(mpcr_engine* e, const float* input, int layout, int nprob, int n_per,
-                                       const float* params, float* cost4, float* theta, float* thetadot,
-                                       uint64_t* best_keys, int index_base, int* status, int flags, void* stream) {
-  if (!e) return fail(MPCR_EINVAL, "null argument");
-  if (!(flags & MPCR_F_DEVICE_PTRS)) return fail(MPCR_EINVAL, "mpcr_rollout_cost_multi takes device pointers");
-  if (nprob < 1 || n_per < 1) return fail(MPCR_EINVAL, "nprob=%d, n_per=%d: both must be >= 1", nprob, n_per);
-  if ((long long)nprob * n_per > e->max_n)
-    return fail(MPCR_EINVAL, "nprob=%d x n_per=%d exceeds max_n=%d", nprob, n_per, e->max_n);
+// mpcr_rollout_cost_dp (nprob = 1) and mpcr_rollout_cost_multi.  One problem
+// runs the one-problem kernels through either entry (prob_n = 0): the MULTI
+// instantiations' problem lookup is paid only where there is one to make.
+static int rollout_dp(mpcr_engine* e, const float* input, int layout, int nprob, int n_per, const float* params,
+                      float* cost4, float* theta, float* thetadot, uint64_t* best_keys, int index_base, int* status,
+                      int flags, void* stream) {
   if (layout != MPCR_LAYOUT_XI && layout != MPCR_LAYOUT_THETADOT) return fail(MPCR_EINVAL, "bad layout %d", layout);
+  if (n_per == 0) return MPCR_OK;  // an empty batch: the buffers may be null
   if (!input || !params || !cost4) return fail(MPCR_EINVAL, "null argument");
   HIPCHK(hipSetDevice(e->device));
   hipStream_t st = (hipStream_t)stream;
   Launch l;
   l.layout = layout; l.n = nprob * n_per; l.index_base = index_base; l.dpar = params;
-  l.nprob = nprob; l.prob_n = n_per;
+  l.nprob = nprob; l.prob_n = nprob > 1 ? n_per : 0;
   l.in = input; l.cost4 = cost4; l.theta = theta; l.thetadot = thetadot;
   l.key = reinterpret_cast<unsigned long long*>(best_keys); l.status = status;
   l.reset_key = (flags & MPCR_F_RESET_BEST) != 0;
@@ -1366,6 +1353,25 @@ extern "C" int mpcr_rollout_cost_multi(mpcr_engine* e, const float* input, int l
   if (rc) return rc;
   if (flags & MPCR_F_SYNC) HIPCHK(hipStreamSynchronize(st));
   return MPCR_OK;
+}
+
+extern "C" int mpcr_rollout_cost_dp(mpcr_engine* e, const float* input, int layout, int n, const float* params,
+                                    float* cost4, float* theta, float* thetadot, uint64_t* best_key, int index_base,
+                                    int* status, int flags, void* stream) {
+  if (!e) return fail(MPCR_EINVAL, "null argument");
+  if (n < 0 || n > e->max_n) return fail(MPCR_EINVAL, "n=%d outside [0, max_n=%d]", n, e->max_n);
+  return rollout_dp(e, input, layout, 1, n, params, cost4, theta, thetadot, best_key, index_base, status, flags,
+                    stream);
+}
+
+extern "C" int mpcr_rollout_cost_multi(mpcr_engine* e, const float* input, int layout, int nprob, int n_per,
+                                       const float* params, float* cost4, float* theta, float* thetadot,
+                                       uint64_t* best_keys, int index_base, int* status, int flags, void* stream) {
+  if (!e) return fail(MPCR_EINVAL, "null argument");
+  if (!(flags & MPCR_F_DEVICE_PTRS)) return fail(MPCR_EINVAL, "mpcr_rollout_cost_multi takes device pointers");
+  if (int rc = check_multi(nprob, n_per, e->max_n)) return rc;
+  return rollout_dp(e, input, layout, nprob, n_per, params, cost4, theta, thetadot, best_keys, index_base, status,
+                    flags, stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -1655,44 +1661,41 @@ extern "C" int mpcr_argmin(mpcr_engine* e, const float* cost, int stride, int n,
   return MPCR_OK;
 }
 
-extern "C" int mpcr_topk(mpcr_engine* e, const float* cost, int stride, int n, int k, int* idx_out, int flags,
-                         void* stream) {
-  if (!e || !cost || !idx_out || stride <= 0 || n < 0) return fail(MPCR_EINVAL, "bad topk arguments");
-  if (k < 0 || k > n || k > TOPK_MAX) return fail(MPCR_EINVAL, "k=%d outside [0, min(n=%d, %d)]", k, n, TOPK_MAX);
+// mpcr_topk (nprob = 1) and mpcr_topk_multi: one workgroup per problem.
+// Without MPCR_F_DEVICE_PTRS (mpcr_topk alone allows it) cost and idx_out are
+// host arrays, staged through the engine's buffers.
+static int topk(mpcr_engine* e, const float* cost, int stride, int nprob, int n_per, int k, int* idx_out, int flags,
+                void* stream) {
+  if (!e || !cost || !idx_out || stride <= 0 || n_per < 0) return fail(MPCR_EINVAL, "bad topk arguments");
+  if (k < 0 || k > n_per || k > TOPK_MAX)
+    return fail(MPCR_EINVAL, "k=%d outside [0, min(n=%d, %d)]", k, n_per, TOPK_MAX);
   if (k == 0) return MPCR_OK;
   HIPCHK(hipSetDevice(e->device));
   hipStream_t st = (hipStream_t)stream;
-  if (flags & MPCR_F_DEVICE_PTRS) {
-    hipLaunchKernelGGL(topk_kernel, dim3(1), dim3(1024), 0, st, cost, stride, n, k, idx_out);
-    HIPCHK(hipGetLastError());
-    if (flags & MPCR_F_SYNC) HIPCHK(hipStreamSynchronize(st));
-    return MPCR_OK;
+  const bool host = !(flags & MPCR_F_DEVICE_PTRS);
+  if (host) {
+    if (n_per > e->max_n || stride > 4) return fail(MPCR_EINVAL, "host topk limited to max_n x 4");
+    HIPCHK(hipMemcpyAsync(e->d_cost, cost, sizeof(float) * (size_t)n_per * stride, hipMemcpyHostToDevice, st));
   }
-  if (n > e->max_n || stride > 4) return fail(MPCR_EINVAL, "host topk limited to max_n x 4");
-  HIPCHK(hipMemcpyAsync(e->d_cost, cost, sizeof(float) * (size_t)n * stride, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(topk_kernel, dim3(1), dim3(1024), 0, st, e->d_cost, stride, n, k, e->d_idx);
+  hipLaunchKernelGGL(topk_kernel, dim3(nprob), dim3(1024), 0, st, host ? e->d_cost : cost, stride, n_per, k,
+                     host ? e->d_idx : idx_out);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(idx_out, e->d_idx, sizeof(int) * k, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
+  if (host) HIPCHK(hipMemcpyAsync(idx_out, e->d_idx, sizeof(int) * k, hipMemcpyDeviceToHost, st));
+  if (host || (flags & MPCR_F_SYNC)) HIPCHK(hipStreamSynchronize(st));
   return MPCR_OK;
+}
+
+extern "C" int mpcr_topk(mpcr_engine* e, const float* cost, int stride, int n, int k, int* idx_out, int flags,
+                         void* stream) {
+  return topk(e, cost, stride, 1, n, k, idx_out, flags, stream);
 }
 
 extern "C" int mpcr_topk_multi(mpcr_engine* e, const float* cost, int stride, int nprob, int n_per, int k,
                                int* idx_out, int flags, void* stream) {
-  if (!e || !cost || !idx_out || stride <= 0) return fail(MPCR_EINVAL, "bad topk arguments");
+  if (!e) return fail(MPCR_EINVAL, "bad topk arguments");
   if (!(flags & MPCR_F_DEVICE_PTRS)) return fail(MPCR_EINVAL, "mpcr_topk_multi takes device pointers");
-  if (nprob < 1 || n_per < 1) return fail(MPCR_EINVAL, "nprob=%d, n_per=%d: both must be >= 1", nprob, n_per);
-  if ((long long)nprob * n_per > e->max_n)
-    return fail(MPCR_EINVAL, "nprob=%d x n_per=%d exceeds max_n=%d", nprob, n_per, e->max_n);
-  if (k < 0 || k > n_per || k > TOPK_MAX)
-    return fail(MPCR_EINVAL, "k=%d outside [0, min(n_per=%d, %d)]", k, n_per, TOPK_MAX);
-  if (k == 0) return MPCR_OK;
-  HIPCHK(hipSetDevice(e->device));
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(topk_kernel, dim3(nprob), dim3(1024), 0, st, cost, stride, n_per, k, idx_out);
-  HIPCHK(hipGetLastError());
-  if (flags & MPCR_F_SYNC) HIPCHK(hipStreamSynchronize(st));
-  return MPCR_OK;
+  if (int rc = check_multi(nprob, n_per, e->max_n)) return rc;
+  return topk(e, cost, stride, nprob, n_per, k, idx_out, flags, stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -1701,12 +1704,11 @@ extern "C" int mpcr_topk_multi(mpcr_engine* e, const float* cost, int stride, in
 struct mpcr_cem {
   int device = 0, nd = 0, H = 0, max_n = 0;
   int nprob = 1;      // Cholesky factors d_LT holds (mpcr_cem_set_problems)
-  int factored_n = 0; // problems the last factor call covered
+  int factored_n = 0; // problems the last factor call covered (0: none yet)
   float* d_X = nullptr;    // 3 x H x 12: Pdot, Pddot, P
   float* d_QT = nullptr;   // LD x LD
   float* d_QbT = nullptr;  // 5nd x LD
   float* d_LT = nullptr;   // LD x LD Cholesky factor (transposed, padded)
-  bool factored = false;
 };
 
 // get_Q_inv (SBP/mjx_planner.py:166-172 as restated by oracle/cem_np.q_inv):
@@ -1836,17 +1838,23 @@ extern "C" void mpcr_cem_free(mpcr_cem* c) {
   delete c;
 }
 
-extern "C" int mpcr_cem_factor(mpcr_cem* c, const float* cov, float reg, int flags, void* stream) {
+// mpcr_cem_factor (nprob = 1) and mpcr_cem_factor_multi: one workgroup per problem
+static int cem_factor(mpcr_cem* c, const float* cov, int nprob, float reg, int flags, void* stream) {
   if (!c || !cov) return fail(MPCR_EINVAL, "null argument");
   if (!(flags & MPCR_F_DEVICE_PTRS)) return fail(MPCR_EINVAL, "mpcr_cem_factor takes device pointers");
+  if (nprob < 1 || nprob > c->nprob)
+    return fail(MPCR_EINVAL, "nprob=%d outside [1, %d] (mpcr_cem_set_problems)", nprob, c->nprob);
   HIPCHK(hipSetDevice(c->device));
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(cholesky_kernel, dim3(1), dim3(256), 0, st, cov, c->nd, reg, c->d_LT);
+  hipLaunchKernelGGL(cholesky_kernel, dim3(nprob), dim3(256), 0, st, cov, c->nd, reg, c->d_LT);
   HIPCHK(hipGetLastError());
-  c->factored = true;
-  c->factored_n = 1;
+  c->factored_n = nprob;
   if (flags & MPCR_F_SYNC) HIPCHK(hipStreamSynchronize(st));
   return MPCR_OK;
+}
+
+extern "C" int mpcr_cem_factor(mpcr_cem* c, const float* cov, float reg, int flags, void* stream) {
+  return cem_factor(c, cov, 1, reg, flags, stream);
 }
 
 // Room for nprob Cholesky factors (the multi-problem entry points).  An
@@ -1867,24 +1875,12 @@ extern "C" int mpcr_cem_set_problems(mpcr_cem* c, int nprob) {
   (void)hipFree(c->d_LT);
   c->d_LT = lt;
   c->nprob = nprob;
-  c->factored = false;
   c->factored_n = 0;
   return MPCR_OK;
 }
 
 extern "C" int mpcr_cem_factor_multi(mpcr_cem* c, const float* cov, int nprob, float reg, int flags, void* stream) {
-  if (!c || !cov) return fail(MPCR_EINVAL, "null argument");
-  if (!(flags & MPCR_F_DEVICE_PTRS)) return fail(MPCR_EINVAL, "mpcr_cem_factor_multi takes device pointers");
-  if (nprob < 1 || nprob > c->nprob)
-    return fail(MPCR_EINVAL, "nprob=%d outside [1, %d] (mpcr_cem_set_problems)", nprob, c->nprob);
-  HIPCHK(hipSetDevice(c->device));
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(cholesky_kernel, dim3(nprob), dim3(256), 0, st, cov, c->nd, reg, c->d_LT);
-  HIPCHK(hipGetLastError());
-  c->factored = true;
-  c->factored_n = nprob;
-  if (flags & MPCR_F_SYNC) HIPCHK(hipStreamSynchronize(st));
-  return MPCR_OK;
+  return cem_factor(c, cov, nprob, reg, flags, stream);
 }
 
 // mpcr_cem_sample_project (nprob = 1, n candidates) and _multi (nprob
@@ -1892,50 +1888,18 @@ extern "C" int mpcr_cem_factor_multi(mpcr_cem* c, const float* cov, int nprob, f
 static int sample_project_launch(mpcr_cem* c, int nprob, int n, const float* mean, uint64_t seed, uint64_t seed_step,
                                  uint64_t counter, int index_base, const float* xi_in, float* xi_samples,
                                  const float* b_eq, int beq_stride, int beq_pstride, int maxiter, const float* bounds,
-                                 float rho, float* xi_out, int flags, hipStream_t st);
-
-extern "C" int mpcr_cem_sample_project(mpcr_cem* c, int n, const float* mean, uint64_t seed, uint64_t counter,
-                                       int index_base, const float* xi_in, float* xi_samples, const float* b_eq, int beq_stride,
-                                       int maxiter, const float* bounds, float rho, float* xi_out, int flags,
-                                       void* stream) {
-  if (!c || !xi_out) return fail(MPCR_EINVAL, "null argument");
+                                 float rho, float* xi_out, int flags, void* stream) {
+  if (!xi_out) return fail(MPCR_EINVAL, "null argument");
   if (!(flags & MPCR_F_DEVICE_PTRS)) return fail(MPCR_EINVAL, "mpcr_cem_sample_project takes device pointers");
-  if (n < 0 || n > c->max_n) return fail(MPCR_EINVAL, "n=%d outside [0, max_n=%d]", n, c->max_n);
   if (!mean && !xi_in) return fail(MPCR_EINVAL, "need mean (sampling) or xi_in");
-  if (mean && !c->factored) return fail(MPCR_EINVAL, "sampling before mpcr_cem_factor");
+  if (mean && c->factored_n < nprob)
+    return fail(MPCR_EINVAL, "sampling %d problem(s) after a factor call that covered %d (mpcr_cem_factor)", nprob,
+                c->factored_n);
   if (maxiter < 0 || (maxiter > 0 && (!b_eq || !bounds || beq_stride < 0)))
     return fail(MPCR_EINVAL, "projection needs b_eq, bounds and maxiter >= 0");
   if (n == 0) return MPCR_OK;
   HIPCHK(hipSetDevice(c->device));
-  return sample_project_launch(c, 1, n, mean, seed, 0, counter, index_base, xi_in, xi_samples, b_eq, beq_stride, 0,
-                               maxiter, bounds, rho, xi_out, flags, (hipStream_t)stream);
-}
-
-extern "C" int mpcr_cem_sample_project_multi(mpcr_cem* c, int nprob, int n_per, const float* mean, uint64_t seed,
-                                             uint64_t seed_step, uint64_t counter, int index_base, const float* xi_in,
-                                             float* xi_samples, const float* b_eq, int maxiter, const float* bounds,
-                                             float rho, float* xi_out, int flags, void* stream) {
-  if (!c || !xi_out) return fail(MPCR_EINVAL, "null argument");
-  if (!(flags & MPCR_F_DEVICE_PTRS)) return fail(MPCR_EINVAL, "mpcr_cem_sample_project_multi takes device pointers");
-  if (nprob < 1 || n_per < 1) return fail(MPCR_EINVAL, "nprob=%d, n_per=%d: both must be >= 1", nprob, n_per);
-  if ((long long)nprob * n_per > c->max_n)
-    return fail(MPCR_EINVAL, "nprob=%d x n_per=%d exceeds max_n=%d", nprob, n_per, c->max_n);
-  if (nprob > 65535) return fail(MPCR_EINVAL, "nprob=%d exceeds the grid's 65535", nprob);
-  if (!mean && !xi_in) return fail(MPCR_EINVAL, "need mean (sampling) or xi_in");
-  if (mean && c->factored_n < nprob)
-    return fail(MPCR_EINVAL, "sampling %d problems after a factor call that covered %d (mpcr_cem_factor_multi)", nprob,
-                c->factored_n);
-  if (maxiter < 0 || (maxiter > 0 && (!b_eq || !bounds)))
-    return fail(MPCR_EINVAL, "projection needs b_eq, bounds and maxiter >= 0");
-  HIPCHK(hipSetDevice(c->device));
-  return sample_project_launch(c, nprob, n_per, mean, seed, seed_step, counter, index_base, xi_in, xi_samples, b_eq, 0,
-                               5 * c->nd, maxiter, bounds, rho, xi_out, flags, (hipStream_t)stream);
-}
-
-static int sample_project_launch(mpcr_cem* c, int nprob, int n, const float* mean, uint64_t seed, uint64_t seed_step,
-                                 uint64_t counter, int index_base, const float* xi_in, float* xi_samples,
-                                 const float* b_eq, int beq_stride, int beq_pstride, int maxiter, const float* bounds,
-                                 float rho, float* xi_out, int flags, hipStream_t st) {
+  hipStream_t st = (hipStream_t)stream;
   ProjArgs a;
   std::memset(&a, 0, sizeof(a));
   a.xi_in = xi_in;
@@ -1973,6 +1937,28 @@ static int sample_project_launch(mpcr_cem* c, int nprob, int n, const float* mea
   return MPCR_OK;
 }
 
+extern "C" int mpcr_cem_sample_project(mpcr_cem* c, int n, const float* mean, uint64_t seed, uint64_t counter,
+                                       int index_base, const float* xi_in, float* xi_samples, const float* b_eq, int beq_stride,
+                                       int maxiter, const float* bounds, float rho, float* xi_out, int flags,
+                                       void* stream) {
+  if (!c) return fail(MPCR_EINVAL, "null argument");
+  if (n < 0 || n > c->max_n) return fail(MPCR_EINVAL, "n=%d outside [0, max_n=%d]", n, c->max_n);
+  return sample_project_launch(c, 1, n, mean, seed, 0, counter, index_base, xi_in, xi_samples, b_eq, beq_stride, 0,
+                               maxiter, bounds, rho, xi_out, flags, stream);
+}
+
+// every candidate of problem p reads the boundary row b_eq + 5 nd p
+extern "C" int mpcr_cem_sample_project_multi(mpcr_cem* c, int nprob, int n_per, const float* mean, uint64_t seed,
+                                             uint64_t seed_step, uint64_t counter, int index_base, const float* xi_in,
+                                             float* xi_samples, const float* b_eq, int maxiter, const float* bounds,
+                                             float rho, float* xi_out, int flags, void* stream) {
+  if (!c) return fail(MPCR_EINVAL, "null argument");
+  if (int rc = check_multi(nprob, n_per, c->max_n)) return rc;
+  if (nprob > 65535) return fail(MPCR_EINVAL, "nprob=%d exceeds the grid's 65535", nprob);
+  return sample_project_launch(c, nprob, n_per, mean, seed, seed_step, counter, index_base, xi_in, xi_samples, b_eq, 0,
+                               5 * c->nd, maxiter, bounds, rho, xi_out, flags, stream);
+}
+
 extern "C" int mpcr_project(mpcr_cem* c, const float* xi, const float* b_eq, int beq_stride, int n, int maxiter,
                             const float* bounds, float rho, float* xi_out, int flags, void* stream) {
   if (!xi) return fail(MPCR_EINVAL, "null xi");
@@ -1980,31 +1966,14 @@ extern "C" int mpcr_project(mpcr_cem* c, const float* xi, const float* b_eq, int
                                  flags, stream);
 }
 
-extern "C" int mpcr_cem_update(mpcr_cem* c, const float* xi, int n, const float* cost, int stride,
-                               const int* elite_idx, int k, float lamda, float alpha_mean, float alpha_cov, float reg,
-                               float* mean, float* cov, int flags, void* stream) {
+// mpcr_cem_update (nprob = 1) and mpcr_cem_update_multi: one workgroup per problem
+static int cem_update(mpcr_cem* c, const float* xi, int nprob, int n_per, const float* cost, int stride,
+                      const int* elite_idx, int k, float lamda, float alpha_mean, float alpha_cov, float reg,
+                      float* mean, float* cov, int flags, void* stream) {
   if (!c || !xi || !cost || !elite_idx || !mean || !cov || stride <= 0) return fail(MPCR_EINVAL, "null argument");
   if (!(flags & MPCR_F_DEVICE_PTRS)) return fail(MPCR_EINVAL, "mpcr_cem_update takes device pointers");
-  if (k <= 0 || k > n || k > TOPK_MAX) return fail(MPCR_EINVAL, "k=%d outside [1, min(n=%d, %d)]", k, n, TOPK_MAX);
-  HIPCHK(hipSetDevice(c->device));
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(cem_update_kernel, dim3(1), dim3(1024), 0, st, xi, n, c->nd * PJ_NB, cost, stride, elite_idx, k,
-                     lamda, alpha_mean, alpha_cov, reg, mean, cov);
-  HIPCHK(hipGetLastError());
-  if (flags & MPCR_F_SYNC) HIPCHK(hipStreamSynchronize(st));
-  return MPCR_OK;
-}
-
-extern "C" int mpcr_cem_update_multi(mpcr_cem* c, const float* xi, int nprob, int n_per, const float* cost, int stride,
-                                     const int* elite_idx, int k, float lamda, float alpha_mean, float alpha_cov,
-                                     float reg, float* mean, float* cov, int flags, void* stream) {
-  if (!c || !xi || !cost || !elite_idx || !mean || !cov || stride <= 0) return fail(MPCR_EINVAL, "null argument");
-  if (!(flags & MPCR_F_DEVICE_PTRS)) return fail(MPCR_EINVAL, "mpcr_cem_update_multi takes device pointers");
-  if (nprob < 1 || n_per < 1) return fail(MPCR_EINVAL, "nprob=%d, n_per=%d: both must be >= 1", nprob, n_per);
-  if ((long long)nprob * n_per > c->max_n)
-    return fail(MPCR_EINVAL, "nprob=%d x n_per=%d exceeds max_n=%d", nprob, n_per, c->max_n);
   if (k <= 0 || k > n_per || k > TOPK_MAX)
-    return fail(MPCR_EINVAL, "k=%d outside [1, min(n_per=%d, %d)]", k, n_per, TOPK_MAX);
+    return fail(MPCR_EINVAL, "k=%d outside [1, min(n=%d, %d)]", k, n_per, TOPK_MAX);
   HIPCHK(hipSetDevice(c->device));
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(cem_update_kernel, dim3(nprob), dim3(1024), 0, st, xi, n_per, c->nd * PJ_NB, cost, stride,
@@ -2012,6 +1981,22 @@ extern "C" int mpcr_cem_update_multi(mpcr_cem* c, const float* xi, int nprob, in
   HIPCHK(hipGetLastError());
   if (flags & MPCR_F_SYNC) HIPCHK(hipStreamSynchronize(st));
   return MPCR_OK;
+}
+
+extern "C" int mpcr_cem_update(mpcr_cem* c, const float* xi, int n, const float* cost, int stride,
+                               const int* elite_idx, int k, float lamda, float alpha_mean, float alpha_cov, float reg,
+                               float* mean, float* cov, int flags, void* stream) {
+  return cem_update(c, xi, 1, n, cost, stride, elite_idx, k, lamda, alpha_mean, alpha_cov, reg, mean, cov, flags,
+                    stream);
+}
+
+extern "C" int mpcr_cem_update_multi(mpcr_cem* c, const float* xi, int nprob, int n_per, const float* cost, int stride,
+                                     const int* elite_idx, int k, float lamda, float alpha_mean, float alpha_cov,
+                                     float reg, float* mean, float* cov, int flags, void* stream) {
+  if (!c) return fail(MPCR_EINVAL, "null argument");
+  if (int rc = check_multi(nprob, n_per, c->max_n)) return rc;
+  return cem_update(c, xi, nprob, n_per, cost, stride, elite_idx, k, lamda, alpha_mean, alpha_cov, reg, mean, cov,
+                    flags, stream);
 }
 
 #include "comm.hip"

@@ -92,7 +92,7 @@ struct RolloutArgs {
   // problem p owns candidates [p prob_n, (p + 1) prob_n) of the call, reads
   // its parameter block from dpar + p PAR_N and reduces into best_key[p] with
   // the low word index_base + (index within the problem).  prob_n = 0: one
-  // problem.  prob_off is this launch's first candidate relative to the call
+  // problem (also what the host sets for a multi call of one).  prob_off is this launch's first candidate relative to the call
   // (group_args), and index_base then stays the call's.  Read by the MULTI
   // instantiations of rollout_kernel, which the launchers pick for prob_n > 0.
   int prob_n, prob_off;

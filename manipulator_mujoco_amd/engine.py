@@ -157,23 +157,37 @@ class Engine:
         p[16:20] = np.asarray(qtgt, dtype=np.float32).reshape(-1)[:4]
         return p
 
-    def rollout_cost_dp(self, inp, layout: int, params, cost4, theta=None, thetadot=None, best_key=None,
-                        index_base: int = 0, status=None, reset_best: bool = True, stream=None):
-        """``rollout_cost`` with the per-call arguments in a device tensor
-        (``params``, 20 float32, see ``Engine.params``): graph-capturable."""
+    def _rollout_dp(self, nprob, inp, layout, params, cost4, theta, thetadot, best_keys, index_base, status,
+                    reset_best, stream):
+        """nprob None: ``rollout_cost_dp`` (its own C entry, which takes an
+        empty batch); else ``rollout_cost_multi``."""
         import torch
         for name, t in (("input", inp), ("params", params), ("cost4", cost4)):
             if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
                 raise ValueError(f"{name} must be a contiguous float32 CUDA tensor")
-        if params.numel() < 20:
-            raise ValueError("params needs 20 floats")
+        n, lib = int(inp.shape[0]), _lib.load()
+        fn, shape = lib.mpcr_rollout_cost_dp, (n,)
+        if nprob is not None:
+            if nprob < 1 or n % nprob:
+                raise ValueError(f"input rows ({n}) must split evenly over nprob={nprob} problems")
+            if best_keys is not None and best_keys.numel() < nprob:
+                raise ValueError("best_keys needs nprob elements")
+            fn, shape = lib.mpcr_rollout_cost_multi, (nprob, n // nprob)
+        if params.numel() < 20 * (nprob or 1):
+            raise ValueError("params needs 20 floats per problem")
         ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
         st = stream if stream is not None else torch.cuda.current_stream(inp.device).cuda_stream
         flags = MPCR_F_DEVICE_PTRS | (MPCR_F_RESET_BEST if reset_best else 0)
-        check(_lib.load().mpcr_rollout_cost_dp(self.handle, ptr(inp), layout, int(inp.shape[0]), ptr(params),
-                                               ptr(cost4), ptr(theta), ptr(thetadot), ptr(best_key),
-                                               int(index_base), ptr(status), flags, ctypes.c_void_p(st)))
+        check(fn(self.handle, ptr(inp), layout, *shape, ptr(params), ptr(cost4), ptr(theta), ptr(thetadot),
+                 ptr(best_keys), int(index_base), ptr(status), flags, ctypes.c_void_p(st)))
         return cost4
+
+    def rollout_cost_dp(self, inp, layout: int, params, cost4, theta=None, thetadot=None, best_key=None,
+                        index_base: int = 0, status=None, reset_best: bool = True, stream=None):
+        """``rollout_cost`` with the per-call arguments in a device tensor
+        (``params``, 20 float32, see ``Engine.params``): graph-capturable."""
+        return self._rollout_dp(None, inp, layout, params, cost4, theta, thetadot, best_key, index_base, status,
+                                reset_best, stream)
 
     def rollout_cost_multi(self, inp, layout: int, params, nprob: int, cost4, theta=None, thetadot=None,
                            best_keys=None, index_base: int = 0, status=None, reset_best: bool = True, stream=None):
@@ -182,25 +196,10 @@ class Engine:
         (p + 1) n_per); ``params`` is (nprob, 20), one ``Engine.params`` block
         per problem; ``best_keys`` an int64 tensor of nprob elements whose key
         p carries ``index_base`` + the index within problem p.  Bitwise the
-        ``rollout_cost_dp`` calls on the slices.  Graph-capturable."""
-        import torch
-        for name, t in (("input", inp), ("params", params), ("cost4", cost4)):
-            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
-                raise ValueError(f"{name} must be a contiguous float32 CUDA tensor")
-        nprob = int(nprob)
-        if nprob < 1 or inp.shape[0] % nprob:
-            raise ValueError(f"input rows ({inp.shape[0]}) must split evenly over nprob={nprob} problems")
-        if params.numel() < 20 * nprob:
-            raise ValueError("params needs nprob x 20 floats")
-        if best_keys is not None and best_keys.numel() < nprob:
-            raise ValueError("best_keys needs nprob elements")
-        ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
-        st = stream if stream is not None else torch.cuda.current_stream(inp.device).cuda_stream
-        flags = MPCR_F_DEVICE_PTRS | (MPCR_F_RESET_BEST if reset_best else 0)
-        check(_lib.load().mpcr_rollout_cost_multi(self.handle, ptr(inp), layout, nprob, int(inp.shape[0]) // nprob,
-                                                  ptr(params), ptr(cost4), ptr(theta), ptr(thetadot), ptr(best_keys),
-                                                  int(index_base), ptr(status), flags, ctypes.c_void_p(st)))
-        return cost4
+        ``rollout_cost_dp`` calls on the slices; one problem runs the very
+        kernel ``rollout_cost_dp`` runs.  Graph-capturable."""
+        return self._rollout_dp(int(nprob), inp, layout, params, cost4, theta, thetadot, best_keys, index_base,
+                                status, reset_best, stream)
 
     def trace(self, inp, layout: int, q0, w, ptgt, qtgt):
         """Debug/parity run (host arrays): cost4, theta, per-step eef pose, masked slot distances."""

@@ -24,8 +24,11 @@ on the first call (per-tick inputs live in static device buffers).
 
 With ``num_problems=B``, ``compute_cem_batch`` plans B independent problems
 (own start state, target, weights, distribution and best key) in one tick:
-the same five kernels per iteration, each launched once over all problems
-(the ``*_multi`` entry points), bitwise what B one-problem planners compute.
+the same five kernels per iteration, each launched once over all problems,
+bitwise what B one-problem planners compute.  There is one tick path: every
+planner calls the ``*_multi`` entry points over its B problems, and the
+default B = 1 is their ``nprob = 1`` case (the one-problem kernels), which
+``compute_cem`` and ``compute_cem_batch`` share, captured graph included.
 
 Reference behaviours kept on purpose, each behind a flag:
   * elites are gathered from the *unprojected* samples (``elite_from_filtered=False``)
@@ -175,8 +178,6 @@ class cem_planner:  # noqa: N801 (reference name)
         self._costs = torch.empty((it_n,) + pb + (n, 4), **f32)
         self._mean_in = torch.empty(pb + (self.nvar,), **f32)
         self._graphs = None
-        self._multi = False         # compute_cem_batch: the segments below run the multi-problem kernels
-        self._graphs_multi = None   # ... and replay their own captured tick
         if verbose and self.rank == 0:
             self.print_info()
 
@@ -198,36 +199,25 @@ class cem_planner:  # noqa: N801 (reference name)
             self._mean.copy_(self._mean_in)
             self._cov.copy_(self._eye10)  # (broadcast over the problems)
         last = it == self.maxiter_cem - 1
-        if self._multi:
-            # the same kernels, one workgroup / grid row per problem
-            B, n = self.num_problems, self.n_local
-            self.cem.factor_multi(self._cov.view(B, self.nvar, self.nvar), 0.003)
-            self.cem.sample_project_multi(B, n, self._mean, self.seed, it, self._beq, self.maxiter_projection, bounds,
-                                          rho=1.0, seed_step=self.seed_step, xi_samples=self._xs, out=self._xf)
-            self.engine.rollout_cost_multi(self._xf.view(B * n, self.nvar), MPCR_LAYOUT_XI, self._par, B,
-                                           self._costs[it], theta=self._theta[it], thetadot=self._thetadot[it],
-                                           best_keys=self._key if last else None)
-            return
-        self.cem.factor(self._cov, 0.003)
-        self.cem.sample_project(self.n_local, self._mean, self.seed, it, self._beq, self.maxiter_projection, bounds,
-                                rho=1.0, xi_samples=self._xs, out=self._xf, index_base=self.index_base)
-        self.engine.rollout_cost_dp(self._xf, MPCR_LAYOUT_XI, self._par, self._costs[it], theta=self._theta[it],
-                                    thetadot=self._thetadot[it], best_key=self._key if last else None,
-                                    index_base=self.index_base)
+        # one workgroup / grid row per problem; one problem (B = 1, this
+        # rank's shard of it from index_base on) is the same calls
+        B, n = self.num_problems, self.n_local
+        self.cem.factor_multi(self._cov.view(B, self.nvar, self.nvar), 0.003)
+        self.cem.sample_project_multi(B, n, self._mean, self.seed, it, self._beq, self.maxiter_projection, bounds,
+                                      rho=1.0, seed_step=self.seed_step, xi_samples=self._xs, out=self._xf,
+                                      index_base=self.index_base)
+        self.engine.rollout_cost_multi(self._xf.view(B * n, self.nvar), MPCR_LAYOUT_XI, self._par, B,
+                                       self._costs[it], theta=self._theta[it], thetadot=self._thetadot[it],
+                                       best_keys=self._key if last else None, index_base=self.index_base)
 
     def _seg_local_update(self, it):
         """compute_ellite_samples + compute_mean_cov on one rank (:355-360)."""
         src = self._xf if self.elite_from_filtered else self._xs
-        if self._multi:
-            B, n = self.num_problems, self.n_local
-            idx = self._idx.view(B, self.ellite_num)
-            topk_multi(self.engine, self._costs[it], B, self.ellite_num, stride=4, out=idx)
-            self.cem.update_multi(src.view(B, n, self.nvar), self._costs[it], 4, idx, self.lamda, self.alpha_mean,
-                                  self.alpha_cov, self._mean, self._cov, reg=1e-4)
-            return
-        topk(self.engine, self._costs[it], self.ellite_num, stride=4, out=self._idx)
-        self.cem.update(src, self._costs[it], 4, self._idx, self.lamda, self.alpha_mean, self.alpha_cov,
-                        self._mean, self._cov, reg=1e-4)
+        B, n = self.num_problems, self.n_local
+        idx = self._idx.view(B, self.ellite_num)
+        topk_multi(self.engine, self._costs[it], B, self.ellite_num, stride=4, out=idx)
+        self.cem.update_multi(src.view(B, n, self.nvar), self._costs[it], 4, idx, self.lamda, self.alpha_mean,
+                              self.alpha_cov, self._mean, self._cov, reg=1e-4)
 
     def _topk_fn(self, cost, k):
         return topk(self.engine, cost, k, stride=1)
@@ -300,6 +290,19 @@ class cem_planner:  # noqa: N801 (reference name)
         finally:
             self.graph = graph
 
+    def _stage(self, xi_mean, init_pos, init_vel, init_acc, target_pos, target_rot, weights):
+        """The tick's inputs, one row per problem, into the static device
+        buffers the (captured) kernels read."""
+        import torch
+        B, d = self.num_problems, self.num_dof
+        self._mean_in.copy_(torch.as_tensor(np.ascontiguousarray(xi_mean)).view(self._mean_in.shape))
+        z = np.zeros((B, d))
+        st = np.stack([init_pos, init_vel, init_acc, z, z], axis=2)  # state_term per problem (:374-384)
+        # compute_boundary_vec (:174-178)
+        self._beq.copy_(torch.as_tensor(st.reshape(B, 5 * d).astype(np.float32)).view(self._beq.shape))
+        par = np.stack([Engine.params(init_pos[p], weights[p], target_pos[p], target_rot[p]) for p in range(B)])
+        self._par.copy_(torch.as_tensor(par).view(self._par.shape))
+
     def compute_cem(self, xi_mean, init_pos=(1.5, -1.8, 1.75, -1.25, -1.6, 0.0), init_vel=None, init_acc=None,
                     target_pos=None, target_rot=None):
         """One MPC tick of CEM (SBP/mjx_planner.py:364-406). Returns the reference 9-tuple (numpy)."""
@@ -321,11 +324,8 @@ class cem_planner:  # noqa: N801 (reference name)
 
         if self.ellite_num < 1:
             raise ValueError("num_elite * num_batch must select at least one elite")
-        # per-tick inputs into the static device buffers the (captured) kernels read
-        self._mean_in.copy_(torch.as_tensor(np.asarray(xi_mean, np.float32).reshape(self.nvar)))
-        st = np.stack([init_pos, init_vel, init_acc, np.zeros(d), np.zeros(d)], axis=1)  # state_term (:374-384)
-        self._beq.copy_(torch.as_tensor(st.reshape(5 * d).astype(np.float32)))  # compute_boundary_vec (:174-178)
-        self._par.copy_(torch.as_tensor(Engine.params(init_pos, w, target_pos, target_rot)))
+        self._stage(np.asarray(xi_mean, np.float32).reshape(1, self.nvar), init_pos[None], init_vel[None],
+                    init_acc[None], target_pos[None], target_rot[None], [w])
         self._run_iterations()
 
         costs, theta, thetadot = self._costs, self._theta, self._thetadot
@@ -384,19 +384,8 @@ class cem_planner:  # noqa: N801 (reference name)
             weights = [[self.cost_weights["w_pos"], self.cost_weights["w_rot"], self.cost_weights["w_col"]]] * B
         weights = rows(weights, 3, "weights", np.float32)
 
-        # per-tick inputs into the static device buffers the (captured) kernels read
-        self._mean_in.copy_(torch.as_tensor(np.ascontiguousarray(xi_mean)).view(self._mean_in.shape))
-        z = np.zeros((B, d))
-        st = np.stack([init_pos, init_vel, init_acc, z, z], axis=2)  # state_term per problem (:374-384)
-        self._beq.copy_(torch.as_tensor(st.reshape(B, 5 * d).astype(np.float32)).view(self._beq.shape))
-        par = np.stack([Engine.params(init_pos[p], weights[p], target_pos[p], target_rot[p]) for p in range(B)])
-        self._par.copy_(torch.as_tensor(par).view(self._par.shape))
-        self._multi, single = True, self._graphs
-        self._graphs = self._graphs_multi
-        try:
-            self._run_iterations()
-        finally:
-            self._graphs_multi, self._graphs, self._multi = self._graphs, single, False
+        self._stage(xi_mean, init_pos, init_vel, init_acc, target_pos, target_rot, weights)
+        self._run_iterations()
 
         # each problem's best candidate of the last iteration: the low word of
         # its key is the index within the problem; one gather, one transfer
