@@ -22,6 +22,7 @@
 // rollout_narrow.hip and rollout_wide.hip; its launchers declared in rollout.h); cem.hip:
 // the CEM distribution step
 #include "rollout.h"
+#include "step_table.h"
 
 // horizon segments of dual-arm rollouts (rollout_launch): steps per segment
 // (0 = one launch) and candidate groups on their own streams.  Measured
@@ -114,6 +115,53 @@ struct mpcr_engine {
   int* d_cone_face = nullptr;
   bool wide = false;  // kernel variant: rollout_kernel<32, 32, 72, true>
 };
+
+// build_step_table (step_table.h) derives the moving-body map, the static
+// poses, the tree numbering and the dof kinds from the model on its own (it is
+// host code without HIP, tested on the CPU); build_dev_model derives them for
+// the device model.  Every resolved index and every value the two copy from
+// the model must agree, bit for bit: checked at each engine creation, so the
+// two cannot drift apart unnoticed.
+static_assert(ST_NB == DX_NB && ST_NV == DX_NV && ST_NP == DX_NP && ST_NJ == DX_NJ && ST_NEQ == DX_NEQ,
+              "step table capacities = device model capacities");
+static_assert(ST_BK_FREE == BK_FREE && ST_BK_HINGE == BK_HINGE && ST_BK_SLIDE == BK_SLIDE && ST_BK_WELD == BK_WELD,
+              "body kinds");
+static_assert(ST_MINVAL == kMinVal && ST_MINIMP == kMinImp && ST_MAXIMP == kMaxImp, "the kernel's impedance constants");
+static bool step_table_matches(const StepTable& t, const DevModel& d) {
+  auto same = [](const float* a, const float* b, int n) { return std::memcmp(a, b, sizeof(float) * n) == 0; };
+  if (t.nbody != d.nbody) return false;
+  for (int i = 0; i < d.nbody; i++) {
+    const StepBody& r = t.body[i];
+    const int j = d.body_jnt[i];
+    if (r.kind != d.body_kind[i] || r.anc != d.body_anc[i] || r.qposadr != (j >= 0 ? d.jnt_qposadr[j] : -1)) return false;
+    if (!same(r.bquat, d.body_bquat[i], 4) || !same(r.bpos, d.body_bpos[i], 3) || !same(r.ipos, d.body_ipos[i], 3))
+      return false;
+    if (j >= 0 && r.qpos0 != d.jnt_qpos0[j]) return false;
+    if (r.kind == BK_HINGE && (!same(r.axis, d.jnt_axis[j], 3) || !same(r.jpos, d.jnt_pos[j], 3))) return false;
+  }
+  for (int i = 0; i < d.nv; i++) {
+    const StepDof& r = t.dof[i];
+    const int j = d.dof_jnt[i];
+    if (r.body != d.dof_body[i] || r.kind != d.dof_kind[i] || r.sub != d.dof_sub[i] ||
+        r.tree != (r.body >= 0 ? d.body_tree[r.body] : -1))
+      return false;
+    if (!same(r.axis, d.jnt_axis[j], 3) || !same(r.jpos, d.jnt_pos[j], 3)) return false;
+  }
+  for (int p = 0; p < d.npair; p++) {
+    const StepRow& r = t.row[ST_ROW_PAIR + p];
+    if (r.margin != d.pair_margin[p] || ((r.flags & ST_CONDIM1) != 0) != (d.pair_condim[p] == 1)) return false;
+  }
+  for (int j = 0; j < d.njnt; j++) {
+    const StepRow& r = t.row[ST_ROW_JNT + j];
+    const bool lim = d.jnt_limited[j] && (d.jnt_type[j] == MPCR_JNT_SLIDE || d.jnt_type[j] == MPCR_JNT_HINGE);
+    if (r.qposadr != d.jnt_qposadr[j] || r.dofadr != d.jnt_dofadr[j] || ((r.flags & ST_LIMITED) != 0) != lim ||
+        r.margin != d.jnt_margin[j] || r.diag != d.dof_invweight0[d.jnt_dofadr[j]] || !same(r.range, d.jnt_range[j], 2))
+      return false;
+  }
+  for (int q = 0; q < d.neq; q++)
+    if (t.row[ST_ROW_EQ + q].diag != d.eq_diag[q]) return false;
+  return true;
+}
 
 // The narrow variant (16-wide solves, 16 bodies, 24 collision geoms, Euler,
 // joint equalities only) covers the single-arm scenes; anything else runs the
@@ -1096,7 +1144,10 @@ extern "C" int mpcr_engine_create(const mpcr_model* m, int device, int max_n, in
   }
   const int nc = e->host.nctrl;
   const size_t in_cols = (size_t)nc * (horizon > nbasis ? horizon : nbasis);
-  if (hipMalloc(&e->d_model, sizeof(DevModel)) != hipSuccess ||
+  // the device model with the narrow kernels' step table directly behind it
+  // (step_table.h: the kernels address it as model + 1)
+  static_assert(sizeof(DevModel) % alignof(mpcr::StepTable) == 0, "the step table's alignment behind the device model");
+  if (hipMalloc(reinterpret_cast<void**>(&e->d_model), sizeof(DevModel) + sizeof(StepTable)) != hipSuccess ||
       hipMalloc(&e->d_pdot, sizeof(float) * horizon * nbasis) != hipSuccess ||
       hipMalloc(&e->d_in, sizeof(float) * max_n * in_cols) != hipSuccess ||
       hipMalloc(&e->d_cost, sizeof(float) * max_n * 4) != hipSuccess ||
@@ -1120,6 +1171,23 @@ extern "C" int mpcr_engine_create(const mpcr_model* m, int device, int max_n, in
                               (size_t)horizon) != hipSuccess) {
     mpcr_engine_free(e);
     return fail(MPCR_ENOMEM, "device allocation failed");
+  }
+  if (!e->wide) {
+    // built once: the model and the timestep are fixed for the engine's life
+    // (single-arm kernels only: the dual-arm ones never read it)
+    std::vector<StepTable> step(1);
+    if (build_step_table(e->host, step[0]) != 0) {
+      mpcr_engine_free(e);
+      return fail(MPCR_EMODEL, "model exceeds the step table's capacities");
+    }
+    if (!step_table_matches(step[0], e->dev)) {
+      mpcr_engine_free(e);
+      return fail(MPCR_EMODEL, "step table and device model disagree (step_table.h / build_dev_model)");
+    }
+    if (hipMemcpy(e->d_model + 1, step.data(), sizeof(StepTable), hipMemcpyHostToDevice) != hipSuccess) {
+      mpcr_engine_free(e);
+      return fail(MPCR_EHIP, "step table upload failed");
+    }
   }
   if (hipMemcpy(e->d_model, &e->dev, sizeof(DevModel), hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(e->d_pdot, pdot, sizeof(float) * horizon * nbasis, hipMemcpyHostToDevice) != hipSuccess ||

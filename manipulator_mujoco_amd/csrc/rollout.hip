@@ -19,6 +19,7 @@
 //   mjx.step                 mujoco-mjx 3.3.1 (third party)
 #pragma once
 #include "rollout.h"
+#include "step_table.h"
 #include "../../include/mpcr_model.h"  // MPCR_LUT_R (the engine's hull start table)
 
 namespace mpcr {
@@ -121,6 +122,25 @@ __device__ __forceinline__ const MPCR_GMEM DevModel* uniform_model(const DevMode
   const unsigned long long a = reinterpret_cast<unsigned long long>(p);
   const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
   return reinterpret_cast<const MPCR_GMEM DevModel*>(((unsigned long long)hi << 32) | lo);
+}
+
+// MPCR_STEP_TABLE: which phases of the single-arm kernels read the step table
+// (bit 0 kinematics, 1 motion subspaces, 2 constraint rows); 7 is the shipped
+// build, the others attribute a change in results or time
+#ifndef MPCR_STEP_TABLE
+#define MPCR_STEP_TABLE 7
+#endif
+template <class S> constexpr bool kStepKin = !S::WIDE && (MPCR_STEP_TABLE & 1) != 0;
+template <class S> constexpr bool kStepDof = !S::WIDE && (MPCR_STEP_TABLE & 2) != 0;
+template <class S> constexpr bool kStepRow = !S::WIDE && (MPCR_STEP_TABLE & 4) != 0;
+// The step table (step_table.h) behind the device model, and quad q (16
+// bytes: one dwordx4 load) of one of its records.  Single-arm kernels only.
+__device__ __forceinline__ const StepTable* step_table(const DevModel* m) {
+  return reinterpret_cast<const StepTable*>(m + 1);
+}
+template <class R>
+__device__ __forceinline__ float4 recq(const R& r, int q) {
+  return reinterpret_cast<const float4*>(&r)[q];
 }
 
 __device__ __forceinline__ float rdlane(float v, int l) {
@@ -2934,6 +2954,52 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
   // two waves per candidate -- before the first barrier, since the collision
   // wave's constraint rows need them
   auto cdof_phase = [&]() {
+    if constexpr (kStepDof<S>) {
+      // single-arm kernels: the dof's record of the step table (body, kind,
+      // tree, free axis | joint axis | joint anchor); no anchor term when
+      // every joint sits at its body's origin
+      if (lane < nv) {
+        const StepTable* st = step_table(m);
+        const float4 d0 = recq(st->dof[lane], 0);
+        const int bd = __float_as_int(d0.x), kind = __float_as_int(d0.y), tr = __float_as_int(d0.z),
+                  k = __float_as_int(d0.w);
+        float* c = s.cdof[lane];
+        if (kind == 2) {  // free translation
+          c[0] = c[1] = c[2] = 0.f;
+          c[3] = k == 0 ? 1.f : 0.f;
+          c[4] = k == 1 ? 1.f : 0.f;
+          c[5] = k == 2 ? 1.f : 0.f;
+        } else {
+          float ax[3], anchor[3] = {s.xpos[bd][0], s.xpos[bd][1], s.xpos[bd][2]};
+          if (kind == 3) {
+            ax[0] = s.xmat[bd][k]; ax[1] = s.xmat[bd][3 + k]; ax[2] = s.xmat[bd][6 + k];  // by index, no selects
+          } else {
+            const float4 d1 = recq(st->dof[lane], 1);
+            const float ja[3] = {d1.x, d1.y, d1.z};
+            float R[9];
+#pragma unroll
+            for (int i = 0; i < 9; i++) R[i] = s.xmat[bd][i];
+            mv(ax, R, ja);
+            if (!(st->flags & ST_ANCHOR0)) {
+              const float4 d2 = recq(st->dof[lane], 2);
+              const float jp[3] = {d2.x, d2.y, d2.z};
+              float w[3];
+              mv(w, R, jp);
+              anchor[0] += w[0]; anchor[1] += w[1]; anchor[2] += w[2];
+            }
+          }
+          if (kind == 1) {
+            c[0] = c[1] = c[2] = 0.f;
+            c[3] = ax[0]; c[4] = ax[1]; c[5] = ax[2];
+          } else {
+            float off[3] = {s.com[tr][0] - anchor[0], s.com[tr][1] - anchor[1], s.com[tr][2] - anchor[2]}, cr[3];
+            cross(cr, ax, off);
+            c[0] = ax[0]; c[1] = ax[1]; c[2] = ax[2];
+            c[3] = cr[0]; c[4] = cr[1]; c[5] = cr[2];
+          }
+        }
+      }
+    } else {
     if (lane < nv) {
       const int bd = m->dof_body[lane], kind = m->dof_kind[lane];
       const int tr = m->body_tree[bd];
@@ -2971,6 +3037,7 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
         }
       }
     }
+    }
   };
   for (int t = t_begin; t < t_end; t++) {
     // Launder the model pointer every step: otherwise the compiler hoists
@@ -3003,6 +3070,51 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
     {
       float q[4] = {1.f, 0.f, 0.f, 0.f}, p[3] = {0.f, 0.f, 0.f};
       int anc = -1;
+      if constexpr (kStepKin<S>) {
+        // single-arm kernels: the body's record of the step table -- kind,
+        // ancestor, the joint's qpos address and reference | local orientation
+        // | position | axis (a slide's already in the parent frame) and, only
+        // where some joint sits off its body's origin, anchor | the local
+        // rotation matrix
+        if (lane < nb) {
+          const StepTable* st = step_table(m);
+          const float4 b0 = recq(st->body[lane], 0), b1 = recq(st->body[lane], 1), b2 = recq(st->body[lane], 2);
+          const int kind = __float_as_int(b0.x), qa0 = __float_as_int(b0.z);
+          anc = __float_as_int(b0.y);
+          q[0] = b1.x; q[1] = b1.y; q[2] = b1.z; q[3] = b1.w;
+          p[0] = b2.x; p[1] = b2.y; p[2] = b2.z;
+          if (kind == BK_FREE) {
+            const int a = qa0;
+            p[0] = s.qpos[a]; p[1] = s.qpos[a + 1]; p[2] = s.qpos[a + 2];
+            q[0] = s.qpos[a + 3]; q[1] = s.qpos[a + 4]; q[2] = s.qpos[a + 5]; q[3] = s.qpos[a + 6];
+            float n = sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+            if (n < kMinVal) { q[0] = 1.f; q[1] = q[2] = q[3] = 0.f; }
+            else { q[0] /= n; q[1] /= n; q[2] /= n; q[3] /= n; }
+          } else if (kind == BK_HINGE || kind == BK_SLIDE) {
+            const float qa = s.qpos[qa0] - b0.w;
+            const float4 b3 = recq(st->body[lane], 3);
+            if (kind == BK_SLIDE) {
+              p[0] += b3.x * qa; p[1] += b3.y * qa; p[2] += b3.z * qa;
+            } else {
+              float sn, cs;
+              __sincosf(0.5f * qa, &sn, &cs);
+              float qj[4] = {cs, b3.x * sn, b3.y * sn, b3.z * sn};
+              if (!(st->flags & ST_ANCHOR0)) {
+                const float4 b5 = recq(st->body[lane], 5), r0 = recq(st->body[lane], 6), r1 = recq(st->body[lane], 7),
+                             r2 = recq(st->body[lane], 8);
+                const float R[9] = {r0.x, r0.y, r0.z, r1.x, r1.y, r1.z, r2.x, r2.y, r2.z};
+                float Rj[9], c[3] = {b5.x, b5.y, b5.z}, rc[3], d[3], w[3];
+                q2m(Rj, qj);
+                mv(rc, Rj, c);
+                d[0] = c[0] - rc[0]; d[1] = c[1] - rc[1]; d[2] = c[2] - rc[2];
+                mv(w, R, d);
+                p[0] += w[0]; p[1] += w[1]; p[2] += w[2];
+              }
+              qmul(q, q, qj);
+            }
+          }
+        }
+      } else {
       if (lane < nb) {
         const int kind = m->body_kind[lane];
         const int j = m->body_jnt[lane];
@@ -3041,6 +3153,7 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
           }
         }
       }
+      }
       for (int r = 0; r < m->jump_rounds; r++) {
         const int src = anc >= 0 ? anc : lane;
         float aq[4], ap[3];
@@ -3066,7 +3179,13 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
         s.xquat[lane][0] = q[0]; s.xquat[lane][1] = q[1]; s.xquat[lane][2] = q[2]; s.xquat[lane][3] = q[3];
 #pragma unroll
         for (int k = 0; k < 9; k++) s.xmat[lane][k] = R[k];
-        mv(w, R, m->body_ipos[lane]);
+        if constexpr (kStepKin<S>) {
+          const float4 b4 = recq(step_table(m)->body[lane], 4);
+          const float ip[3] = {b4.x, b4.y, b4.z};
+          mv(w, R, ip);
+        } else {
+          mv(w, R, m->body_ipos[lane]);
+        }
         s.xipos[lane][0] = p[0] + w[0]; s.xipos[lane][1] = p[1] + w[1]; s.xipos[lane][2] = p[2] + w[2];
       }
     }
@@ -3822,6 +3941,19 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
       const int ncon = s.ncon;
       const int neq = (m->disableflags & 64) ? 0 : (S::WIDE ? m->neqrow : m->neq);
       int nlim_l = 0, lsides = 0;
+      if constexpr (kStepRow<S>) {
+        // single-arm kernels: the joint's row record of the step table
+        // (margin, flags | range, qpos address)
+        if (lane < m->njnt && !(m->disableflags & 32)) {
+          const StepRow& rj = step_table(m)->row[ST_ROW_JNT + lane];
+          const float4 j2 = recq(rj, 2), j3 = recq(rj, 3);
+          if (__float_as_int(j2.z) & ST_LIMITED) {
+            const float q = s.qpos[__float_as_int(j3.z)];
+            if (q - j3.x < j2.x) { nlim_l++; lsides |= 1; }
+            if (j3.y - q < j2.x) { nlim_l++; lsides |= 2; }
+          }
+        }
+      } else
       if (lane < m->njnt && !(m->disableflags & 32) && m->jnt_limited[lane] &&
           (m->jnt_type[lane] == 2 || m->jnt_type[lane] == 3)) {
         const float q = s.qpos[m->jnt_qposadr[lane]];
@@ -4000,6 +4132,65 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
       if (rows_j) block_sync();
       else sync();
       // row parameters: vel, impedance, D, aref
+      if constexpr (kStepRow<S>) {
+        // single-arm kernels: the constraint source's record of the step
+        // table holds what depends on solref / solimp / timestep alone -- the
+        // clamped impedance bounds, 1 / width, 1 / mid, 1 / (1 - mid), the
+        // reference's stiffness K and damping B, margin and the diagonal
+        // (a pyramid's 1 + mu^2 folded in)
+        for (int r = lane + rl0; r < nefc; r += rls) {
+          const int src = s.efc_src[r], kind = src >> 24, id = (src >> 4) & 0xfffff, side = src & 15;
+          const StepTable* st = step_table(m);
+          float pos;
+          int ri;
+          if (kind == 1) {
+            const int j1 = m->eq_j1[id], j2 = m->eq_j2[id];
+            const float* c = m->eq_data[id];
+            const float q1 = s.qpos[m->jnt_qposadr[j1]] - m->jnt_qpos0[j1];
+            if (j2 >= 0) {
+              const float dif = s.qpos[m->jnt_qposadr[j2]] - m->jnt_qpos0[j2];
+              pos = q1 - (c[0] + dif * (c[1] + dif * (c[2] + dif * (c[3] + dif * c[4]))));
+            } else {
+              pos = q1 - c[0];
+            }
+            ri = ST_ROW_EQ + id;
+          } else if (kind == 2) {
+            ri = ST_ROW_JNT + id;
+            const float4 j3 = recq(st->row[ri], 3);
+            const float q = s.qpos[__float_as_int(j3.z)];
+            pos = side == 0 ? q - j3.x : j3.y - q;
+          } else {
+            ri = ST_ROW_PAIR + s.con_pair[id];
+            pos = s.con_dist[id];
+          }
+          const float4 a0 = recq(st->row[ri], 0), a1 = recq(st->row[ri], 1), a2 = recq(st->row[ri], 2);
+          const float vel = jdot(s, gx, r, s.qvel);
+          const float dpos = pos - a2.x;
+          const float x = fabsf(dpos * a0.z);
+          float imp;
+          if (x >= 1.f) {
+            imp = a0.y;
+          } else if (x <= 0.f) {
+            imp = a0.x;
+          } else {
+            const int fl = __float_as_int(a2.z);
+            const float mid = a0.w, power = a2.w;
+            float y;
+            if (fl & ST_POW1) y = x;
+            else if (fl & ST_POW2) y = x <= mid ? x * x * a1.x : 1.f - (1.f - x) * (1.f - x) * a1.y;  // default solimp
+            else if (x <= mid) y = powf(x, power) / powf(mid, power - 1.f);
+            else y = 1.f - powf(1.f - x, power) / powf(1.f - mid, power - 1.f);
+            imp = a0.x + y * (a0.y - a0.x);
+          }
+          const float R = fmaxf((1.f - imp) / imp * a2.y, kMinVal);
+          s.efc_D[r] = 1.f / R;
+          s.efc_aref[r] = -a1.w * vel - a1.z * imp * dpos;
+          if (args.dbg && b == 0 && t == H - 1 && r < DBG_MAXROW) {
+            float* o = args.dbg + DBG_ROW + 3 * r;
+            o[0] = s.efc_D[r]; o[1] = s.efc_aref[r]; o[2] = vel;
+          }
+        }
+      } else
       for (int r = lane + rl0; r < nefc; r += rls) {
         const int src = s.efc_src[r], kind = src >> 24, id = (src >> 4) & 0xfffff, side = src & 15;
         float pos, margin, diag;

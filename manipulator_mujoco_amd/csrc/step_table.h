@@ -1,0 +1,273 @@
+// step_table.h -- what the single-arm rollout kernels read of the model every
+// step, laid out once per engine: one contiguous 16-byte-aligned record per
+// lane and phase (kinematics by body, motion subspaces by dof, constraint-row
+// parameters by constraint source) with the dependent indices resolved and
+// the constants that depend on the model and the timestep alone already
+// evaluated (in double, rounded once to fp32).
+//
+// Plain host C++ (no HIP): build_step_table() runs at engine creation
+// (engine.hip) and in a stand-alone CPU test (tests/test_step_table.py).  The
+// table is uploaded directly behind the device model (DevModel) in the same
+// allocation; the narrow kernels reach it as (const StepTable*)(model + 1),
+// so neither DevModel nor the launch arguments change.  (A pointer field in
+// DevModel would say so in the types, but any change of sizeof(DevModel) or of
+// the launch arguments changes the dual-arm unit's device code: the model
+// pointer's launder scales by that size, the kernel metadata carries the
+// argument size.  engine.hip's mpcr_engine_create is the one place a device
+// model is allocated.)  engine.hip checks the table against the device model
+// it builds (step_table_matches) at every engine creation.
+//
+// Device indices as in engine.hip build_dev_model: moving bodies (not welded
+// to the world) in model order, pairs / joints / equalities by their model
+// index.  (The geoms have no records: a geom's rotation matrix evaluated in
+// double has exact zeros where the kernel's fp32 q2m leaves 6e-8, which moves
+// the ties of axis-aligned box contacts and with them the planner scene's
+// parity -- DESIGN.md, "Measured and not kept".)
+#pragma once
+#include <math.h>
+#include <stdint.h>
+#include <string.h>
+
+#include "../../include/mpcr_model.h"
+
+namespace mpcr {
+
+constexpr int ST_NB = 32, ST_NV = 32, ST_NP = 768, ST_NJ = 32, ST_NEQ = 8;  // = DX_* (mpcr_device.h)
+// rows of StepTable::row: pairs, then joints (limit rows), then equalities
+constexpr int ST_ROW_PAIR = 0, ST_ROW_JNT = ST_NP, ST_ROW_EQ = ST_NP + ST_NJ, ST_NROW = ST_NP + ST_NJ + ST_NEQ;
+// the kernel's constants (rollout.h kMinVal / kMinImp / kMaxImp)
+constexpr float ST_MINVAL = 1e-15f, ST_MINIMP = 0.0001f, ST_MAXIMP = 0.9999f;
+
+// StepTable::flags
+enum { ST_ANCHOR0 = 1 };  // every hinge / slide joint sits at its body's origin (jnt_pos = 0): no anchor terms
+// StepRow::flags
+enum {
+  ST_POW2 = 1,     // solimp power == 2 (the default): y = x^2 / mid | 1 - (1 - x)^2 / (1 - mid)
+  ST_POW1 = 2,     // power == 1: y = x
+  ST_LIMITED = 4,  // joint rows: a limited hinge / slide joint
+  ST_CONDIM1 = 8   // pair rows: frictionless contact (one row)
+};
+// body kinds (mpcr_device.h BK_*)
+enum { ST_BK_FREE = 1, ST_BK_HINGE = 2, ST_BK_SLIDE = 3, ST_BK_WELD = 4 };
+
+// kinematics, by moving body (quads of 4 floats; 144 B)
+struct alignas(16) StepBody {
+  int32_t kind, anc, qposadr;  // ST_BK_*; first moving ancestor (-1: none); the joint's qpos address (-1: weld)
+  float qpos0;                 // the joint's reference position
+  float bquat[4];              // pre-joint local (or, under a static parent, world) orientation
+  float bpos[3], pad0;         // and position
+  float axis[3], pad1;         // hinge: joint axis in the body frame; slide: R(bquat) axis, the direction in the parent frame
+  float ipos[3], pad2;         // centre of mass in the body frame
+  float jpos[3], pad3;         // hinge anchor in the body frame             } read only when some joint sits
+  float R[3][4];               // rows of the rotation matrix of bquat      } off its body's origin (no ST_ANCHOR0)
+};
+// motion subspaces, by dof (48 B)
+struct alignas(16) StepDof {
+  int32_t body, kind, tree, sub;  // kind: 0 hinge 1 slide 2 free translation 3 free rotation; sub: free axis 0..2
+  float axis[3], pad0;            // the joint's axis and anchor in the body frame
+  float jpos[3], pad1;
+};
+// constraint-row parameters, by constraint source (64 B)
+struct alignas(16) StepRow {
+  float dmin, dmax, iwidth, mid;  // clamped solimp d0 / dwidth, 1 / width
+  float imid, i1mid, K, B;        // 1 / mid, 1 / (1 - mid); aref = -B vel - K imp (pos - margin)
+  float margin, diag;             // pair: margin - gap, invweight sum x (1 + mu^2 unless condim 1)
+  int32_t flags;
+  float power;
+  float range[2];                 // joint rows: limits, qpos address, dof address (dofadr: not read by the
+  int32_t qposadr, dofadr;        // kernel; it fills the quad and is checked against the device model)
+};
+
+struct alignas(16) StepTable {
+  int32_t flags, nbody, pad[2];  // nbody: for the checks (tests, step_table_matches), not read by the kernel
+  StepBody body[ST_NB];
+  StepDof dof[ST_NV];
+  StepRow row[ST_NROW];
+};
+
+namespace step_detail {
+inline void qmul(double r[4], const double a[4], const double b[4]) {
+  const double t[4] = {a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3],
+                       a[0] * b[1] + a[1] * b[0] + a[2] * b[3] - a[3] * b[2],
+                       a[0] * b[2] - a[1] * b[3] + a[2] * b[0] + a[3] * b[1],
+                       a[0] * b[3] + a[1] * b[2] - a[2] * b[1] + a[3] * b[0]};
+  memcpy(r, t, sizeof(t));
+}
+inline void q2m(double m[9], const double q[4]) {
+  const double w = q[0], x = q[1], y = q[2], z = q[3];
+  m[0] = 1 - 2 * (y * y + z * z); m[1] = 2 * (x * y - w * z); m[2] = 2 * (x * z + w * y);
+  m[3] = 2 * (x * y + w * z); m[4] = 1 - 2 * (x * x + z * z); m[5] = 2 * (y * z - w * x);
+  m[6] = 2 * (x * z - w * y); m[7] = 2 * (y * z + w * x); m[8] = 1 - 2 * (x * x + y * y);
+}
+inline void rot(double r[3], const double q[4], const double v[3]) {
+  double m[9];
+  q2m(m, q);
+  for (int i = 0; i < 3; i++) r[i] = m[3 * i] * v[0] + m[3 * i + 1] * v[1] + m[3 * i + 2] * v[2];
+}
+inline double clampd(double x, double lo, double hi) { return x < lo ? lo : (x > hi ? hi : x); }
+
+// the parameters of one constraint source from its solref / solimp
+inline void row_params(StepRow& r, const double solref[2], const double solimp[5], double timestep, int disableflags) {
+  double dmin = clampd(solimp[0], (double)ST_MINIMP, (double)ST_MAXIMP);
+  double dmax = clampd(solimp[1], (double)ST_MINIMP, (double)ST_MAXIMP);
+  double width = solimp[2], mid = solimp[3];
+  const double power = solimp[4];
+  // a flat impedance (the kernel's early return 0.5 (dmin + dmax)): stored as
+  // dmin = dmax = that value with 1 / width = 0, so the general path returns it
+  const bool flat = (float)dmin == (float)dmax || (float)width <= ST_MINVAL;
+  double iwidth = 1.0 / width, imid = 1.0 / mid, i1mid = 1.0 / (1.0 - mid);
+  if (flat) {
+    dmin = dmax = 0.5 * ((double)(float)dmin + (double)(float)dmax);
+    iwidth = 0.0; mid = 0.5; imid = 2.0; i1mid = 2.0;
+  }
+  // the reference acceleration's stiffness and damping (d = the clamped dmax
+  // of the solimp as given, also for a flat impedance)
+  const double d = clampd(solimp[1], (double)ST_MINIMP, (double)ST_MAXIMP);
+  double tc = solref[0];
+  const double dr = solref[1];
+  double K, B;
+  if ((float)tc > 0.f) {
+    if (!(disableflags & MPCR_DSBL_REFSAFE) && tc < 2.0 * timestep) tc = 2.0 * timestep;
+    K = 1.0 / (d * d * tc * tc * dr * dr);
+    B = 2.0 / (d * tc);
+  } else {
+    K = -tc / (d * d);
+    B = -dr / d;
+  }
+  r.dmin = (float)dmin; r.dmax = (float)dmax; r.iwidth = (float)iwidth; r.mid = (float)mid;
+  r.imid = (float)imid; r.i1mid = (float)i1mid; r.K = (float)K; r.B = (float)B;
+  r.power = (float)power;
+  r.flags = flat ? ST_POW1 : ((float)power == 2.f ? ST_POW2 : ((float)power == 1.f ? ST_POW1 : 0));
+}
+}  // namespace step_detail
+
+// Fills t from the model.  Returns 0, or -1 when the model exceeds the
+// table's capacities (the engine has then already refused it).
+inline int build_step_table(const mpcr_model_t& m, StepTable& t) {
+  using namespace step_detail;
+  memset(&t, 0, sizeof(t));
+  if (m.nbody > MPCR_MAX_BODY || m.njnt > ST_NJ || m.nv > ST_NV || m.npair > ST_NP || m.neq > ST_NEQ)
+    return -1;
+  // moving bodies; world poses of the static ones
+  int dmap[MPCR_MAX_BODY], nb = 0;
+  double wpos[MPCR_MAX_BODY][3] = {}, wquat[MPCR_MAX_BODY][4] = {};
+  dmap[0] = -1;
+  wquat[0][0] = 1;
+  for (int b = 1; b < m.nbody; b++) dmap[b] = m.body_weldid[b] != 0 ? nb++ : -1;
+  if (nb > ST_NB) return -1;
+  for (int b = 1; b < m.nbody; b++) {
+    if (dmap[b] >= 0) continue;
+    const int p = m.body_parentid[b];
+    double r[3];
+    rot(r, wquat[p], m.body_pos[b]);
+    for (int k = 0; k < 3; k++) wpos[b][k] = wpos[p][k] + r[k];
+    qmul(wquat[b], wquat[p], m.body_quat[b]);
+    const double n = sqrt(wquat[b][0] * wquat[b][0] + wquat[b][1] * wquat[b][1] + wquat[b][2] * wquat[b][2] +
+                          wquat[b][3] * wquat[b][3]);
+    for (int k = 0; k < 4; k++) wquat[b][k] /= n;
+  }
+  // kinematic trees in order of first appearance
+  int roots[MPCR_MAX_BODY], nroot = 0, btree[ST_NB];
+  for (int b = 1; b < m.nbody; b++) {
+    if (dmap[b] < 0) continue;
+    int tr = -1;
+    for (int k = 0; k < nroot; k++)
+      if (roots[k] == m.body_rootid[b]) tr = k;
+    if (tr < 0) { roots[nroot] = m.body_rootid[b]; tr = nroot++; }
+    btree[dmap[b]] = tr;
+  }
+  t.nbody = nb;
+  bool anchor0 = true;
+  for (int b = 1; b < m.nbody; b++) {
+    const int i = dmap[b];
+    if (i < 0) continue;
+    StepBody& r = t.body[i];
+    const int p = m.body_parentid[b];
+    const int j = m.body_jntnum[b] ? m.body_jntadr[b] : -1;
+    r.kind = j < 0 ? ST_BK_WELD
+                   : (m.jnt_type[j] == MPCR_JNT_FREE ? ST_BK_FREE
+                                                     : (m.jnt_type[j] == MPCR_JNT_HINGE ? ST_BK_HINGE : ST_BK_SLIDE));
+    double bq[4], bp[3];
+    if (dmap[p] < 0) {  // static parent: its constant world pose folded in
+      double w[3];
+      rot(w, wquat[p], m.body_pos[b]);
+      for (int k = 0; k < 3; k++) bp[k] = wpos[p][k] + w[k];
+      qmul(bq, wquat[p], m.body_quat[b]);
+      r.anc = -1;
+    } else {
+      memcpy(bp, m.body_pos[b], sizeof(bp));
+      memcpy(bq, m.body_quat[b], sizeof(bq));
+      r.anc = dmap[p];
+    }
+    if (r.kind == ST_BK_FREE) r.anc = -1;
+    r.qposadr = j >= 0 ? m.jnt_qposadr[j] : -1;
+    r.qpos0 = j >= 0 ? (float)m.qpos0[m.jnt_qposadr[j]] : 0.f;
+    double R[9];
+    q2m(R, bq);
+    for (int k = 0; k < 4; k++) r.bquat[k] = (float)bq[k];
+    for (int k = 0; k < 3; k++) {
+      r.bpos[k] = (float)bp[k];
+      r.ipos[k] = (float)m.body_ipos[b][k];
+      for (int c = 0; c < 3; c++) r.R[k][c] = (float)R[3 * k + c];
+    }
+    if (r.kind == ST_BK_HINGE || r.kind == ST_BK_SLIDE) {
+      for (int k = 0; k < 3; k++) {
+        const double* a = m.jnt_axis[j];
+        r.axis[k] = r.kind == ST_BK_HINGE ? (float)a[k] : (float)(R[3 * k] * a[0] + R[3 * k + 1] * a[1] + R[3 * k + 2] * a[2]);
+        r.jpos[k] = (float)m.jnt_pos[j][k];
+        if (r.jpos[k] != 0.f) anchor0 = false;
+      }
+    }
+  }
+  t.flags = anchor0 ? ST_ANCHOR0 : 0;
+  // dofs
+  for (int i = 0; i < m.nv; i++) {
+    StepDof& r = t.dof[i];
+    const int j = m.dof_jntid[i], sub = i - m.jnt_dofadr[j];
+    r.body = dmap[m.dof_bodyid[i]];
+    r.kind = m.jnt_type[j] == MPCR_JNT_HINGE ? 0 : (m.jnt_type[j] == MPCR_JNT_SLIDE ? 1 : (sub < 3 ? 2 : 3));
+    r.tree = r.body >= 0 ? btree[r.body] : -1;
+    r.sub = sub < 3 ? sub : sub - 3;
+    for (int k = 0; k < 3; k++) { r.axis[k] = (float)m.jnt_axis[j][k]; r.jpos[k] = (float)m.jnt_pos[j][k]; }
+  }
+  // constraint sources
+  for (int p = 0; p < m.npair; p++) {
+    StepRow& r = t.row[ST_ROW_PAIR + p];
+    row_params(r, m.pair_solref[p], m.pair_solimp[p], m.timestep, m.disableflags);
+    const double mu = m.pair_friction[p];
+    const double invw = m.body_invweight0[m.geom_bodyid[m.pair_geom1[p]]][0] +
+                        m.body_invweight0[m.geom_bodyid[m.pair_geom2[p]]][0];
+    r.margin = (float)(m.pair_margin[p] - m.pair_gap[p]);
+    r.diag = (float)(m.pair_condim[p] == 1 ? invw : invw * (1.0 + mu * mu));
+    if (m.pair_condim[p] == 1) r.flags |= ST_CONDIM1;
+    r.qposadr = r.dofadr = -1;
+  }
+  for (int j = 0; j < m.njnt; j++) {
+    StepRow& r = t.row[ST_ROW_JNT + j];
+    row_params(r, m.jnt_solref[j], m.jnt_solimp[j], m.timestep, m.disableflags);
+    r.margin = (float)m.jnt_margin[j];
+    r.diag = (float)m.dof_invweight0[m.jnt_dofadr[j]];
+    if (m.jnt_limited[j] && (m.jnt_type[j] == MPCR_JNT_SLIDE || m.jnt_type[j] == MPCR_JNT_HINGE)) r.flags |= ST_LIMITED;
+    r.range[0] = (float)m.jnt_range[j][0];
+    r.range[1] = (float)m.jnt_range[j][1];
+    r.qposadr = m.jnt_qposadr[j];
+    r.dofadr = m.jnt_dofadr[j];
+  }
+  for (int e = 0; e < m.neq; e++) {
+    StepRow& r = t.row[ST_ROW_EQ + e];
+    row_params(r, m.eq_solref[e], m.eq_solimp[e], m.timestep, m.disableflags);
+    double diag = 0;
+    if (m.eq_type[e] == MPCR_EQ_JOINT) {
+      diag = m.dof_invweight0[m.jnt_dofadr[m.eq_obj1[e]]];
+      if (m.eq_obj2[e] >= 0) diag += m.dof_invweight0[m.jnt_dofadr[m.eq_obj2[e]]];
+    } else if (m.eq_type[e] == MPCR_EQ_CONNECT) {
+      diag = m.body_invweight0[m.eq_obj1[e]][0] + m.body_invweight0[m.eq_obj2[e]][0];
+    }
+    r.margin = 0.f;
+    r.diag = (float)diag;
+    r.qposadr = r.dofadr = -1;
+  }
+  return 0;
+}
+
+}  // namespace mpcr
