@@ -208,6 +208,39 @@ int mpcr_rollout_cost_multi(mpcr_engine* e, const float* input, int layout, int 
                             const float* params, float* cost4, float* theta, float* thetadot, uint64_t* best_keys,
                             int index_base, int* status, int flags, void* stream);
 
+/* A state block: what a plant holds, fp32, device memory:
+   qpos[DX_NQ] | qvel[DX_NV] | qacc_warmstart[DX_NV] | qacc[DX_NV] | eef[8]
+   (eef: tcp site position | hande body quaternion wxyz | unused).  Returns
+   the floats per block and writes the offset of each part (NULL skips one);
+   the model's nq / nv entries of a part are used, the rest is padding.  Host
+   only, no device. */
+int mpcr_state_layout(int* qpos, int* qvel, int* qacc_warmstart, int* qacc, int* eef);
+
+/* mpcr_rollout_cost_multi from a given full state, and / or returning the
+   final states (a backward-compatible addition like the *_multi calls).
+   start (nullable): problem p's candidates begin from qpos | qvel |
+   qacc_warmstart of the block at start + p start_stride, where they
+   otherwise begin from the model's template state with a zero warm start;
+   start_stride is in floats, 0 (every problem shares one block) or at least
+   the block size.  The qacc and eef parts of a start block are ignored, and
+   everything else is a rollout's as ever: qpos[ctrl_qposadr[j]] = init_pos[j]
+   from the parameter block applies afterwards, the hull climbs start afresh
+   and the slot history at step 0 -- so a block that holds the template state
+   gives bitwise the results of mpcr_rollout_cost_multi.  The reference's
+   compute_cem starts every rollout from the template (mjx_planner.py:105-107);
+   this departs from it on request only.  The block is read when the kernel
+   runs (graph-capturable; a replay sees new contents) and never written.
+   final_state (nullable): nprob n_per blocks, candidate i's receiving qpos |
+   qvel | qacc_warmstart after the last step, that step's qacc and its
+   pre-integration eef pose: what a plant holds after the same H steps from
+   the same state.  Padding entries are left as they were.
+   start == NULL && final_state == NULL runs exactly what
+   mpcr_rollout_cost_multi runs.  Device pointers only. */
+int mpcr_rollout_cost_state(mpcr_engine* e, const float* input, int layout, int nprob, int n_per,
+                            const float* params, const float* start, int start_stride, float* final_state,
+                            float* cost4, float* theta, float* thetadot, uint64_t* best_keys, int index_base,
+                            int* status, int flags, void* stream);
+
 /* Closed-loop plant: one environment of the model, stepped by the rollout
    kernel (fp32 state resident on the device).  Created at the template
    state (qpos_init, qvel_init, zero warm start). */
@@ -226,6 +259,10 @@ int mpcr_plant_get_state(mpcr_plant* p, double* qpos, double* qvel, double* qacc
    current velocities).  commit = 0: mj_forward, the state is not advanced.
    Blocks until done. */
 int mpcr_plant_step(mpcr_plant* p, const double* qvel_ctrl, int commit, void* stream);
+/* Asynchronous device-to-device copy of the plant's state block
+   (mpcr_state_layout) to d_dst on stream: a planner's start state
+   (mpcr_rollout_cost_state) without a host round trip. */
+int mpcr_plant_copy_state(mpcr_plant* p, float* d_dst, void* stream);
 
 /* argmin over cost[i*stride] with NaN-first / first-index semantics
    (jnp.argmin).  key_out (device, nullable) receives the packed key. */

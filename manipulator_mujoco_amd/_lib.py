@@ -35,6 +35,9 @@ EXPORTS = (
 _MULTI = ("mpcr_rollout_cost_multi", "mpcr_topk_multi", "mpcr_cem_set_problems", "mpcr_cem_factor_multi",
           "mpcr_cem_sample_project_multi", "mpcr_cem_update_multi")
 EXPORTS += _MULTI
+# planning from a state, likewise: absent from an older build
+_STATE = ("mpcr_state_layout", "mpcr_rollout_cost_state", "mpcr_plant_copy_state")
+EXPORTS += _STATE
 _VOID = ("mpcr_last_error", "mpcr_model_free", "mpcr_engine_free", "mpcr_best_key_decode", "mpcr_cem_free",
          "mpcr_plant_free", "mpcr_comm_free")
 
@@ -121,8 +124,17 @@ def load():
     for name, at in multi.items():
         if have_multi:
             getattr(lib, name).argtypes = at
+    state = {
+        "mpcr_state_layout": [P(i), P(i), P(i), P(i), P(i)],
+        "mpcr_rollout_cost_state": [vp, vp, i, i, i, vp, vp, i, vp, vp, vp, vp, vp, i, vp, i, vp],
+        "mpcr_plant_copy_state": [vp, vp, vp],
+    }
+    have_state = hasattr(lib, _STATE[0])
+    for name, at in state.items():
+        if have_state:
+            getattr(lib, name).argtypes = at
     for name in EXPORTS + ("mpcr_rollout_trace", "mpcr_plant_step_debug", "mpcr_plant_dbg_size"):
-        if name in _MULTI and not have_multi:
+        if (name in _MULTI and not have_multi) or (name in _STATE and not have_state):
             continue
         if name not in _VOID:
             getattr(lib, name).restype = i

@@ -1281,6 +1281,10 @@ struct Launch {
   float* dbg = nullptr;
   bool reset_key = false;
   int nprob = 1, prob_n = 0;  // nprob > 1: problems of prob_n candidates each (0: one problem)
+  // a batch's start block per problem (stride in floats) and final block per candidate (RolloutArgs)
+  const float* start = nullptr;
+  float* final_state = nullptr;
+  int start_stride = 0;
 };
 
 static int launch_rollout(mpcr_engine* e, const Launch& l, hipStream_t st) {
@@ -1318,7 +1322,15 @@ static int launch_rollout(mpcr_engine* e, const Launch& l, hipStream_t st) {
   a.seg_min_n = e->seg_min_n;
   a.prob_n = l.prob_n;
   a.prob_off = 0;
-  std::memcpy(a.par, l.par, sizeof(a.par));
+  // a call with a device parameter block carries its StateArgs in par's
+  // bytes (rollout.h; null pointers when it has no state blocks) and never
+  // parameter values, so has_state() cannot read those as pointers
+  if (l.dpar) {
+    set_state_args(a, StateArgs{l.start, l.final_state, l.start_stride});
+  } else {
+    if (l.start || l.final_state) return fail(MPCR_EINVAL, "state blocks need a device parameter block");
+    std::memcpy(a.par, l.par, sizeof(a.par));
+  }
   if (l.key && l.reset_key) hipLaunchKernelGGL(fill_u64, dim3(l.nprob), dim3(1), 0, st, l.key, ~0ull);
   rollout_launch(e->wide, a, (const DevModel*)e->d_model, l.n, st, e->seg_groups, e->seg_stream,
                  e->seg_event);
@@ -1400,12 +1412,14 @@ static int check_multi(int nprob, int n_per, int max_n) {
   return MPCR_OK;
 }
 
-// mpcr_rollout_cost_dp (nprob = 1) and mpcr_rollout_cost_multi.  One problem
+// mpcr_rollout_cost_dp (nprob = 1), mpcr_rollout_cost_multi and
+// mpcr_rollout_cost_state (start / final_state, else null).  One problem
 // runs the one-problem kernels through either entry (prob_n = 0): the MULTI
 // instantiations' problem lookup is paid only where there is one to make.
 static int rollout_dp(mpcr_engine* e, const float* input, int layout, int nprob, int n_per, const float* params,
                       float* cost4, float* theta, float* thetadot, uint64_t* best_keys, int index_base, int* status,
-                      int flags, void* stream) {
+                      int flags, void* stream, const float* start = nullptr, int start_stride = 0,
+                      float* final_state = nullptr) {
   if (layout != MPCR_LAYOUT_XI && layout != MPCR_LAYOUT_THETADOT) return fail(MPCR_EINVAL, "bad layout %d", layout);
   if (n_per == 0) return MPCR_OK;  // an empty batch: the buffers may be null
   if (!input || !params || !cost4) return fail(MPCR_EINVAL, "null argument");
@@ -1417,6 +1431,7 @@ static int rollout_dp(mpcr_engine* e, const float* input, int layout, int nprob,
   l.in = input; l.cost4 = cost4; l.theta = theta; l.thetadot = thetadot;
   l.key = reinterpret_cast<unsigned long long*>(best_keys); l.status = status;
   l.reset_key = (flags & MPCR_F_RESET_BEST) != 0;
+  l.start = start; l.start_stride = start_stride; l.final_state = final_state;
   int rc = launch_rollout(e, l, st);
   if (rc) return rc;
   if (flags & MPCR_F_SYNC) HIPCHK(hipStreamSynchronize(st));
@@ -1440,6 +1455,29 @@ extern "C" int mpcr_rollout_cost_multi(mpcr_engine* e, const float* input, int l
   if (int rc = check_multi(nprob, n_per, e->max_n)) return rc;
   return rollout_dp(e, input, layout, nprob, n_per, params, cost4, theta, thetadot, best_keys, index_base, status,
                     flags, stream);
+}
+
+extern "C" int mpcr_state_layout(int* qpos, int* qvel, int* qacc_warmstart, int* qacc, int* eef) {
+  if (qpos) *qpos = ST_QPOS;
+  if (qvel) *qvel = ST_QVEL;
+  if (qacc_warmstart) *qacc_warmstart = ST_QWS;
+  if (qacc) *qacc = ST_QACC;
+  if (eef) *eef = ST_EEF;
+  return ST_N;
+}
+
+extern "C" int mpcr_rollout_cost_state(mpcr_engine* e, const float* input, int layout, int nprob, int n_per,
+                                       const float* params, const float* start, int start_stride, float* final_state,
+                                       float* cost4, float* theta, float* thetadot, uint64_t* best_keys,
+                                       int index_base, int* status, int flags, void* stream) {
+  if (!e) return fail(MPCR_EINVAL, "null argument");
+  if (!(flags & MPCR_F_DEVICE_PTRS)) return fail(MPCR_EINVAL, "mpcr_rollout_cost_state takes device pointers");
+  if (int rc = check_multi(nprob, n_per, e->max_n)) return rc;
+  if (start && start_stride != 0 && start_stride < ST_N)
+    return fail(MPCR_EINVAL, "start_stride=%d: 0 (one block for every problem) or at least the block's %d floats",
+                start_stride, (int)ST_N);
+  return rollout_dp(e, input, layout, nprob, n_per, params, cost4, theta, thetadot, best_keys, index_base, status,
+                    flags, stream, start, start ? start_stride : 0, final_state);
 }
 
 // ---------------------------------------------------------------------------
@@ -1519,6 +1557,22 @@ extern "C" int mpcr_plant_get_state(mpcr_plant* p, double* qpos, double* qvel, d
     for (int i = 0; i < h.nv; i++) qacc[i] = p->h_state[ST_QACC + i];
   if (eef)
     for (int i = 0; i < 7; i++) eef[i] = p->h_state[ST_EEF + i];
+  return MPCR_OK;
+}
+
+// the plant's block (mpcr_state_layout) to device memory, in stream order: a
+// planner's start state (mpcr_rollout_cost_state) with no host round trip
+extern "C" int mpcr_plant_copy_state(mpcr_plant* p, float* d_dst, void* stream) {
+  if (!p || !d_dst) return fail(MPCR_EINVAL, "null argument");
+  HIPCHK(hipSetDevice(p->e->device));
+  // the copy runs on the plant's device: the destination must live there
+  hipPointerAttribute_t at;
+  if (hipPointerGetAttributes(&at, d_dst) != hipSuccess || at.type != hipMemoryTypeDevice ||
+      at.device != p->e->device) {
+    (void)hipGetLastError();
+    return fail(MPCR_EINVAL, "d_dst must be device memory on the plant's device %d", p->e->device);
+  }
+  HIPCHK(hipMemcpyAsync(d_dst, p->d_state, sizeof(float) * ST_N, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return MPCR_OK;
 }
 

@@ -87,7 +87,10 @@ struct RolloutArgs {
   // pose of the last step always go to state when plant != 0
   float* state;
   int layout, n, H, nbasis, index_base, plant;
-  float par[PAR_N];  // q0[8] | w[4] | ptgt[4] | qtgt[4] (any norm)
+  // q0[8] | w[4] | ptgt[4] | qtgt[4] (any norm), for calls without dpar.  A
+  // call with dpar does not use it, and carries a StateArgs in its first
+  // bytes instead (below; launch_rollout writes one or the other)
+  float par[PAR_N];
   // several independent problems in one call (mpcr_rollout_cost_multi):
   // problem p owns candidates [p prob_n, (p + 1) prob_n) of the call, reads
   // its parameter block from dpar + p PAR_N and reduces into best_key[p] with
@@ -97,6 +100,38 @@ struct RolloutArgs {
   // instantiations of rollout_kernel, which the launchers pick for prob_n > 0.
   int prob_n, prob_off;
 };
+// A batch's start and final states (mpcr_rollout_cost_state, which always
+// passes dpar), ST_* blocks like the plant's.  Kept in the bytes of
+// RolloutArgs::par, which such a call does not use, and copied out with
+// state_args(): the argument block keeps its layout, and the kernels that do
+// not read it compile to the code they had.  start (nullable): the candidates
+// of problem p begin from qpos | qvel | qacc_warmstart of the block at start +
+// p start_stride (stride 0: one block for every problem) where they
+// otherwise take the template's and a zero warm start; read-only, the
+// init_pos override, fresh hull-climb hints and the slot history as ever.
+// Per problem, so candidate groups leave it alone (group_args).  final_state
+// (nullable): candidate b's block at final_state + b ST_N receives what a
+// plant holds after the same H steps.  Neither is plant mode: plant stays 0
+// and segments stay eligible.  Read by the STATE instantiations of
+// rollout_kernel, which the launchers pick when has_state().
+struct StateArgs {
+  const float* start;
+  float* final_state;
+  int start_stride;
+};
+static_assert(sizeof(StateArgs) <= sizeof(float) * PAR_N, "StateArgs inside par");
+__host__ __device__ inline StateArgs state_args(const RolloutArgs& a) {
+  StateArgs s;
+  __builtin_memcpy(&s, a.par, sizeof(s));
+  return s;
+}
+inline void set_state_args(RolloutArgs& a, const StateArgs& s) { __builtin_memcpy(a.par, &s, sizeof(s)); }
+// whether a launch starts from, or returns, state blocks
+inline bool has_state(const RolloutArgs& a) {
+  if (!a.dpar) return false;
+  const StateArgs s = state_args(a);
+  return s.start || s.final_state;
+}
 
 // Per-block LDS image, sized by the kernel variant: NVW = dense-solve width
 // (16 or 32 dofs), NBW = moving bodies, NGW = collision geoms.  Row stride

@@ -2693,10 +2693,20 @@ __device__ __forceinline__ mfx16 mfma_rows32(const S& s, const float* gx, int ne
 // instantiation, so the one-problem kernels compile from the source they had
 // (the extra scalar values moved the register allocation of the whole
 // kernel: C3 +0.5 % when the one kernel served both).
-template <int NVW, int NBW, int NGW, bool WIDE, int WPC = 1, bool MULTI = false>
+// STATE: a batch that starts from state blocks and / or returns its final
+// states (RolloutArgs::st, mpcr_rollout_cost_state).  Its own instantiation
+// for the same reason, on top of the MULTI one (which serves one problem too,
+// prob_n = 0): with the eight kernels reading the pointers themselves, at the
+// same resource usage, C3 measured +0.85 % per step (kernel time 1.528 ->
+// 1.542 ms).  In the other instantiations the STATE terms below fold away at
+// compile time.  Never the plant (plant = 0).
+template <int NVW, int NBW, int NGW, bool WIDE, int WPC = 1, bool MULTI = false, bool STATE = false>
 __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrowWavesPerSimd)
     rollout_kernel(RolloutArgs args, const DevModel* __restrict__ mptr) {
   static_assert(WPC == 1 || WPC == 2, "waves per candidate");
+  static_assert(MULTI || !STATE, "the STATE instantiations look the problem's start block up");
+  StateArgs sa = {nullptr, nullptr, 0};
+  if constexpr (STATE) sa = state_args(args);
   using S = typename std::conditional<WIDE, typename std::conditional<WPC == 2, SmemW2, SmemW>::type,
                                       typename std::conditional<WPC == 2, SmemN2, SmemN>::type>::type;
   const int wv = WPC == 2 ? (int)(threadIdx.x >> 6) : 0;
@@ -2840,14 +2850,19 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
   };
 
   // ---- rollout init: template state, qpos[:nctrl] = init_pos ----------------
-  //      (plant mode: the caller's state, no init_pos override)
+  //      (plant mode: the caller's state, no init_pos override; a batch's start
+  //      state, StateArgs::start: qpos | qvel | qacc_warmstart of the problem's
+  //      block in the template's place, everything else as from the template)
   const bool from_state = (args.plant & 1) != 0;
   if (run_main) {  // (WPC = 2: wave 0 sets the image up, wave 1 waits at the barrier below)
+  const float* st_in = nullptr;  // STATE: the problem's start block (null: the template)
   if constexpr (MULTI) {
     // the candidate's problem (mpcr_rollout_cost_multi): wave-uniform, scalar
     const int pr = args.prob_n ? (args.prob_off + b) / args.prob_n : 0;
     const float* dp = args.dpar + (size_t)pr * PAR_N;
     if (lane < PAR_N) s.par[lane] = dp[lane];
+    if constexpr (STATE)
+      if (sa.start) st_in = sa.start + (size_t)pr * sa.start_stride;
   } else {
     if (lane < PAR_N) s.par[lane] = args.dpar ? args.dpar[lane] : args.par[lane];
   }
@@ -2869,12 +2884,15 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
       s.qacc[lane] = 0.f;
     }
   } else {
+  // the block to start from, if any: the plant's own, or (STATE) the problem's
+  const bool from_blk = STATE ? st_in != nullptr : from_state;
+  const float* const blk = STATE ? st_in : args.state;
   for (int i = lane; i < S::NQW; i += WAVE)
-    s.qpos[i] = i < m->nq ? (from_state ? args.state[ST_QPOS + i] : m->qpos_init[i]) : 0.f;
+    s.qpos[i] = i < m->nq ? (from_blk ? blk[ST_QPOS + i] : m->qpos_init[i]) : 0.f;
   if (lane < NVW) {
     const bool v = lane < nv;
-    s.qvel[lane] = v ? (from_state ? args.state[ST_QVEL + lane] : m->qvel_init[lane]) : 0.f;
-    s.qws[lane] = v && from_state ? args.state[ST_QWS + lane] : 0.f;
+    s.qvel[lane] = v ? (from_blk ? blk[ST_QVEL + lane] : m->qvel_init[lane]) : 0.f;
+    s.qws[lane] = v && from_blk ? blk[ST_QWS + lane] : 0.f;
     s.qacc[lane] = 0.f;
   }
   }
@@ -3287,8 +3305,8 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
         float* e = args.trace_eef + ((size_t)b * H + t) * 7;
         e[0] = ep[0]; e[1] = ep[1]; e[2] = ep[2]; e[3] = eq[0]; e[4] = eq[1]; e[5] = eq[2]; e[6] = eq[3];
       }
-      if (args.plant && t == H - 1) {
-        float* e = args.state + ST_EEF;
+      if ((STATE ? sa.final_state != nullptr : args.plant != 0) && t == H - 1) {  // the last step's pre-integration pose
+        float* e = (STATE ? sa.final_state + (size_t)b * ST_N : args.state) + ST_EEF;
         e[0] = ep[0]; e[1] = ep[1]; e[2] = ep[2]; e[3] = eq[0]; e[4] = eq[1]; e[5] = eq[2]; e[6] = eq[3];
       }
     }
@@ -4721,13 +4739,18 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
 
   STAMP(10);
   PROF_FLUSH
-  if (args.plant && run_main) {  // single-environment plant: qacc of the last step, state back
-    if (lane < nv) args.state[ST_QACC + lane] = s.qacc[lane];
-    if (args.plant & 2) {
-      if (lane < m->nq) args.state[ST_QPOS + lane] = s.qpos[lane];
+  // the state after the last step, with that step's qacc: the single
+  // environment's block (plant; advanced only when plant & 2) or candidate b's
+  // block of a batch's final states (STATE; written by the segment that ends at H)
+  const bool wr_state = STATE ? sa.final_state != nullptr && !suspend : args.plant != 0;
+  float* const sout = STATE ? sa.final_state + (size_t)b * ST_N : args.state;
+  if (wr_state && run_main) {
+    if (lane < nv) sout[ST_QACC + lane] = s.qacc[lane];
+    if (STATE || (args.plant & 2)) {
+      if (lane < m->nq) sout[ST_QPOS + lane] = s.qpos[lane];
       if (lane < nv) {
-        args.state[ST_QVEL + lane] = s.qvel[lane];
-        args.state[ST_QWS + lane] = s.qws[lane];
+        sout[ST_QVEL + lane] = s.qvel[lane];
+        sout[ST_QWS + lane] = s.qws[lane];
       }
     }
   }

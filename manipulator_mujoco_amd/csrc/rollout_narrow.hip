@@ -72,6 +72,13 @@ static RolloutArgs group_args(const RolloutArgs& a, int off, int n) {
   g.tdscratch = a.tdscratch + o * th_row;
   g.slot_prev = a.slot_prev + o * (a.nslot > 0 ? a.nslot : 1);
   g.seg_state = a.seg_state + o * SEG_STRIDE;
+  // final states are per candidate; the start states are per problem, which
+  // prob_off locates (one problem: the one block), so start stays put
+  if (has_state(a)) {
+    StateArgs sa = state_args(a);
+    if (sa.final_state) sa.final_state += o * ST_N;
+    set_state_args(g, sa);
+  }
   return g;
 }
 
@@ -130,14 +137,21 @@ void rollout_launch(bool wide, const RolloutArgs& a0, const DevModel* dm, unsign
     }
   } else {
     const bool multi = a.prob_n > 0;  // several problems: the MULTI instantiations
-    if ((int)grid <= wpc2_max_n() && multi)
+    // (the STATE instantiations last: the code object lays the kernels out
+    // in the order this chain names them, and the others keep their places)
+    const bool state = has_state(a);  // state blocks: the STATE instantiations (one problem or several)
+    if (!state && (int)grid <= wpc2_max_n() && multi)
       hipLaunchKernelGGL((rollout_kernel<16, 16, 24, false, 2, true>), dim3(grid), dim3(2 * WAVE), 0, st, a, dm);
-    else if ((int)grid <= wpc2_max_n())
+    else if (!state && (int)grid <= wpc2_max_n())
       hipLaunchKernelGGL((rollout_kernel<16, 16, 24, false, 2>), dim3(grid), dim3(2 * WAVE), 0, st, a, dm);
-    else if (multi)
+    else if (!state && multi)
       hipLaunchKernelGGL((rollout_kernel<16, 16, 24, false, 1, true>), dim3(grid), dim3(WAVE), 0, st, a, dm);
-    else
+    else if (!state)
       hipLaunchKernelGGL((rollout_kernel<16, 16, 24, false>), dim3(grid), dim3(WAVE), 0, st, a, dm);
+    else if ((int)grid <= wpc2_max_n())
+      hipLaunchKernelGGL((rollout_kernel<16, 16, 24, false, 2, true, true>), dim3(grid), dim3(2 * WAVE), 0, st, a, dm);
+    else
+      hipLaunchKernelGGL((rollout_kernel<16, 16, 24, false, 1, true, true>), dim3(grid), dim3(WAVE), 0, st, a, dm);
   }
 }
 

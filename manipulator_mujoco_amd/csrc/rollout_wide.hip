@@ -11,14 +11,19 @@ namespace mpcr {
 // the dual-arm kernels' launches (rollout_launch's wide branch calls these)
 void rollout_wide_launch(int wpc, unsigned grid, hipStream_t st, const RolloutArgs& a, const DevModel* dm) {
   const bool multi = a.prob_n > 0;  // several problems: the MULTI instantiations
-  if (wpc == 2 && multi)
+  const bool state = has_state(a);  // state blocks: the STATE instantiations (one problem or several), named last
+  if (!state && wpc == 2 && multi)
     hipLaunchKernelGGL((rollout_kernel<32, 32, 72, true, 2, true>), dim3(grid), dim3(2 * WAVE), 0, st, a, dm);
-  else if (wpc == 2)
+  else if (!state && wpc == 2)
     hipLaunchKernelGGL((rollout_kernel<32, 32, 72, true, 2>), dim3(grid), dim3(2 * WAVE), 0, st, a, dm);
-  else if (multi)
+  else if (!state && multi)
     hipLaunchKernelGGL((rollout_kernel<32, 32, 72, true, 1, true>), dim3(grid), dim3(WAVE), 0, st, a, dm);
-  else
+  else if (!state)
     hipLaunchKernelGGL((rollout_kernel<32, 32, 72, true>), dim3(grid), dim3(WAVE), 0, st, a, dm);
+  else if (wpc == 2)
+    hipLaunchKernelGGL((rollout_kernel<32, 32, 72, true, 2, true, true>), dim3(grid), dim3(2 * WAVE), 0, st, a, dm);
+  else
+    hipLaunchKernelGGL((rollout_kernel<32, 32, 72, true, 1, true, true>), dim3(grid), dim3(WAVE), 0, st, a, dm);
 }
 hipError_t rollout_wide_occupancy(int* info) {
   const void* k = reinterpret_cast<const void*>(&rollout_kernel<32, 32, 72, true>);

@@ -58,6 +58,38 @@ class Model:
         self.handle = None
 
 
+def state_layout():
+    """``mpcr_state_layout``: the offset of each part of a state block (qpos,
+    qvel, qacc_warmstart, qacc, eef) and the block's ``size``, in floats.
+    Needs the library, no GPU."""
+    o = [ctypes.c_int() for _ in range(5)]
+    size = _lib.load().mpcr_state_layout(*(ctypes.byref(x) for x in o))
+    return dict(zip(("qpos", "qvel", "qacc_warmstart", "qacc", "eef"), (x.value for x in o)), size=size)
+
+
+def pack_state(compiled_model, qpos=None, qvel=None, qacc_warmstart=None):
+    """``Engine.pack_state`` for a compiled model (no GPU needed)."""
+    m, lay = compiled_model, state_layout()
+    blk = np.zeros(lay["size"], dtype=np.float32)
+    for name, x, n, dflt in (("qpos", qpos, int(m.nq), m.qpos_init), ("qvel", qvel, int(m.nv), m.qvel_init),
+                             ("qacc_warmstart", qacc_warmstart, int(m.nv), np.zeros(int(m.nv)))):
+        a = np.asarray(dflt if x is None else x, dtype=np.float64).reshape(-1)
+        if a.size < n:
+            raise ValueError(f"{name} needs {n} entries, got {a.size}")
+        blk[lay[name]:lay[name] + n] = a[:n]
+    return blk
+
+
+def unpack_state(compiled_model, block):
+    """The parts of state blocks (..., size), host array or tensor moved to the
+    host: dict of qpos (..., nq), qvel / qacc_warmstart / qacc (..., nv), eef (..., 7)."""
+    lay = state_layout()
+    b = np.asarray(block.cpu() if hasattr(block, "cpu") else block)
+    nq, nv = int(compiled_model.nq), int(compiled_model.nv)
+    return {k: b[..., lay[k]:lay[k] + n] for k, n in (("qpos", nq), ("qvel", nv), ("qacc_warmstart", nv),
+                                                      ("qacc", nv), ("eef", 7))}
+
+
 class Engine:
     def __init__(self, compiled_model, num_steps: int, max_n: int, pdot: np.ndarray, device: int = 0):
         lib = _lib.load()
@@ -157,10 +189,23 @@ class Engine:
         p[16:20] = np.asarray(qtgt, dtype=np.float32).reshape(-1)[:4]
         return p
 
+    @staticmethod
+    def state_layout():
+        """``mpcr_state_layout``: the offsets of a state block's parts and its
+        size in floats (no GPU needed)."""
+        return state_layout()
+
+    def pack_state(self, qpos=None, qvel=None, qacc_warmstart=None):
+        """A float32 state block (host) holding qpos (nq), qvel (nv) and
+        qacc_warmstart (nv); a part left out is the model's template state's
+        (qpos_init, qvel_init, a zero warm start), the rest of the block 0."""
+        return pack_state(self.model.compiled, qpos, qvel, qacc_warmstart)
+
     def _rollout_dp(self, nprob, inp, layout, params, cost4, theta, thetadot, best_keys, index_base, status,
-                    reset_best, stream):
+                    reset_best, stream, state=None):
         """nprob None: ``rollout_cost_dp`` (its own C entry, which takes an
-        empty batch); else ``rollout_cost_multi``."""
+        empty batch); else ``rollout_cost_multi`` or, with state = (start,
+        final_state), ``rollout_cost_state``."""
         import torch
         for name, t in (("input", inp), ("params", params), ("cost4", cost4)):
             if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
@@ -176,9 +221,25 @@ class Engine:
         if params.numel() < 20 * (nprob or 1):
             raise ValueError("params needs 20 floats per problem")
         ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        extra = ()
+        if state is not None:
+            start, final_state = state
+            blk = self.state_layout()["size"]
+            for name, t in (("start", start), ("final_state", final_state)):
+                if t is not None and (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32
+                                      or not t.is_contiguous() or t.device != inp.device):
+                    raise ValueError(f"{name} must be a contiguous float32 CUDA tensor on the input's device")
+            stride = 0
+            if start is not None:
+                if start.numel() not in (blk, nprob * blk) or start.shape[-1] != blk:
+                    raise ValueError(f"start must hold one block of {blk} floats, or one per problem")
+                stride = blk if nprob > 1 and start.numel() == nprob * blk else 0
+            if final_state is not None and (final_state.numel() != n * blk or final_state.shape[-1] != blk):
+                raise ValueError(f"final_state must be ({n}, {blk})")
+            fn, extra = lib.mpcr_rollout_cost_state, (ptr(start), stride, ptr(final_state))
         st = stream if stream is not None else torch.cuda.current_stream(inp.device).cuda_stream
         flags = MPCR_F_DEVICE_PTRS | (MPCR_F_RESET_BEST if reset_best else 0)
-        check(fn(self.handle, ptr(inp), layout, *shape, ptr(params), ptr(cost4), ptr(theta), ptr(thetadot),
+        check(fn(self.handle, ptr(inp), layout, *shape, ptr(params), *extra, ptr(cost4), ptr(theta), ptr(thetadot),
                  ptr(best_keys), int(index_base), ptr(status), flags, ctypes.c_void_p(st)))
         return cost4
 
@@ -200,6 +261,22 @@ class Engine:
         kernel ``rollout_cost_dp`` runs.  Graph-capturable."""
         return self._rollout_dp(int(nprob), inp, layout, params, cost4, theta, thetadot, best_keys, index_base,
                                 status, reset_best, stream)
+
+    def rollout_cost_state(self, inp, layout: int, params, nprob: int, cost4, start=None, final_state=None,
+                           theta=None, thetadot=None, best_keys=None, index_base: int = 0, status=None,
+                           reset_best: bool = True, stream=None):
+        """``rollout_cost_multi`` from a given full state and / or returning
+        the final states (``mpcr_rollout_cost_state``).  ``start``: a device
+        tensor of one state block (``pack_state``, ``Plant.copy_state``) shared
+        by every problem, or (nprob, block) with one per problem -- its qpos,
+        qvel and qacc_warmstart replace the template state, the parameter
+        block's init_pos still overrides the arm joints.  ``final_state``: a
+        device tensor (nprob * n_per, block) that receives, per candidate,
+        what a plant holds after the same steps.  Both None:
+        ``rollout_cost_multi``.  Graph-capturable; a replay reads ``start``
+        afresh."""
+        return self._rollout_dp(int(nprob), inp, layout, params, cost4, theta, thetadot, best_keys, index_base,
+                                status, reset_best, stream, state=(start, final_state))
 
     def trace(self, inp, layout: int, q0, w, ptgt, qtgt):
         """Debug/parity run (host arrays): cost4, theta, per-step eef pose, masked slot distances."""
@@ -236,6 +313,7 @@ class Plant:
         h = ctypes.c_void_p()
         check(lib.mpcr_plant_create(self.model.handle, int(device), ctypes.byref(h)))
         self.handle = h
+        self.device = int(device)
         self.qpos = np.zeros(self.nq)
         self.qvel = np.zeros(self.nv)
         self.qacc = np.zeros(self.nv)
@@ -264,6 +342,20 @@ class Plant:
                                                None if qv is None else qv.ctypes.data_as(dp),
                                                None if qw is None else qw.ctypes.data_as(dp)))
         self._pull()
+
+    def copy_state(self, tensor, stream=None):
+        """The plant's state block into ``tensor`` (float32, CUDA, contiguous,
+        at least one block), device to device on the current torch stream
+        (``mpcr_plant_copy_state``): a planner's start state."""
+        import torch
+        size = Engine.state_layout()["size"]
+        if (not isinstance(tensor, torch.Tensor) or not tensor.is_cuda or tensor.dtype != torch.float32
+                or not tensor.is_contiguous() or tensor.numel() < size or tensor.device.index != self.device):
+            raise ValueError(f"tensor must be a contiguous float32 CUDA tensor of at least {size} elements on the "
+                             f"plant's device (cuda:{self.device})")
+        st = stream if stream is not None else torch.cuda.current_stream(tensor.device).cuda_stream
+        check(_lib.load().mpcr_plant_copy_state(self.handle, ctypes.c_void_p(tensor.data_ptr()), ctypes.c_void_p(st)))
+        return tensor
 
     def forward(self):
         """mj_forward: qacc and the eef pose at the current state."""

@@ -56,8 +56,11 @@ def run_cem_planner(num_dof=None, num_batch=None, num_steps=None, maxiter_cem=No
                     target_names=None, show_viewer=None, cam_distance=None, show_contact_points=None,
                     position_threshold=None, rotation_threshold=None, save_data=None, data_dir=None,
                     stop_at_final_target=None, *, max_ticks=100, model_path=None, device=None, graph=True,
-                    verbose=True, planner_kwargs=None):
-    """Run the CEM planner in closed loop for ``max_ticks`` ticks (headless)."""
+                    verbose=True, planner_kwargs=None, plan_from_state=False):
+    """Run the CEM planner in closed loop for ``max_ticks`` ticks (headless).
+    plan_from_state: every tick's rollouts start from the plant's full state
+    (a device copy of its block) instead of the template state with the arm
+    joints set, which is the reference's behaviour and the default."""
     if initial_qpos is None:
         initial_qpos = [1.5, -1.8, 1.75, -1.25, -1.6, 0]
     if target_names is None:
@@ -76,7 +79,8 @@ def run_cem_planner(num_dof=None, num_batch=None, num_steps=None, maxiter_cem=No
     cem = cem_planner(num_dof=num_dof, num_batch=num_batch, num_steps=num_steps, maxiter_cem=maxiter_cem,
                       w_pos=w_pos, w_rot=w_rot, w_col=w_col, num_elite=num_elite, timestep=timestep,
                       maxiter_projection=maxiter_projection, model_path=model_path, device=device, graph=graph,
-                      verbose=verbose, **({"return_rollouts": False} | (planner_kwargs or {})))
+                      verbose=verbose, **({"return_rollouts": False} | (planner_kwargs or {})
+                                          | ({"plan_from_state": True} if plan_from_state else {})))
     log(f"Initialized CEM Planner: {round(time.time() - start_time, 2)}s")
 
     model = cem.model
@@ -98,7 +102,9 @@ def run_cem_planner(num_dof=None, num_batch=None, num_steps=None, maxiter_cem=No
     target_pos = bodies.pos(target_names[0])
     target_rot = bodies.quat(target_names[0])
     start_time = time.time()
-    _ = cem.compute_cem(xi_mean, data.qpos[ctrl_q], data.qvel[ctrl_v], data.qacc[ctrl_v], target_pos, target_rot)
+    from_plant = {"state": data} if plan_from_state else {}  # each tick plans from the plant's state
+    _ = cem.compute_cem(xi_mean, data.qpos[ctrl_q], data.qvel[ctrl_v], data.qacc[ctrl_v], target_pos, target_rot,
+                        **from_plant)
     log(f"Compute CEM: {round(time.time() - start_time, 2)}s")
 
     thetadot = np.zeros(num_dof)
@@ -121,7 +127,7 @@ def run_cem_planner(num_dof=None, num_batch=None, num_steps=None, maxiter_cem=No
             bodies.set("target_0", data.site_xpos_tcp, data.xquat_hande)
 
         cost, best_cost_g, best_cost_r, best_cost_c, best_vels, best_traj, xi_mean, _, _ = cem.compute_cem(
-            xi_mean, data.qpos[ctrl_q], data.qvel[ctrl_v], data.qacc[ctrl_v], target_pos, target_rot)
+            xi_mean, data.qpos[ctrl_q], data.qvel[ctrl_v], data.qacc[ctrl_v], target_pos, target_rot, **from_plant)
 
         thetadot = np.mean(best_vels[1:num_steps - 2], axis=0)
         data.step(thetadot)
@@ -200,6 +206,8 @@ def main(argv=None):  # SBP/mpc_planner.py:256-314
     parser.add_argument("--max_ticks", type=int, default=100)
     parser.add_argument("--model", type=str, default=None, help="MJCF path or bundled model name")
     parser.add_argument("--no_graph", action="store_true")
+    parser.add_argument("--plan_from_state", action="store_true",
+                        help="plan each tick from the plant's full state, not the template state")
     a = parser.parse_args(argv)
     return run_cem_planner(num_dof=a.num_dof, num_batch=a.num_batch, num_steps=a.num_steps,
                            maxiter_cem=a.maxiter_cem, maxiter_projection=a.maxiter_projection, w_pos=a.w_pos,
@@ -209,7 +217,7 @@ def main(argv=None):  # SBP/mpc_planner.py:256-314
                            position_threshold=a.position_threshold, rotation_threshold=a.rotation_threshold,
                            save_data=a.save_data, data_dir=a.data_dir,
                            stop_at_final_target=not a.continue_after_final, max_ticks=a.max_ticks,
-                           model_path=a.model, graph=not a.no_graph)
+                           model_path=a.model, graph=not a.no_graph, plan_from_state=a.plan_from_state)
 
 
 if __name__ == "__main__":

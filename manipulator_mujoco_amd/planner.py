@@ -93,13 +93,20 @@ class cem_planner:  # noqa: N801 (reference name)
     seed_step           problem p draws with the Philox key seed + p seed_step
                         (0: every problem the same draws), i.e. what a
                         planner built with that seed draws
+    plan_from_state     rollouts start from a full state per problem (object,
+                        fingers, other arm; ``compute_cem(state=...)``) instead
+                        of the model's template state with only the arm joints
+                        set, which is what the reference does (:105-107) and
+                        the default here.  The state lives in a static device
+                        buffer, initialised to the template, that the
+                        (captured) rollouts read each tick
     """
 
     def __init__(self, num_dof=None, num_batch=None, num_steps=None, timestep=None, maxiter_cem=None,
                  num_elite=None, w_pos=None, w_rot=None, w_col=None, maxiter_projection=None, *,
                  model_path=None, device=None, seed=0, elite_from_filtered=False, graph=False, group=None,
                  gather_rollouts=False, return_rollouts=True, capture_exchange=True, verbose=True,
-                 num_problems=1, seed_step=0):
+                 num_problems=1, seed_step=0, plan_from_state=False):
         import torch
         import torch.distributed as tdist
 
@@ -177,6 +184,11 @@ class cem_planner:  # noqa: N801 (reference name)
         self._theta = torch.empty((it_n,) + pb + (n, self.num_dof * H), **f32)
         self._costs = torch.empty((it_n,) + pb + (n, 4), **f32)
         self._mean_in = torch.empty(pb + (self.nvar,), **f32)
+        # one start state block per problem (Engine.pack_state), the template until a tick stages another
+        self.plan_from_state = bool(plan_from_state)
+        self._state = None
+        if self.plan_from_state:
+            self._state = torch.as_tensor(self.engine.pack_state()).to(self.device).repeat(B, 1).contiguous()
         self._graphs = None
         if verbose and self.rank == 0:
             self.print_info()
@@ -206,9 +218,14 @@ class cem_planner:  # noqa: N801 (reference name)
         self.cem.sample_project_multi(B, n, self._mean, self.seed, it, self._beq, self.maxiter_projection, bounds,
                                       rho=1.0, seed_step=self.seed_step, xi_samples=self._xs, out=self._xf,
                                       index_base=self.index_base)
-        self.engine.rollout_cost_multi(self._xf.view(B * n, self.nvar), MPCR_LAYOUT_XI, self._par, B,
-                                       self._costs[it], theta=self._theta[it], thetadot=self._thetadot[it],
-                                       best_keys=self._key if last else None, index_base=self.index_base)
+        out = dict(theta=self._theta[it], thetadot=self._thetadot[it], best_keys=self._key if last else None,
+                   index_base=self.index_base)
+        if self.plan_from_state:  # the same launch, reading each problem's start block
+            self.engine.rollout_cost_state(self._xf.view(B * n, self.nvar), MPCR_LAYOUT_XI, self._par, B,
+                                           self._costs[it], start=self._state, **out)
+        else:
+            self.engine.rollout_cost_multi(self._xf.view(B * n, self.nvar), MPCR_LAYOUT_XI, self._par, B,
+                                           self._costs[it], **out)
 
     def _seg_local_update(self, it):
         """compute_ellite_samples + compute_mean_cov on one rank (:355-360)."""
@@ -303,9 +320,34 @@ class cem_planner:  # noqa: N801 (reference name)
         par = np.stack([Engine.params(init_pos[p], weights[p], target_pos[p], target_rot[p]) for p in range(B)])
         self._par.copy_(torch.as_tensor(par).view(self._par.shape))
 
+    def _stage_states(self, states):
+        """Each problem's start state into its block of the static buffer: a
+        ``Plant`` (device-to-device copy of its block), ``(qpos, qvel[,
+        qacc_warmstart])`` arrays, or None, which keeps what is staged."""
+        import torch
+        if states is None:
+            return
+        if not self.plan_from_state:
+            raise ValueError("a start state needs a planner built with plan_from_state=True")
+        if len(states) != self.num_problems:
+            raise ValueError(f"{len(states)} start states for {self.num_problems} problem(s)")
+        for p, st in enumerate(states):
+            if st is None:
+                continue
+            if hasattr(st, "copy_state"):
+                st.copy_state(self._state[p])
+            else:
+                if not 2 <= len(st) <= 3:
+                    raise ValueError("a start state is a Plant or (qpos, qvel[, qacc_warmstart])")
+                self._state[p].copy_(torch.as_tensor(self.engine.pack_state(*st)))
+
     def compute_cem(self, xi_mean, init_pos=(1.5, -1.8, 1.75, -1.25, -1.6, 0.0), init_vel=None, init_acc=None,
-                    target_pos=None, target_rot=None):
-        """One MPC tick of CEM (SBP/mjx_planner.py:364-406). Returns the reference 9-tuple (numpy)."""
+                    target_pos=None, target_rot=None, state=None):
+        """One MPC tick of CEM (SBP/mjx_planner.py:364-406). Returns the reference 9-tuple (numpy).
+        state (planners built with plan_from_state): the full state the
+        rollouts start from, a ``Plant`` or ``(qpos, qvel[, qacc_warmstart])``;
+        None keeps the one staged last (at first the template).  init_pos
+        still sets the arm joints."""
         import torch
 
         from . import dist as mdist
@@ -326,6 +368,7 @@ class cem_planner:  # noqa: N801 (reference name)
             raise ValueError("num_elite * num_batch must select at least one elite")
         self._stage(np.asarray(xi_mean, np.float32).reshape(1, self.nvar), init_pos[None], init_vel[None],
                     init_acc[None], target_pos[None], target_rot[None], [w])
+        self._stage_states(None if state is None else [state])
         self._run_iterations()
 
         costs, theta, thetadot = self._costs, self._theta, self._thetadot
@@ -352,7 +395,7 @@ class cem_planner:  # noqa: N801 (reference name)
         return tuple(o.cpu().numpy() if isinstance(o, torch.Tensor) else o for o in out)
 
     def compute_cem_batch(self, xi_mean, init_pos, init_vel=None, init_acc=None, target_pos=None, target_rot=None,
-                          weights=None):
+                          weights=None, states=None):
         """One MPC tick of ``num_problems`` independent CEM problems in one
         batched sequence of launches (each kernel of ``compute_cem`` once,
         over every problem): xi_mean (B, nvar), init_pos / init_vel /
@@ -361,7 +404,9 @@ class cem_planner:  # noqa: N801 (reference name)
         problem).  Returns the 9 entries of ``compute_cem``, each stacked
         over the problems on a new leading axis: ``out[j][p]`` is bitwise
         entry j of ``compute_cem`` on a planner with seed ``seed + p
-        seed_step`` given problem p's arguments."""
+        seed_step`` given problem p's arguments.  states (planners built with
+        plan_from_state): one start state per problem, each as ``compute_cem``'s
+        ``state`` (a None entry keeps that problem's)."""
         import torch
 
         B, d, H, n, it_n = self.num_problems, self.num_dof, self.num, self.n_local, self.maxiter_cem
@@ -385,6 +430,7 @@ class cem_planner:  # noqa: N801 (reference name)
         weights = rows(weights, 3, "weights", np.float32)
 
         self._stage(xi_mean, init_pos, init_vel, init_acc, target_pos, target_rot, weights)
+        self._stage_states(states)
         self._run_iterations()
 
         # each problem's best candidate of the last iteration: the low word of
