@@ -173,6 +173,19 @@ int mpcr_rollout_occupancy(int device, int* info);
    Process-wide (an atomic read by every engine's next launch; the
    environment is read once, when the library loads). */
 int mpcr_set_two_wave_max_n(int n);
+/* Self-test of the rollout kernels' wave reductions on `device`: in holds nvec
+   vectors of 64 floats (host memory, 1 <= nvec <= 65536), one 64-lane block
+   sums each with every form the kernels use, out (host, 12 floats per vector)
+   receives
+     [0] the reference sum (six DPP steps, lane 63)     [1] the full sum
+     [2] [3] the two-value form on vectors b, b + 1     (indices cyclic in nvec)
+     [4] [5] [6] the three-value form on b, b + 1, b + 2
+     [7] the reference on lanes 0-15 (the rest +0)      [8] the one-row form on the same
+     [9] the reference on lanes 0-31 (the rest +0)      [10] the two-row form on the same
+     [11] 0.
+   Every production form must equal its reference bit for bit
+   (tests/test_gpu_reduce.py). */
+int mpcr_selftest_reduce(int device, const float* in, int nvec, float* out);
 /* Kernel dispatches one mpcr_rollout_cost call over n candidates issues on
    this engine (1, or -- dual-arm batches above the resident-block count --
    one per horizon segment and candidate group, MPCR_SEG_STEPS /

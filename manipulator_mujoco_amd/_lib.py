@@ -38,6 +38,9 @@ EXPORTS += _MULTI
 # planning from a state, likewise: absent from an older build
 _STATE = ("mpcr_state_layout", "mpcr_rollout_cost_state", "mpcr_plant_copy_state")
 EXPORTS += _STATE
+# the wave-reduction self-test, likewise
+_SELFTEST = ("mpcr_selftest_reduce",)
+EXPORTS += _SELFTEST
 _VOID = ("mpcr_last_error", "mpcr_model_free", "mpcr_engine_free", "mpcr_best_key_decode", "mpcr_cem_free",
          "mpcr_plant_free", "mpcr_comm_free")
 
@@ -133,8 +136,12 @@ def load():
     for name, at in state.items():
         if have_state:
             getattr(lib, name).argtypes = at
+    have_selftest = hasattr(lib, _SELFTEST[0])
+    if have_selftest:
+        lib.mpcr_selftest_reduce.argtypes = [i, vp, i, vp]
     for name in EXPORTS + ("mpcr_rollout_trace", "mpcr_plant_step_debug", "mpcr_plant_dbg_size"):
-        if (name in _MULTI and not have_multi) or (name in _STATE and not have_state):
+        if (name in _MULTI and not have_multi) or (name in _STATE and not have_state) or (
+                name in _SELFTEST and not have_selftest):
             continue
         if name not in _VOID:
             getattr(lib, name).restype = i

@@ -573,7 +573,8 @@ static int build_dev_model(const mpcr_model_t& m, const int32_t* lutadr, DevMode
   d.nctrl = m.nctrl;
   d.iterations = m.iterations;
   d.ls_iterations = m.ls_iterations;
-  d.disableflags = m.disableflags;
+  // (MPCR_NEWTON_REUSE=0, read when the engine is created: the kernel's first Newton iteration recomputes)
+  d.disableflags = m.disableflags | (env_int_or("MPCR_NEWTON_REUSE", 1) ? 0 : DEV_NO_NEWTON_REUSE);
   d.timestep = (float)m.timestep;
   d.tolerance = (float)m.tolerance;
   d.ls_tolerance = (float)m.ls_tolerance;
@@ -1357,6 +1358,13 @@ extern "C" int mpcr_rollout_occupancy(int device, int* info) {
   if (!info) return fail(MPCR_EINVAL, "null argument");
   HIPCHK(hipSetDevice(device));
   HIPCHK(rollout_occupancy(info));
+  return MPCR_OK;
+}
+
+extern "C" int mpcr_selftest_reduce(int device, const float* in, int nvec, float* out) {
+  if (!in || !out || nvec < 1 || nvec > 65536) return fail(MPCR_EINVAL, "selftest_reduce: null argument or nvec outside 1..65536");
+  HIPCHK(hipSetDevice(device));
+  HIPCHK(rollout_selftest_reduce(in, nvec, out));
   return MPCR_OK;
 }
 

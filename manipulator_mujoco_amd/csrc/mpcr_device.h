@@ -51,6 +51,11 @@ inline const MPCR_GMEM T* as_gmem(T* p) {
 // body kinds for the kinematics pass
 enum { BK_STATIC = 0, BK_FREE = 1, BK_HINGE = 2, BK_SLIDE = 3, BK_WELD = 4 };
 
+// DevModel::disableflags carries the model's MPCR_DSBL_* bits and, above
+// them, this engine-set one: Newton's first iteration recomputes what the
+// warm-start choice computed (rollout.hip; MPCR_NEWTON_REUSE=0, tests)
+constexpr int DEV_NO_NEWTON_REUSE = 1 << 30;
+
 struct DevModel {
   int nbody, njnt, nq, nv, ngeom, npair, neq, nslot;
   int nctrl, ntree, hande_body, tcp_body;

@@ -372,6 +372,8 @@ hipError_t rollout_wide_occupancy(int* info);
 int rollout_dispatches(bool wide, const RolloutArgs& a, unsigned grid, int groups, bool streams);
 // resident blocks per CU, static LDS bytes, VGPRs: narrow (0..2), wide (3..5)
 hipError_t rollout_occupancy(int* info);
+constexpr int REDUCE_SELFTEST_OUT = 12;  // floats per vector of mpcr_selftest_reduce (include/mpcr.h)
+hipError_t rollout_selftest_reduce(const float* in, int n, float* out);  // host pointers
 int rollout_set_wpc2_max_n(int n);  // two waves per candidate up to n (narrow variant); returns the previous
 
 }  // namespace mpcr

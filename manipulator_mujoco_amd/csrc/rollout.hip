@@ -158,7 +158,11 @@ template <int CTRL, int ROWS>
 __device__ __forceinline__ float dppf_rows(float v) {
   return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROWS, 0xF, false));
 }
-__device__ __forceinline__ float wsum(float v) {
+// the reference form, every step a builtin: the compiler folds the in-row
+// steps into v_add_f32_dpp but leaves each cross-row step as v_mov (old = 0),
+// v_mov_b32_dpp, v_add_f32 -- 11 VALU.  Kept for mpcr_selftest_reduce, which
+// holds every production form below to its bits.
+__device__ __forceinline__ float wsum_ref(float v) {
   v += dppf<0xB1>(v);
   v += dppf<0x4E>(v);
   v += dppf<0x124>(v);
@@ -166,6 +170,82 @@ __device__ __forceinline__ float wsum(float v) {
   v += dppf_rows<0x142, 0xA>(v);  // row_bcast:15 into rows 1, 3
   v += dppf_rows<0x143, 0xC>(v);  // row_bcast:31 into rows 2, 3
   return rdlane(v, 63);
+}
+// the four in-row steps: lane 15 of each row ends with its row's sum
+__device__ __forceinline__ float wsum_row(float v) {
+  v += dppf<0xB1>(v);
+  v += dppf<0x4E>(v);
+  v += dppf<0x124>(v);
+  v += dppf<0x128>(v);
+  return v;
+}
+// The cross-row steps as one v_add_f32_dpp each (the rows a step does not
+// write keep their value where the reference adds 0 to it; only lane 63 is
+// read, and it sees the same sums in the same order): 7 VALU.  The hazard
+// recogniser does not look inside the string, so the two wait states between a
+// VALU write and a DPP read of the same register stand in it, and the one
+// ahead of the caller's v_readlane closes it.  wsum2 / wsum3 reduce
+// independent values side by side, each in its own six-step order: the other
+// values' adds stand where the s_nop would.
+#define MPCR_DPP15 " row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
+#define MPCR_DPP31 " row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"
+__device__ __forceinline__ float wsum(float v) {
+  v = wsum_row(v);
+  asm("s_nop 1\n\t"
+      "v_add_f32_dpp %0, %0, %0" MPCR_DPP15
+      "s_nop 1\n\t"
+      "v_add_f32_dpp %0, %0, %0" MPCR_DPP31
+      "s_nop 0"
+      : "+v"(v));
+  return rdlane(v, 63);
+}
+__device__ __forceinline__ void wsum2(float& a, float& b) {
+  a = wsum_row(a);
+  b = wsum_row(b);
+  asm("s_nop 1\n\t"
+      "v_add_f32_dpp %0, %0, %0" MPCR_DPP15
+      "v_add_f32_dpp %1, %1, %1" MPCR_DPP15
+      "s_nop 0\n\t"
+      "v_add_f32_dpp %0, %0, %0" MPCR_DPP31
+      "v_add_f32_dpp %1, %1, %1" MPCR_DPP31
+      "s_nop 0"
+      : "+v"(a), "+v"(b));
+  a = rdlane(a, 63);
+  b = rdlane(b, 63);
+}
+__device__ __forceinline__ void wsum3(float& a, float& b, float& c) {
+  a = wsum_row(a);
+  b = wsum_row(b);
+  c = wsum_row(c);
+  asm("s_nop 1\n\t"
+      "v_add_f32_dpp %0, %0, %0" MPCR_DPP15
+      "v_add_f32_dpp %1, %1, %1" MPCR_DPP15
+      "v_add_f32_dpp %2, %2, %2" MPCR_DPP15
+      "v_add_f32_dpp %0, %0, %0" MPCR_DPP31
+      "v_add_f32_dpp %1, %1, %1" MPCR_DPP31
+      "v_add_f32_dpp %2, %2, %2" MPCR_DPP31
+      "s_nop 0"
+      : "+v"(a), "+v"(b), "+v"(c));
+  a = rdlane(a, 63);
+  b = rdlane(b, 63);
+  c = rdlane(c, 63);
+}
+// Sum of a value that is +0 in every lane from W on (W = 16: one row, the
+// in-row steps alone; W = 32: two rows, the row_bcast:15 step joins them):
+// the steps left out add +0 in the reference.  Its one visible effect, -0
+// becoming +0 (a row whose lanes are all -0), is restored on the scalar unit,
+// so the value is wsum's bit for bit.  5 VALU (W = 16), 6 (W = 32).
+template <int W>
+__device__ __forceinline__ float wsum_lo(float v) {
+  static_assert(W == 16 || W == 32, "one or two rows");
+  v = wsum_row(v);
+  if constexpr (W == 32)
+    asm("s_nop 1\n\t"
+        "v_add_f32_dpp %0, %0, %0" MPCR_DPP15
+        "s_nop 0"
+        : "+v"(v));
+  const unsigned u = (unsigned)__builtin_amdgcn_readlane(__float_as_int(v), W - 1);
+  return __uint_as_float(u == 0x80000000u ? 0u : u);
 }
 __device__ __forceinline__ int lanes_below(unsigned long long mask) {
   return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
@@ -2411,9 +2491,10 @@ template <class S, bool Q0 = true, class T = LsReal<S>>
 __device__ __forceinline__ LsPtT<T> ls_eval(const S& s, int lane, const float qg[3], T alpha) {
   float q0, q1, q2;
   ls_rows(s, lane, alpha, q0, q1, q2);
-  q0 = Q0 ? wsum(q0) + qg[0] : 0.f;
-  q1 = wsum(q1) + qg[1];
-  q2 = wsum(q2) + qg[2];
+  if constexpr (Q0) wsum3(q0, q1, q2); else wsum2(q1, q2);
+  q0 = Q0 ? q0 + qg[0] : 0.f;
+  q1 = q1 + qg[1];
+  q2 = q2 + qg[2];
   LsPtT<T> p = ls_make<T>(alpha, q0, q1, q2);
   p.full = Q0;
   return p;
@@ -2429,8 +2510,9 @@ __device__ __forceinline__ void ls_finish(const S& s, int lane, const float qg[3
     if (eq || ls_neg(jar, jv, a.alpha)) qa += c0;
     if (eq || ls_neg(jar, jv, b.alpha)) qb += c0;
   }
-  qa = wsum(qa) + qg[0];
-  qb = wsum(qb) + qg[0];
+  wsum2(qa, qb);
+  qa = qa + qg[0];
+  qb = qb + qg[0];
   if (!a.full) { a.cost = a.cost + qa; a.full = true; }
   if (!b.full) { b.cost = b.cost + qb; b.full = true; }
 }
@@ -2454,8 +2536,16 @@ __device__ __forceinline__ void ls_eval3(const S& s, int lane, const float qg[3]
       if (eq || ls_neg(jar, jv, al[k])) { q[3 * k] += c0; q[3 * k + 1] += c1; q[3 * k + 2] += c2; }
     }
   }
+  if constexpr (Q0) {
+    wsum3(q[0], q[1], q[2]);
+    wsum3(q[3], q[4], q[5]);
+    wsum3(q[6], q[7], q[8]);
+  } else {
+    wsum3(q[1], q[2], q[4]);
+    wsum3(q[5], q[7], q[8]);
+  }
 #pragma unroll
-  for (int k = 0; k < 9; k++) q[k] = (Q0 || k % 3) ? wsum(q[k]) + qg[k % 3] : 0.f;
+  for (int k = 0; k < 9; k++) q[k] = (Q0 || k % 3) ? q[k] + qg[k % 3] : 0.f;
   p0 = ls_make<T>(a0, q[0], q[1], q[2]);
   p1 = ls_make<T>(a1, q[3], q[4], q[5]);
   p2 = ls_make<T>(a2, q[6], q[7], q[8]);
@@ -2546,8 +2636,9 @@ __device__ __forceinline__ void ls_cones3(const S& s, const DevModel* __restrict
       e[3 * k] += c0; e[3 * k + 1] += c1; e[3 * k + 2] += c2;
     }
   }
-#pragma unroll
-  for (int k = 0; k < 9; k++) e[k] = wsum(e[k]);
+  wsum3(e[0], e[1], e[2]);
+  wsum3(e[3], e[4], e[5]);
+  wsum3(e[6], e[7], e[8]);
 }
 
 template <class T>
@@ -3269,9 +3360,9 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
     }
     for (int tr = 0; tr < m->ntree; tr++) {
       float mm = (lane < nb && m->body_tree[lane] == tr) ? m->body_mass[lane] : 0.f;
-      float cx = wsum(mm * (lane < nb ? s.xipos[lane][0] : 0.f));
-      float cy = wsum(mm * (lane < nb ? s.xipos[lane][1] : 0.f));
-      float cz = wsum(mm * (lane < nb ? s.xipos[lane][2] : 0.f));
+      float cx = wsum_lo<NBW>(mm * (lane < nb ? s.xipos[lane][0] : 0.f));
+      float cy = wsum_lo<NBW>(mm * (lane < nb ? s.xipos[lane][1] : 0.f));
+      float cz = wsum_lo<NBW>(mm * (lane < nb ? s.xipos[lane][2] : 0.f));
       if (lane == 0) {
         float tm = m->tree_mass[tr];
         s.com[tr][0] = cx / tm; s.com[tr][1] = cy / tm; s.com[tr][2] = cz / tm;
@@ -4358,9 +4449,23 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
     {
       const int nefc = s.nefc;
       float qacc_l = lane < NVW ? s.qas[lane] : 0.f;  // this lane's dof value
+      // Single-arm kernels: the warm-start choice below evaluates M a, the
+      // Gauss term and the cost at both candidates, and Newton's first
+      // iteration starts at the one it picks -- the same expressions on the
+      // same data.  So the choice keeps M a_w and the chosen side's reduced
+      // sums, and iteration 0 takes them instead of an m_dot and two wave sums
+      // (-24 VALU per C3 candidate-step).  The rows' J a - aref are recomputed:
+      // keeping both sides' in efc_jar / efc_jv saved 21 more but any LDS store
+      // in the choice's row loop took the one-wave kernels from 118 to 124
+      // VGPRs ("Measured and not kept").  DEV_NO_NEWTON_REUSE in the
+      // device model's flags (MPCR_NEWTON_REUSE=0, tests) recomputes all.
+      bool ws_keep = false, ws_won = false;
+      float ws_maw = 0.f, ws_gw = 0.f, ws_cost = 0.f;
       if (nefc > 0) {
         // warm start: the better of qacc_warmstart and qacc_smooth
-        if (!(m->disableflags & 4)) {
+        const int dflags = m->disableflags;
+        if (!(dflags & 4)) {
+          if constexpr (!S::WIDE) ws_keep = !(dflags & DEV_NO_NEWTON_REUSE);
           // (the Gauss term of qacc_smooth itself is (M a_s - f_s)'(a_s - a_s) = 0)
           const float maw = lane < nv ? m_dot(lane, s.qws) : 0.f;
           const float gw = lane < nv ? (maw - s.qfs[lane]) * (s.qws[lane] - s.qas[lane]) : 0.f;
@@ -4389,9 +4494,17 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
             if (eq || jw < 0.f) cw += s.efc_D[r] * jw * jw;
             if (eq || js < 0.f) cs += s.efc_D[r] * js * js;
           }
-          const float costw = 0.5f * wsum(gw) + 0.5f * wsum(cw);
-          const float costs = 0.5f * wsum(cs);
+          wsum2(cw, cs);
+          const float gws = wsum_lo<NVW>(gw);
+          const float costw = 0.5f * gws + 0.5f * cw;
+          const float costs = 0.5f * cs;
           if (costw < costs && lane < NVW) qacc_l = s.qws[lane];
+          if constexpr (!S::WIDE) {
+            ws_won = costw < costs;
+            ws_maw = maw;
+            ws_gw = ws_won ? gws : 0.f;  // (the Gauss term at qacc_smooth is 0)
+            ws_cost = ws_won ? costw : costs;
+          }
           if (args.dbg && b == 0 && t == H - 1 && lane == 0) {
             args.dbg[DBG_INFO + 0] = costw < costs ? 1.f : 0.f;
             args.dbg[DBG_INFO + 1] = costw;
@@ -4415,7 +4528,10 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
           wt_newton++;
 #endif
           // Ma, jar, cost at the current qacc; per-row force and active D
-          const float ma = lane < nv ? m_dot(lane, s.qacc) : 0.f;
+          const bool reuse = !S::WIDE && ws_keep;  // wave-uniform; the first iteration only (cleared below)
+          float ma;
+          if (reuse && ws_won) ma = ws_maw;
+          else ma = lane < nv ? m_dot(lane, s.qacc) : 0.f;
           float cc = 0.f;
           for (int r = lane; r < nefc; r += WAVE) {
             const float jar = jdot(s, gx, r, s.qacc) - s.efc_aref[r];
@@ -4442,8 +4558,14 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
               }
             }
           }
-          const float gauss = wsum(lane < nv ? (ma - s.qfs[lane]) * (s.qacc[lane] - s.qas[lane]) : 0.f);
-          const float cost = 0.5f * gauss + 0.5f * wsum(cc);
+          float gauss, cost;
+          if (reuse) {
+            gauss = ws_gw;
+            cost = ws_cost;
+          } else {
+            gauss = wsum_lo<NVW>(lane < nv ? (ma - s.qfs[lane]) * (s.qacc[lane] - s.qas[lane]) : 0.f);
+            cost = 0.5f * gauss + 0.5f * wsum(cc);
+          }
           sync();
           if (hess2) block_sync();  // this iteration's active set, to wave 1
           STAMP(29);
@@ -4497,7 +4619,7 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
             sync();  // qcs (srch) is rewritten below
           }
           STAMP(30);
-          const float gn = sqrtf(wsum(grad * grad));
+          const float gn = sqrtf(wsum_lo<NVW>(grad * grad));
           // MuJoCo's stop test, plus its fp32 floor: an improvement within ~8 ulp
           // of the cost is rounding noise (without it fp32 iterates on noise
           // where the fp64 solve has converged: 3.9 vs 1.9 iterations per
@@ -4552,12 +4674,12 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
           // Mv, jv, quadratic coefficients
           const float mvv = lane < nv ? m_dot(lane, s.srch) : 0.f;
           for (int r = lane; r < nefc; r += WAVE) s.efc_jv[r] = jdot(s, gx, r, s.srch);
-          const float sn = sqrtf(wsum(search * search));
+          const float sn = sqrtf(wsum_lo<NVW>(search * search));
           const float gtol = m->tolerance * m->ls_tolerance * sn * m->meaninertia * (float)(nv > 1 ? nv : 1);
           float qg[3];
           qg[0] = 0.5f * gauss;
-          qg[1] = wsum(lane < nv ? search * (ma - s.qfs[lane]) : 0.f);
-          qg[2] = 0.5f * wsum(search * mvv);
+          qg[1] = wsum_lo<NVW>(lane < nv ? search * (ma - s.qfs[lane]) : 0.f);
+          qg[2] = 0.5f * wsum_lo<NVW>(search * mvv);
           sync();
           using LT = LsReal<S>;
           using LsPt = LsPtT<LT>;
@@ -4631,6 +4753,7 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
           if (args.dbg && b == 0 && t == H - 1 && lane == 0) args.dbg[DBG_INFO + 7] = (float)(it + 1);
           if (improved && lane < NVW) s.qacc[lane] = (float)((LT)s.qacc[lane] + alpha * (LT)s.srch[lane]);
           prev_cost = cost;
+          ws_keep = false;
           sync();
           STAMP(9);
         }

@@ -169,4 +169,53 @@ hipError_t rollout_occupancy(int* info) {
   return rollout_wide_occupancy(info + 3);
 }
 
+// mpcr_selftest_reduce: every wave-sum form of rollout.hip on caller-given
+// vectors, one 64-lane block per vector.  out[12 b ..] = wsum_ref, wsum,
+// wsum2 (a, b), wsum3 (a, b, c), wsum_ref of lanes 0-15, wsum_lo<16>,
+// wsum_ref of lanes 0-31, wsum_lo<32>, 0; the second and third values of the
+// multi-value forms are vectors b + 1 and b + 2 (cyclic).  Each form gets its
+// own opaque copy of the input, so it runs its own instructions start to end.
+__device__ __forceinline__ float opaque(float v) {
+  asm volatile("" : "+v"(v));
+  return v;
+}
+__global__ __launch_bounds__(WAVE) void reduce_selftest_kernel(const float* __restrict__ in, int n,
+                                                               float* __restrict__ out) {
+  const int lane = threadIdx.x, b = blockIdx.x;
+  const float v = in[(size_t)b * WAVE + lane];
+  const float w = in[(size_t)((b + 1) % n) * WAVE + lane];
+  const float x = in[(size_t)((b + 2) % n) * WAVE + lane];
+  float r[REDUCE_SELFTEST_OUT];
+  r[0] = wsum_ref(opaque(v));
+  r[1] = wsum(opaque(v));
+  r[2] = opaque(v); r[3] = opaque(w);
+  wsum2(r[2], r[3]);
+  r[4] = opaque(v); r[5] = opaque(w); r[6] = opaque(x);
+  wsum3(r[4], r[5], r[6]);
+  r[7] = wsum_ref(opaque(lane < 16 ? v : 0.f));
+  r[8] = wsum_lo<16>(opaque(lane < 16 ? v : 0.f));
+  r[9] = wsum_ref(opaque(lane < 32 ? v : 0.f));
+  r[10] = wsum_lo<32>(opaque(lane < 32 ? v : 0.f));
+  r[11] = 0.f;
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < REDUCE_SELFTEST_OUT; k++) out[(size_t)b * REDUCE_SELFTEST_OUT + k] = r[k];
+  }
+}
+hipError_t rollout_selftest_reduce(const float* in, int n, float* out) {
+  float *din = nullptr, *dout = nullptr;
+  const size_t nin = (size_t)n * WAVE * sizeof(float), nout = (size_t)n * REDUCE_SELFTEST_OUT * sizeof(float);
+  hipError_t e = hipMalloc(&din, nin);
+  if (e == hipSuccess) e = hipMalloc(&dout, nout);
+  if (e == hipSuccess) e = hipMemcpy(din, in, nin, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(reduce_selftest_kernel, dim3(n), dim3(WAVE), 0, 0, din, n, dout);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(out, dout, nout, hipMemcpyDeviceToHost);
+  (void)hipFree(din);
+  (void)hipFree(dout);
+  return e;
+}
+
 }  // namespace mpcr
