@@ -116,7 +116,7 @@ int mpcr_model_set_timestep(mpcr_model* m, double timestep);
 int mpcr_model_info(const mpcr_model* m, int* nq, int* nv, int* nslot, int* nctrl, int* npair);
 void mpcr_model_free(mpcr_model* m);
 /* The support start table an engine builds for m's convex hulls (model
-   format v9 dropped it from the blob; engine.hip hull_start_table): R x R
+   format v9 dropped it from the blob; dev_model.h hull_start_table): R x R
    cells on each of the 6 cube faces (R = 0: the library's MPCR_LUT_R), cell
    (2 axis + negative) R^2 + iu R + iv (rollout.hip lut_cell), each naming
    the global hull vertex extreme along the cell centre (fp64; the lowest

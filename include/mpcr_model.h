@@ -40,7 +40,7 @@ extern "C" {
 #define MPCR_MAX_HULLA  49152 /* hull-graph adjacency entries */
 /* support start table resolution: 6 cube faces x R x R cells per hull.  Not
    part of the blob since v9 -- the engine builds the table from hull_vert
-   (engine.hip hull_start_table), so R is the library's build-time choice
+   (dev_model.h hull_start_table), so R is the library's build-time choice
    (round 5: 16 -> 128; 256 measured in round 6, DESIGN.md perf log) */
 #ifndef MPCR_LUT_R
 #define MPCR_LUT_R      128

@@ -39,8 +39,8 @@ SRC = [u[0] for u in UNITS]
 # missing): the rebuild check and source_hash() read this list.  The MJCF
 # library's source and ABI header are listed too, so the hash names the whole
 # native build.
-DEPS = SRC + [os.path.join(CSRC, f) for f in ("rollout.hip", "rollout.h", "step_table.h", "cem.hip", "comm.hip",
-                                              "mpcr_device.h", "mjcf_embed.cpp")] + [
+DEPS = SRC + [os.path.join(CSRC, f) for f in ("rollout.hip", "rollout.h", "step_table.h", "model_frames.h", "dev_model.h",
+                                              "cem.hip", "comm.hip", "mpcr_device.h", "mjcf_embed.cpp")] + [
     os.path.join(os.path.dirname(HERE), "include", f) for f in ("mpcr.h", "mpcr_model.h", "mpcr_mjcf.h")]
 OUT = os.path.join(HERE, "libmpcr.so")
 ARCH = os.environ.get("MPCR_OFFLOAD_ARCH", "gfx950")

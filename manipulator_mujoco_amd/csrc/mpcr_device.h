@@ -1,7 +1,7 @@
 // mpcr_device.h — fp32 device mirror of mpcr_model_t with the derived tables
 // the wave-per-rollout kernel needs (static-body poses folded in, subtree /
 // dof-chain bitmasks, collision-geom remap).  Built once per engine on the
-// host (engine.cpp: build_dev_model) and read by the kernel with uniform
+// host (dev_model.h: build_dev_model) and read by the kernel with uniform
 // (scalar-cache) loads.
 #pragma once
 #include <stdint.h>
@@ -161,7 +161,7 @@ struct DevModel {
   // convex hulls of mesh geoms (geom frame), hill-climbing graph -----------------
   int geom_hulladr[DX_NG];
   int geom_hullnum[DX_NG];
-  int geom_lutadr[DX_NG];  // first hull_lut cell (engine.hip hull_start_table), -1: no table
+  int geom_lutadr[DX_NG];  // first hull_lut cell (dev_model.h hull_start_table), -1: no table
   const MPCR_GMEM float4* hull_vert;  // xyz | degree (int bits in w)
   const MPCR_GMEM int2* hull_info;    // (adjacency start, count) per vertex
   const MPCR_GMEM float4* hull_adjv;  // neighbour xyz | (index | degree << 16) (bits in w): one load per neighbour

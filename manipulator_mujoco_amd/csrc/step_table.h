@@ -14,10 +14,12 @@
 // the launch arguments changes the dual-arm unit's device code: the model
 // pointer's launder scales by that size, the kernel metadata carries the
 // argument size.  engine.hip's mpcr_engine_create is the one place a device
-// model is allocated.)  engine.hip checks the table against the device model
-// it builds (step_table_matches) at every engine creation.
+// model is allocated.)  The bodies, frames, trees and dof kinds come from
+// model_frames() (model_frames.h), which the device model's builder
+// (dev_model.h build_dev_model) reads too, as it does the row values both
+// hold; tests/test_dev_model.py compares the two results on the CPU.
 //
-// Device indices as in engine.hip build_dev_model: moving bodies (not welded
+// Device indices as in dev_model.h build_dev_model: moving bodies (not welded
 // to the world) in model order, pairs / joints / equalities by their model
 // index.  (The geoms have no records: a geom's rotation matrix evaluated in
 // double has exact zeros where the kernel's fp32 q2m leaves 6e-8, which moves
@@ -28,7 +30,7 @@
 #include <stdint.h>
 #include <string.h>
 
-#include "../../include/mpcr_model.h"
+#include "model_frames.h"
 
 namespace mpcr {
 
@@ -47,9 +49,6 @@ enum {
   ST_LIMITED = 4,  // joint rows: a limited hinge / slide joint
   ST_CONDIM1 = 8   // pair rows: frictionless contact (one row)
 };
-// body kinds (mpcr_device.h BK_*)
-enum { ST_BK_FREE = 1, ST_BK_HINGE = 2, ST_BK_SLIDE = 3, ST_BK_WELD = 4 };
-
 // kinematics, by moving body (quads of 4 floats; 144 B)
 struct alignas(16) StepBody {
   int32_t kind, anc, qposadr;  // ST_BK_*; first moving ancestor (-1: none); the joint's qpos address (-1: weld)
@@ -75,35 +74,17 @@ struct alignas(16) StepRow {
   int32_t flags;
   float power;
   float range[2];                 // joint rows: limits, qpos address, dof address (dofadr: not read by the
-  int32_t qposadr, dofadr;        // kernel; it fills the quad and is checked against the device model)
+  int32_t qposadr, dofadr;        // kernel; it fills the quad and the tests compare it with the device model's)
 };
 
 struct alignas(16) StepTable {
-  int32_t flags, nbody, pad[2];  // nbody: for the checks (tests, step_table_matches), not read by the kernel
+  int32_t flags, nbody, pad[2];  // nbody: for the tests, not read by the kernel
   StepBody body[ST_NB];
   StepDof dof[ST_NV];
   StepRow row[ST_NROW];
 };
 
 namespace step_detail {
-inline void qmul(double r[4], const double a[4], const double b[4]) {
-  const double t[4] = {a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3],
-                       a[0] * b[1] + a[1] * b[0] + a[2] * b[3] - a[3] * b[2],
-                       a[0] * b[2] - a[1] * b[3] + a[2] * b[0] + a[3] * b[1],
-                       a[0] * b[3] + a[1] * b[2] - a[2] * b[1] + a[3] * b[0]};
-  memcpy(r, t, sizeof(t));
-}
-inline void q2m(double m[9], const double q[4]) {
-  const double w = q[0], x = q[1], y = q[2], z = q[3];
-  m[0] = 1 - 2 * (y * y + z * z); m[1] = 2 * (x * y - w * z); m[2] = 2 * (x * z + w * y);
-  m[3] = 2 * (x * y + w * z); m[4] = 1 - 2 * (x * x + z * z); m[5] = 2 * (y * z - w * x);
-  m[6] = 2 * (x * z - w * y); m[7] = 2 * (y * z + w * x); m[8] = 1 - 2 * (x * x + y * y);
-}
-inline void rot(double r[3], const double q[4], const double v[3]) {
-  double m[9];
-  q2m(m, q);
-  for (int i = 0; i < 3; i++) r[i] = m[3 * i] * v[0] + m[3 * i + 1] * v[1] + m[3 * i + 2] * v[2];
-}
 inline double clampd(double x, double lo, double hi) { return x < lo ? lo : (x > hi ? hi : x); }
 
 // the parameters of one constraint source from its solref / solimp
@@ -148,65 +129,22 @@ inline int build_step_table(const mpcr_model_t& m, StepTable& t) {
   memset(&t, 0, sizeof(t));
   if (m.nbody > MPCR_MAX_BODY || m.njnt > ST_NJ || m.nv > ST_NV || m.npair > ST_NP || m.neq > ST_NEQ)
     return -1;
-  // moving bodies; world poses of the static ones
-  int dmap[MPCR_MAX_BODY], nb = 0;
-  double wpos[MPCR_MAX_BODY][3] = {}, wquat[MPCR_MAX_BODY][4] = {};
-  dmap[0] = -1;
-  wquat[0][0] = 1;
-  for (int b = 1; b < m.nbody; b++) dmap[b] = m.body_weldid[b] != 0 ? nb++ : -1;
-  if (nb > ST_NB) return -1;
-  for (int b = 1; b < m.nbody; b++) {
-    if (dmap[b] >= 0) continue;
-    const int p = m.body_parentid[b];
-    double r[3];
-    rot(r, wquat[p], m.body_pos[b]);
-    for (int k = 0; k < 3; k++) wpos[b][k] = wpos[p][k] + r[k];
-    qmul(wquat[b], wquat[p], m.body_quat[b]);
-    const double n = sqrt(wquat[b][0] * wquat[b][0] + wquat[b][1] * wquat[b][1] + wquat[b][2] * wquat[b][2] +
-                          wquat[b][3] * wquat[b][3]);
-    for (int k = 0; k < 4; k++) wquat[b][k] /= n;
-  }
-  // kinematic trees in order of first appearance
-  int roots[MPCR_MAX_BODY], nroot = 0, btree[ST_NB];
-  for (int b = 1; b < m.nbody; b++) {
-    if (dmap[b] < 0) continue;
-    int tr = -1;
-    for (int k = 0; k < nroot; k++)
-      if (roots[k] == m.body_rootid[b]) tr = k;
-    if (tr < 0) { roots[nroot] = m.body_rootid[b]; tr = nroot++; }
-    btree[dmap[b]] = tr;
-  }
-  t.nbody = nb;
+  ModelFrames f;
+  if (model_frames(m, f) != 0 || f.nbody > ST_NB) return -1;
+  t.nbody = f.nbody;
   bool anchor0 = true;
-  for (int b = 1; b < m.nbody; b++) {
-    const int i = dmap[b];
-    if (i < 0) continue;
+  for (int i = 0; i < f.nbody; i++) {
     StepBody& r = t.body[i];
-    const int p = m.body_parentid[b];
-    const int j = m.body_jntnum[b] ? m.body_jntadr[b] : -1;
-    r.kind = j < 0 ? ST_BK_WELD
-                   : (m.jnt_type[j] == MPCR_JNT_FREE ? ST_BK_FREE
-                                                     : (m.jnt_type[j] == MPCR_JNT_HINGE ? ST_BK_HINGE : ST_BK_SLIDE));
-    double bq[4], bp[3];
-    if (dmap[p] < 0) {  // static parent: its constant world pose folded in
-      double w[3];
-      rot(w, wquat[p], m.body_pos[b]);
-      for (int k = 0; k < 3; k++) bp[k] = wpos[p][k] + w[k];
-      qmul(bq, wquat[p], m.body_quat[b]);
-      r.anc = -1;
-    } else {
-      memcpy(bp, m.body_pos[b], sizeof(bp));
-      memcpy(bq, m.body_quat[b], sizeof(bq));
-      r.anc = dmap[p];
-    }
-    if (r.kind == ST_BK_FREE) r.anc = -1;
+    const int b = f.id[i], j = f.jnt[i];
+    r.kind = f.kind[i];
+    r.anc = f.anc[i];
     r.qposadr = j >= 0 ? m.jnt_qposadr[j] : -1;
     r.qpos0 = j >= 0 ? (float)m.qpos0[m.jnt_qposadr[j]] : 0.f;
     double R[9];
-    q2m(R, bq);
-    for (int k = 0; k < 4; k++) r.bquat[k] = (float)bq[k];
+    q2m(R, f.bquat[i]);
+    for (int k = 0; k < 4; k++) r.bquat[k] = (float)f.bquat[i][k];
     for (int k = 0; k < 3; k++) {
-      r.bpos[k] = (float)bp[k];
+      r.bpos[k] = (float)f.bpos[i][k];
       r.ipos[k] = (float)m.body_ipos[b][k];
       for (int c = 0; c < 3; c++) r.R[k][c] = (float)R[3 * k + c];
     }
@@ -223,11 +161,11 @@ inline int build_step_table(const mpcr_model_t& m, StepTable& t) {
   // dofs
   for (int i = 0; i < m.nv; i++) {
     StepDof& r = t.dof[i];
-    const int j = m.dof_jntid[i], sub = i - m.jnt_dofadr[j];
-    r.body = dmap[m.dof_bodyid[i]];
-    r.kind = m.jnt_type[j] == MPCR_JNT_HINGE ? 0 : (m.jnt_type[j] == MPCR_JNT_SLIDE ? 1 : (sub < 3 ? 2 : 3));
-    r.tree = r.body >= 0 ? btree[r.body] : -1;
-    r.sub = sub < 3 ? sub : sub - 3;
+    const int j = m.dof_jntid[i];
+    r.body = f.dmap[m.dof_bodyid[i]];
+    r.kind = f.dof_kind[i];
+    r.tree = r.body >= 0 ? f.tree[r.body] : -1;
+    r.sub = f.dof_sub[i];
     for (int k = 0; k < 3; k++) { r.axis[k] = (float)m.jnt_axis[j][k]; r.jpos[k] = (float)m.jnt_pos[j][k]; }
   }
   // constraint sources
@@ -237,34 +175,27 @@ inline int build_step_table(const mpcr_model_t& m, StepTable& t) {
     const double mu = m.pair_friction[p];
     const double invw = m.body_invweight0[m.geom_bodyid[m.pair_geom1[p]]][0] +
                         m.body_invweight0[m.geom_bodyid[m.pair_geom2[p]]][0];
-    r.margin = (float)(m.pair_margin[p] - m.pair_gap[p]);
-    r.diag = (float)(m.pair_condim[p] == 1 ? invw : invw * (1.0 + mu * mu));
-    if (m.pair_condim[p] == 1) r.flags |= ST_CONDIM1;
+    r.margin = pair_margin_f(m, p);
+    r.diag = (float)(pair_frictionless(m, p) ? invw : invw * (1.0 + mu * mu));
+    if (pair_frictionless(m, p)) r.flags |= ST_CONDIM1;
     r.qposadr = r.dofadr = -1;
   }
   for (int j = 0; j < m.njnt; j++) {
     StepRow& r = t.row[ST_ROW_JNT + j];
     row_params(r, m.jnt_solref[j], m.jnt_solimp[j], m.timestep, m.disableflags);
-    r.margin = (float)m.jnt_margin[j];
-    r.diag = (float)m.dof_invweight0[m.jnt_dofadr[j]];
-    if (m.jnt_limited[j] && (m.jnt_type[j] == MPCR_JNT_SLIDE || m.jnt_type[j] == MPCR_JNT_HINGE)) r.flags |= ST_LIMITED;
-    r.range[0] = (float)m.jnt_range[j][0];
-    r.range[1] = (float)m.jnt_range[j][1];
+    r.margin = jnt_margin_f(m, j);
+    r.diag = dof_invweight_f(m, m.jnt_dofadr[j]);
+    if (jnt_limit_row(m, j)) r.flags |= ST_LIMITED;
+    r.range[0] = jnt_range_f(m, j, 0);
+    r.range[1] = jnt_range_f(m, j, 1);
     r.qposadr = m.jnt_qposadr[j];
     r.dofadr = m.jnt_dofadr[j];
   }
   for (int e = 0; e < m.neq; e++) {
     StepRow& r = t.row[ST_ROW_EQ + e];
     row_params(r, m.eq_solref[e], m.eq_solimp[e], m.timestep, m.disableflags);
-    double diag = 0;
-    if (m.eq_type[e] == MPCR_EQ_JOINT) {
-      diag = m.dof_invweight0[m.jnt_dofadr[m.eq_obj1[e]]];
-      if (m.eq_obj2[e] >= 0) diag += m.dof_invweight0[m.jnt_dofadr[m.eq_obj2[e]]];
-    } else if (m.eq_type[e] == MPCR_EQ_CONNECT) {
-      diag = m.body_invweight0[m.eq_obj1[e]][0] + m.body_invweight0[m.eq_obj2[e]][0];
-    }
     r.margin = 0.f;
-    r.diag = (float)diag;
+    r.diag = eq_diag_f(m, e);
     r.qposadr = r.dofadr = -1;
   }
   return 0;

@@ -1014,7 +1014,7 @@ static int lut_cell(const double l[3]) {
 }
 
 /* Support start tables.  The model blob carries none since v9 (the engine
-   builds its own, engine.hip hull_start_table); the oracle builds one per
+   builds its own, dev_model.h hull_start_table); the oracle builds one per
    model on first use, by the same definition -- per hull and cube-map cell
    the vertex extreme along the cell centre, cells in scan order, each
    climbing (strict ascent) from the previous cell's vertex, then the lowest
