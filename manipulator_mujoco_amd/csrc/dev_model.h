@@ -415,11 +415,8 @@ inline int build_dev_model(const mpcr_model_t& m, const int32_t* lutadr, const D
   for (int i = 0; i < m.nq; i++) d.qpos_init[i] = (float)m.qpos_init[i];
   for (int i = 0; i < m.nv; i++) d.qvel_init[i] = (float)m.qvel_init[i];
   // collision geoms referenced by pairs
-  std::vector<int> gmap(m.ngeom, -1);
-  int ng = 0;
-  for (int p = 0; p < m.npair; p++)
-    for (int g : {m.pair_geom1[p], m.pair_geom2[p]})
-      if (gmap[g] < 0) gmap[g] = ng++;
+  int gmap[MPCR_MAX_GEOM];
+  const int ng = pair_geom_map(m, gmap);
   if (ng > DX_NG || ng > WAVE) return dev_fail(err, MPCR_EMODEL, "%d collision geoms > %d", ng, DX_NG < WAVE ? DX_NG : WAVE);
   d.ngeom = ng;
   for (int g = 0; g < m.ngeom; g++) {

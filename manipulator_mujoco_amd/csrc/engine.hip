@@ -369,15 +369,19 @@ extern "C" int mpcr_engine_create(const mpcr_model* m, int device, int max_n, in
   if (int rc = compile_dev_model(h, opt, e->dev, t, err)) return refuse(fail(rc, "%s", err.c_str()));
   e->wide = needs_wide(h, e->dev);
   std::vector<StepTable> step;
+  std::vector<StepRecords> recs;
   if (!e->wide) {
     // built once: the model and the timestep are fixed for the engine's life
     // (single-arm kernels only: the dual-arm ones never read it)
     step.resize(1);
-    if (build_step_table(h, step[0]) != 0) return refuse(fail(MPCR_EMODEL, "model exceeds the step table's capacities"));
+    recs.resize(1);
+    if (build_step_table(h, step[0]) != 0 || build_step_records(h, recs[0]) != 0)
+      return refuse(fail(MPCR_EMODEL, "model exceeds the step table's capacities"));
   }
   // upload: the tables the device model points to (hulls, start table, faces,
   // cone cells), the model with the narrow kernels' step table directly behind
-  // it (step_table.h: the kernels address it as model + 1), then the staging
+  // it (step_table.h: the kernels address it as model + 1) and the load
+  // records behind that, then the staging
   // and scratch buffers
   DevBufs& mem = e->mem;
   if (h.nhullv > 0) {
@@ -400,10 +404,13 @@ extern "C" int mpcr_engine_create(const mpcr_model* m, int device, int max_n, in
   const int nc = h.nctrl;
   const size_t rows = (size_t)max_n + 1;  // per-candidate scratch slabs: one spare row of slack
   const size_t nhints = 2 * (size_t)max_n * (e->wide ? SmemW::NHINT : 1);
-  e->d_model = reinterpret_cast<DevModel*>(mem.alloc<char>(sizeof(DevModel) + sizeof(StepTable),
+  static_assert(sizeof(StepTable) % alignof(mpcr::StepRecords) == 0, "the load records' alignment behind the step table");
+  e->d_model = reinterpret_cast<DevModel*>(mem.alloc<char>(sizeof(DevModel) + sizeof(StepTable) + sizeof(StepRecords),
                                                            reinterpret_cast<const char*>(&e->dev), sizeof(DevModel)));
   if (e->d_model && !e->wide &&
-      hipMemcpy(e->d_model + 1, step.data(), sizeof(StepTable), hipMemcpyHostToDevice) != hipSuccess)
+      (hipMemcpy(e->d_model + 1, step.data(), sizeof(StepTable), hipMemcpyHostToDevice) != hipSuccess ||
+       hipMemcpy(reinterpret_cast<char*>(e->d_model + 1) + sizeof(StepTable), recs.data(), sizeof(StepRecords),
+                 hipMemcpyHostToDevice) != hipSuccess))
     mem.rc = MPCR_EHIP;
   e->d_pdot = mem.alloc<float>((size_t)horizon * nbasis, pdot, (size_t)horizon * nbasis);
   e->d_in = mem.alloc<float>((size_t)max_n * nc * (horizon > nbasis ? horizon : nbasis));

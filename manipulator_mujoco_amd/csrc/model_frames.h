@@ -110,6 +110,18 @@ inline int model_frames(const mpcr_model_t& m, ModelFrames& f) {
   return 0;
 }
 
+// Collision geoms (those a pair names) are numbered in order of first
+// appearance over the pairs: gmap[model geom] = collision geom or -1.
+// Returns their number.
+inline int pair_geom_map(const mpcr_model_t& m, int gmap[MPCR_MAX_GEOM]) {
+  for (int g = 0; g < MPCR_MAX_GEOM; g++) gmap[g] = -1;
+  int ng = 0;
+  for (int p = 0; p < m.npair; p++)
+    for (int g : {m.pair_geom1[p], m.pair_geom2[p]})
+      if (gmap[g] < 0) gmap[g] = ng++;
+  return ng;
+}
+
 // Values the step table's rows and the device model both hold (the integer
 // addresses jnt_qposadr / jnt_dofadr are copied as they are).
 inline float pair_margin_f(const mpcr_model_t& m, int p) { return (float)(m.pair_margin[p] - m.pair_gap[p]); }

@@ -96,6 +96,15 @@ namespace mpcr {
 #else
 #define STOP_AT(k)
 #endif
+// sub-stamps inside the constraint-rows phase (-DMPCR_PROFILE -DMPCR_PROFILE_ROWS,
+// single-arm kernels: slots 23..25 are the dual-arm polyhedron manifold's):
+// 23 head, 24 equality / limit Jacobians, 25 contact Jacobians; the row
+// parameters are then what is left in slot 8
+#if defined(MPCR_PROFILE) && defined(MPCR_PROFILE_ROWS)
+#define ROWS_STAMP(i) STAMP(i)
+#else
+#define ROWS_STAMP(i)
+#endif
 
 // ---------------------------------------------------------------------------
 // wave helpers
@@ -125,18 +134,25 @@ __device__ __forceinline__ const MPCR_GMEM DevModel* uniform_model(const DevMode
 }
 
 // MPCR_STEP_TABLE: which phases of the single-arm kernels read the step table
-// (bit 0 kinematics, 1 motion subspaces, 2 constraint rows); 7 is the shipped
-// build, the others attribute a change in results or time
+// (bit 0 kinematics, 1 motion subspaces, 2 constraint rows, 3 the load
+// records: one-level batched loads in place of dependent chains -- rows
+// phase, mass matrix, collision cull, narrow_lane's head, emit_contacts); 15
+// is the shipped build, the others attribute a change in results or time
 #ifndef MPCR_STEP_TABLE
-#define MPCR_STEP_TABLE 7
+#define MPCR_STEP_TABLE 15
 #endif
 template <class S> constexpr bool kStepKin = !S::WIDE && (MPCR_STEP_TABLE & 1) != 0;
 template <class S> constexpr bool kStepDof = !S::WIDE && (MPCR_STEP_TABLE & 2) != 0;
 template <class S> constexpr bool kStepRow = !S::WIDE && (MPCR_STEP_TABLE & 4) != 0;
+template <class S> constexpr bool kStepLoad = !S::WIDE && (MPCR_STEP_TABLE & 8) != 0;
 // The step table (step_table.h) behind the device model, and quad q (16
 // bytes: one dwordx4 load) of one of its records.  Single-arm kernels only.
 __device__ __forceinline__ const StepTable* step_table(const DevModel* m) {
   return reinterpret_cast<const StepTable*>(m + 1);
+}
+// ... and the load records behind the table
+__device__ __forceinline__ const StepRecords* step_records(const DevModel* m) {
+  return reinterpret_cast<const StepRecords*>(step_table(m) + 1);
 }
 template <class R>
 __device__ __forceinline__ float4 recq(const R& r, int q) {
@@ -1729,14 +1745,25 @@ void poly_manifold_wave(const DevModel* __restrict__ m_, const S& s, PS& ps, con
 template <class S>
 __device__ __forceinline__ int narrow_lane(const DevModel* __restrict__ m, const S& s, short* hints, int p, float dist[4],
                             float pos[4][3], float nrm[4][3], float* dbg = nullptr) {
-  const int g1 = m->pair_g1[p], g2 = m->pair_g2[p];
-  const int func = m->pair_func[p];
+  // single-arm kernels: function, geoms and both sizes from the pair's set-up
+  // record, three quads in one level (the model's arrays: pair -> geoms -> sizes)
+  [[maybe_unused]] float4 q0 = {0.f, 0.f, 0.f, 0.f};
+  [[maybe_unused]] float sz1[3], sz2[3];
+  if constexpr (kStepLoad<S>) {
+    const StepPairSetup& ps = step_records(m)->pair[p];
+    q0 = recq(ps, 0);
+    const float4 q2 = recq(ps, 2), q3 = recq(ps, 3);
+    sz1[0] = q2.x; sz1[1] = q2.y; sz1[2] = q2.z;
+    sz2[0] = q3.x; sz2[1] = q3.y; sz2[2] = q3.z;
+  }
+  const int g1 = kStepLoad<S> ? __float_as_int(q0.z) : m->pair_g1[p], g2 = kStepLoad<S> ? __float_as_int(q0.w) : m->pair_g2[p];
+  const int func = kStepLoad<S> ? __float_as_int(q0.x) : m->pair_func[p];
   const float* x1 = s.gxpos[g1];
   const float* x2 = s.gxpos[g2];
   const float* R1 = s.gxmat[g1];
   const float* R2 = s.gxmat[g2];
-  const float* s1 = m->geom_size[g1];
-  const float* s2 = m->geom_size[g2];
+  const float* s1 = kStepLoad<S> ? sz1 : m->geom_size[g1];
+  const float* s2 = kStepLoad<S> ? sz2 : m->geom_size[g2];
 #pragma unroll
   for (int k = 0; k < 4; k++) dist[k] = 1e30f;
   if (func == 0) {  // plane - capsule
@@ -2390,9 +2417,17 @@ __device__ __forceinline__ void emit_contacts(const DevModel* __restrict__ m, S&
                                               SlotHist<S>& sh, int k) {
   int act = 0;
   if (valid) {
-    const int sa = m->pair_slotadr[p];
+    // single-arm kernels: slot address, slot count and margin from the pair's
+    // set-up record, two quads fetched together
+    float4 q0 = {0.f, 0.f, 0.f, 0.f}, q1 = q0;
+    if constexpr (kStepLoad<S>) {
+      const StepPairSetup& ps = step_records(m)->pair[p];
+      q0 = recq(ps, 0);
+      q1 = recq(ps, 1);
+    }
+    const int sa = kStepLoad<S> ? __float_as_int(q0.y) : m->pair_slotadr[p];
     if (sa >= 0) {
-      const int ns = m->pair_ncon[p];
+      const int ns = kStepLoad<S> ? __float_as_int(q1.x) >> 16 : m->pair_ncon[p];
 #pragma unroll
       for (int c = 0; c < 4; c++) {
         if (c < ns) {
@@ -2415,7 +2450,7 @@ __device__ __forceinline__ void emit_contacts(const DevModel* __restrict__ m, S&
       }
     }
     if (!(m->disableflags & 16)) {
-      const float mg = m->pair_margin[p];
+      const float mg = kStepLoad<S> ? q1.w : m->pair_margin[p];
 #pragma unroll
       for (int c = 0; c < 4; c++) act += (c < nsl && dist[c] < mg) ? 1 : 0;
     }
@@ -3628,6 +3663,31 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
       const mfx4 P = mm16<2>([&](int i, int c) { return (i < nv && c < 6) ? s.fvec[i][c] : 0.f; },
                              [&](int c, int j) { return (j < nv && c < 6) ? s.cdof[j][c] : 0.f; }, z4, lane);
       const int j = mr;
+      if constexpr (kStepLoad<S>) {
+        // the four rows' chain masks, the column's and its armature (the
+        // diagonal's: i == j) loaded in one batch ahead of the branches (the
+        // arrays hold DX_NV >= 16 entries: rows past nv read zeros)
+        uint32_t cmi[4];
+#pragma unroll
+        for (int v = 0; v < 4; v++) cmi[v] = m->dof_chainmask[4 * kq + v];
+        const uint32_t cmj = m->dof_chainmask[j];
+        const float arm = m->dof_armature[j];
+#pragma unroll
+        for (int v = 0; v < 4; v++) {
+          const int i = 4 * kq + v;
+          if (i < nv && j < nv) {
+            if ((cmi[v] >> j) & 1u) {
+              const float x = i == j ? P[v] + arm : P[v];
+              m_set(i, j, x);
+              m_set(j, i, x);
+            } else if (!((cmj >> i) & 1u)) {
+              m_set(i, j, 0.f);
+            }
+          } else {
+            m_set(i, j, i == j ? 1.f : 0.f);
+          }
+        }
+      } else {
 #pragma unroll
       for (int v = 0; v < 4; v++) {
         const int i = 4 * kq + v;
@@ -3642,6 +3702,7 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
         } else {
           m_set(i, j, i == j ? 1.f : 0.f);
         }
+      }
       }
       const uint32_t sub = mr < nv ? m->dof_submask[mr] : 0u;
       const mfx4 fb = mm16<4>([&](int, int b) { return ((sub >> b) & 1u) ? 1.f : 0.f; },
@@ -3770,9 +3831,33 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
     for (int k = k_lo; k * WAVE < p_hi; k++) {
       const int p = lane + k * WAVE;
       const bool valid = p < m->npair;
-      const int func = valid ? m->pair_func[p] : -1;
+      // single-arm kernels: the pair's set-up record (function, slot address,
+      // geoms | geom types, bounding radii, margin), two quads fetched
+      // together in place of the chain pair -> geoms -> types / radii
+      float4 ps0 = {0.f, 0.f, 0.f, 0.f}, ps1 = ps0;
+      if constexpr (kStepLoad<S>) {
+        if (valid) {
+          const StepPairSetup& ps = step_records(m)->pair[p];
+          ps0 = recq(ps, 0);
+          ps1 = recq(ps, 1);
+        }
+      }
+      const int func = valid ? (kStepLoad<S> ? __float_as_int(ps0.x) : m->pair_func[p]) : -1;
       const bool defer = S::WIDE && func >= 9;  // general convex: the list
       bool run = valid && (defer ? do_list : do_narrow);
+      if constexpr (kStepLoad<S>) {
+        if (run && __float_as_int(ps0.y) < 0) {
+          const int g1 = __float_as_int(ps0.z), g2 = __float_as_int(ps0.w);
+          const float dx = s.gxpos[g2][0] - s.gxpos[g1][0], dy = s.gxpos[g2][1] - s.gxpos[g1][1],
+                      dz = s.gxpos[g2][2] - s.gxpos[g1][2];
+          if ((__float_as_int(ps1.x) & 255) != 0) {
+            run = sqrtf(dx * dx + dy * dy + dz * dz) <= ps1.y + ps1.z + ps1.w;
+          } else {  // plane vs the other geom's bounding sphere
+            const float* R1 = s.gxmat[g1];
+            run = R1[2] * dx + R1[5] * dy + R1[8] * dz <= ps1.z + ps1.w;
+          }
+        }
+      } else
       if (run && m->pair_slotadr[p] < 0) {
         const int g1 = m->pair_g1[p], g2 = m->pair_g2[p];
         const float dx = s.gxpos[g2][0] - s.gxpos[g1][0], dy = s.gxpos[g2][1] - s.gxpos[g1][1],
@@ -4086,6 +4171,15 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
       }
       const bool ell = S::WIDE && m->cone == 1;
       int ncr = 0;
+      // single-arm kernels: quad 3 of the contact's pair row (StepPairJ), one
+      // load for the row count here and the tree test below
+      float4 pj = {0.f, 0.f, 0.f, 0.f};
+      if constexpr (kStepLoad<S>) {
+        if (lane < ncon) {
+          pj = recq(step_table(m)->row[ST_ROW_PAIR + s.con_pair[lane]], 3);
+          ncr = (__float_as_int(pj.z) >> 16) & 1 ? 1 : 4;
+        }
+      } else
       if (lane < ncon) ncr = m->pair_condim[s.con_pair[lane]] == 1 ? 1 : (ell ? 3 : 4);
       int ncrow;
       const int con_pre = wscan_excl(ncr, ncrow);
@@ -4126,6 +4220,11 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
       }
       {
         bool cross = false;
+        if constexpr (kStepLoad<S>) {
+          const int tr = __float_as_int(pj.z);
+          cross = lane < keep_con && __float_as_int(pj.x) != 0 && __float_as_int(pj.y) != 0 &&
+                  (tr & 255) != ((tr >> 8) & 255);
+        } else
         if (lane < keep_con) {
           const int4 ji = m->pair_jinfo[s.con_pair[lane]];
           cross = ji.x != 0 && ji.y != 0 && ji.z != ji.w;
@@ -4134,8 +4233,35 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
       }
       if (lane == 0) s.nefc = nefc;
       sync();
+      ROWS_STAMP(23);
       // Jacobian entries of equality/limit rows: (row, dof)
       const int nsimple = neq + nlim + ntr;
+      if constexpr (kStepLoad<S>) {
+        // single-arm kernels (equality and limit rows only): the equality's
+        // record (StepEq) and the joint row's dof address, both fetched ahead
+        // of the branch on the row's kind -- one wait per pass (a row of the
+        // other kind reads a record it does not use: the index is masked into
+        // the array)
+        static_assert((ST_NEQ & (ST_NEQ - 1)) == 0 && (ST_NJ & (ST_NJ - 1)) == 0, "the masks below need powers of two");
+        for (int idx = lane + rl0; idx < nsimple * NVW; idx += rls) {
+          const int r = idx >> S::LOG_NVW, i = idx & (NVW - 1);
+          const int src = s.efc_src[r], kind = src >> 24, id = (src >> 4) & 0xfffff, side = src & 15;
+          const StepEq& eq = step_records(m)->eq[id & (ST_NEQ - 1)];
+          const float4 e0 = recq(eq, 0), e1 = recq(eq, 1), e2 = recq(eq, 2);
+          const int ldof = step_table(m)->row[ST_ROW_JNT + (id & (ST_NJ - 1))].dofadr;
+          float v = 0.f;
+          if (kind == 1) {
+            if (i == __float_as_int(e0.y)) v += 1.f;
+            if (__float_as_int(e0.z) >= 0 && i == __float_as_int(e0.w)) {
+              const float dif = s.qpos[__float_as_int(e0.z)] - e1.y;
+              v -= e1.w + dif * (2.f * e2.x + dif * (3.f * e2.y + dif * 4.f * e2.z));
+            }
+          } else if (i == ldof) {
+            v = side == 0 ? 1.f : -1.f;
+          }
+          jstore(s, gx, r, i, v);
+        }
+      } else
       for (int idx = lane + rl0; idx < nsimple * NVW; idx += rls) {
         const int r = idx >> S::LOG_NVW, i = idx & (NVW - 1);
         const int src = s.efc_src[r], kind = src >> 24, id = (src >> 4) & 0xfffff, side = src & 15;
@@ -4190,11 +4316,25 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
         }
         jstore(s, gx, r, i, v);
       }
+      ROWS_STAMP(24);
       // contact Jacobians: (contact, dof) -> J_n +- mu J_t rows
       for (int idx = lane + rl0; idx < keep_con * NVW; idx += rls) {
         const int c = idx >> S::LOG_NVW, i = idx & (NVW - 1);
         const int p = s.con_pair[c];
-        const int4 ji = m->pair_jinfo[p];  // one load: both bodies' dof masks and trees
+        // one load: both bodies' dof masks and trees (single-arm kernels: with
+        // the friction and the condim-1 bit, quad 3 of the pair's row)
+        int4 ji;
+        float muq = 0.f;
+        bool condim1 = false;
+        if constexpr (kStepLoad<S>) {
+          const float4 q3 = recq(step_table(m)->row[ST_ROW_PAIR + p], 3);
+          const int tr = __float_as_int(q3.z);
+          ji = make_int4(__float_as_int(q3.x), __float_as_int(q3.y), tr & 255, (tr >> 8) & 255);
+          condim1 = (tr >> 16) & 1;
+          muq = q3.w;
+        } else {
+          ji = m->pair_jinfo[p];
+        }
         float jd[3] = {0.f, 0.f, 0.f};
         if (i < nv) {
           const float* cd = s.cdof[i];
@@ -4220,14 +4360,14 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
         }
         const float jn = f[0] * jd[0] + f[1] * jd[1] + f[2] * jd[2];
         const int off = s.con_row[c];
-        if (m->pair_condim[p] == 1) {
+        if (kStepLoad<S> ? condim1 : m->pair_condim[p] == 1) {
           jstore(s, gx, off, i, jn);
         } else if (S::WIDE && m->cone == 1) {  // elliptic: J_n, J_t1, J_t2
           jstore(s, gx, off + 0, i, jn);
           jstore(s, gx, off + 1, i, f[3] * jd[0] + f[4] * jd[1] + f[5] * jd[2]);
           jstore(s, gx, off + 2, i, f[6] * jd[0] + f[7] * jd[1] + f[8] * jd[2]);
         } else {
-          const float mu = m->pair_friction[p];
+          const float mu = kStepLoad<S> ? muq : m->pair_friction[p];
           const float jt1 = f[3] * jd[0] + f[4] * jd[1] + f[5] * jd[2];
           const float jt2 = f[6] * jd[0] + f[7] * jd[1] + f[8] * jd[2];
           jstore(s, gx, off + 0, i, jn + mu * jt1);
@@ -4240,6 +4380,7 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
       // and with rows_j the other wave's rows)
       if (rows_j) block_sync();
       else sync();
+      ROWS_STAMP(25);
       // row parameters: vel, impedance, D, aref
       if constexpr (kStepRow<S>) {
         // single-arm kernels: the constraint source's record of the step
@@ -4252,6 +4393,32 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
           const StepTable* st = step_table(m);
           float pos;
           int ri;
+          float4 a0, a1, a2;
+          if constexpr (kStepLoad<S>) {
+            // the row record's four quads issued together ahead of the branch
+            // on the kind (the record's index needs only the source and the
+            // contact's pair); an equality adds its own record (StepEq) in
+            // one level behind them
+            ri = kind == 1 ? ST_ROW_EQ + id : (kind == 2 ? ST_ROW_JNT + id : ST_ROW_PAIR + s.con_pair[kind == 3 ? id : 0]);
+            a0 = recq(st->row[ri], 0); a1 = recq(st->row[ri], 1); a2 = recq(st->row[ri], 2);
+            const float4 j3 = recq(st->row[ri], 3);
+            if (kind == 1) {
+              const StepEq& eq = step_records(m)->eq[id & (ST_NEQ - 1)];
+              const float4 e0 = recq(eq, 0), e1 = recq(eq, 1), e2 = recq(eq, 2);
+              const float q1 = s.qpos[__float_as_int(e0.x)] - e1.x;
+              if (__float_as_int(e0.z) >= 0) {
+                const float dif = s.qpos[__float_as_int(e0.z)] - e1.y;
+                pos = q1 - (e1.z + dif * (e1.w + dif * (e2.x + dif * (e2.y + dif * e2.z))));
+              } else {
+                pos = q1 - e1.z;
+              }
+            } else if (kind == 2) {
+              const float q = s.qpos[__float_as_int(j3.z)];
+              pos = side == 0 ? q - j3.x : j3.y - q;
+            } else {
+              pos = s.con_dist[id];
+            }
+          } else {
           if (kind == 1) {
             const int j1 = m->eq_j1[id], j2 = m->eq_j2[id];
             const float* c = m->eq_data[id];
@@ -4272,7 +4439,8 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
             ri = ST_ROW_PAIR + s.con_pair[id];
             pos = s.con_dist[id];
           }
-          const float4 a0 = recq(st->row[ri], 0), a1 = recq(st->row[ri], 1), a2 = recq(st->row[ri], 2);
+          a0 = recq(st->row[ri], 0); a1 = recq(st->row[ri], 1); a2 = recq(st->row[ri], 2);
+          }
           const float vel = jdot(s, gx, r, s.qvel);
           const float dpos = pos - a2.x;
           const float x = fabsf(dpos * a0.z);

@@ -18,6 +18,9 @@
 // model_frames() (model_frames.h), which the device model's builder
 // (dev_model.h build_dev_model) reads too, as it does the row values both
 // hold; tests/test_dev_model.py compares the two results on the CPU.
+// Behind the table, in the same allocation, lie the load records
+// (StepRecords, build_step_records(); tests/test_step_records.py): model
+// constants gathered so that a lane reaches them in one level of loads.
 //
 // Device indices as in dev_model.h build_dev_model: moving bodies (not welded
 // to the world) in model order, pairs / joints / equalities by their model
@@ -27,6 +30,7 @@
 // parity -- DESIGN.md, "Measured and not kept".)
 #pragma once
 #include <math.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <string.h>
 
@@ -77,11 +81,45 @@ struct alignas(16) StepRow {
   int32_t qposadr, dofadr;        // kernel; it fills the quad and the tests compare it with the device model's)
 };
 
+// quad 3 of a pair's StepRow (in place of range / qposadr / dofadr, which
+// only joint rows have): the contact Jacobian's constants
+struct alignas(16) StepPairJ {
+  uint32_t mask1, mask2;  // dof masks of the two geoms' bodies (static body: 0)
+  int32_t trees;          // tree of body 1 | tree of body 2 << 8 (static body: 0) | frictionless (condim 1) << 16
+  float mu;               // friction
+};
+
 struct alignas(16) StepTable {
   int32_t flags, nbody, pad[2];  // nbody: for the tests, not read by the kernel
   StepBody body[ST_NB];
   StepDof dof[ST_NV];
   StepRow row[ST_NROW];
+};
+
+// The load records: model constants a lane otherwise reaches through a chain
+// of dependent loads (index -> index -> value), gathered so that the lane
+// fetches them in one level, the loads issued together and waited for once.
+// A second struct directly behind the table in the same allocation,
+// (const StepRecords*)(table + 1), with its own builder: the table's layout
+// and build_step_table()'s signature stay.
+// collision set-up, by pair (64 B): the cull, the narrow phase's head and
+// the contact emission
+struct alignas(16) StepPairSetup {
+  int32_t func, slotadr, g1, g2;  // narrow-phase function, first masked slot (-1: none), collision geoms
+  int32_t types;                  // geom type 1 | geom type 2 << 8 | contact slots << 16
+  float rbound1, rbound2, margin; // bounding radii, margin - gap
+  float size1[3], pad0;           // the geoms' sizes
+  float size2[3], pad1;
+};
+// joint equality, by equality (48 B)
+struct alignas(16) StepEq {
+  int32_t qadr1, dadr1, qadr2, dadr2;  // the joints' qpos and dof addresses; no second joint: -1, -1
+  float qpos0_1, qpos0_2, c0, c1;      // reference positions (no second joint: 0), polynomial coefficients
+  float c2, c3, c4, pad;
+};
+struct alignas(16) StepRecords {
+  StepPairSetup pair[ST_NP];
+  StepEq eq[ST_NEQ];
 };
 
 namespace step_detail {
@@ -178,7 +216,16 @@ inline int build_step_table(const mpcr_model_t& m, StepTable& t) {
     r.margin = pair_margin_f(m, p);
     r.diag = (float)(pair_frictionless(m, p) ? invw : invw * (1.0 + mu * mu));
     if (pair_frictionless(m, p)) r.flags |= ST_CONDIM1;
-    r.qposadr = r.dofadr = -1;
+    // quad 3 of a pair row (StepPairJ): with ST_CONDIM1 all the rows phase
+    // reads by pair
+    StepPairJ q;
+    const int b1 = f.dmap[m.geom_bodyid[m.pair_geom1[p]]], b2 = f.dmap[m.geom_bodyid[m.pair_geom2[p]]];
+    q.mask1 = b1 >= 0 ? m.body_dofmask[f.id[b1]] : 0u;
+    q.mask2 = b2 >= 0 ? m.body_dofmask[f.id[b2]] : 0u;
+    q.trees = (b1 >= 0 ? f.tree[b1] : 0) | (b2 >= 0 ? f.tree[b2] : 0) << 8 | (pair_frictionless(m, p) ? 1 << 16 : 0);
+    q.mu = (float)m.pair_friction[p];
+    static_assert(sizeof(q) == 16 && offsetof(StepRow, range) == 48 && sizeof(StepRow) == 64, "quad 3");
+    memcpy(reinterpret_cast<char*>(&r) + 48, &q, sizeof(q));
   }
   for (int j = 0; j < m.njnt; j++) {
     StepRow& r = t.row[ST_ROW_JNT + j];
@@ -197,6 +244,47 @@ inline int build_step_table(const mpcr_model_t& m, StepTable& t) {
     r.margin = 0.f;
     r.diag = eq_diag_f(m, e);
     r.qposadr = r.dofadr = -1;
+  }
+  return 0;
+}
+
+// Fills r from the model: every value by the expression build_dev_model
+// (dev_model.h) has for the array the record replaces.  Returns 0, or -1 when
+// the model exceeds the capacities.
+inline int build_step_records(const mpcr_model_t& m, StepRecords& r) {
+  memset(&r, 0, sizeof(r));
+  if (m.npair > ST_NP || m.neq > ST_NEQ || m.njnt > ST_NJ || m.ngeom > MPCR_MAX_GEOM) return -1;
+  int gmap[MPCR_MAX_GEOM];
+  pair_geom_map(m, gmap);
+  for (int p = 0; p < m.npair; p++) {
+    StepPairSetup& s = r.pair[p];
+    const int g1 = m.pair_geom1[p], g2 = m.pair_geom2[p];
+    s.func = m.pair_func[p];
+    s.slotadr = m.pair_slotadr[p];
+    s.g1 = gmap[g1];
+    s.g2 = gmap[g2];
+    s.types = (m.geom_type[g1] & 255) | (m.geom_type[g2] & 255) << 8 | m.pair_ncon[p] << 16;
+    s.rbound1 = (float)m.geom_rbound[g1];
+    s.rbound2 = (float)m.geom_rbound[g2];
+    s.margin = pair_margin_f(m, p);
+    for (int k = 0; k < 3; k++) { s.size1[k] = (float)m.geom_size[g1][k]; s.size2[k] = (float)m.geom_size[g2][k]; }
+  }
+  for (int e = 0; e < m.neq; e++) {
+    StepEq& q = r.eq[e];
+    q.qadr1 = q.dadr1 = q.qadr2 = q.dadr2 = -1;
+    if (m.eq_type[e] != MPCR_EQ_JOINT) continue;  // (connect: dual-arm kernels only)
+    const int j1 = m.eq_obj1[e], j2 = m.eq_obj2[e];
+    if (j1 < 0 || j1 >= m.njnt || j2 >= m.njnt) return -1;
+    q.qadr1 = m.jnt_qposadr[j1];
+    q.dadr1 = m.jnt_dofadr[j1];
+    q.qpos0_1 = (float)m.qpos0[m.jnt_qposadr[j1]];
+    if (j2 >= 0) {
+      q.qadr2 = m.jnt_qposadr[j2];
+      q.dadr2 = m.jnt_dofadr[j2];
+      q.qpos0_2 = (float)m.qpos0[m.jnt_qposadr[j2]];
+    }
+    q.c0 = (float)m.eq_data[e][0]; q.c1 = (float)m.eq_data[e][1]; q.c2 = (float)m.eq_data[e][2];
+    q.c3 = (float)m.eq_data[e][3]; q.c4 = (float)m.eq_data[e][4];
   }
   return 0;
 }

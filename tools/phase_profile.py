@@ -74,7 +74,13 @@ def main():
                 print(f"  {p:26s} {pw[i] / n / H:10.0f} cyc  {100 * pw[i] / tot:5.1f}%")
         sub = {23: "support vertices", 24: "cone face scan", 25: "SAT support queries", 26: "incident face + polygons",
                27: "clip", 28: "picks"}
-        if any(pw[i] for i in sub):  # inside the polyhedron manifold (wave level, atomics per stamp)
+        rows = {23: "head", 24: "equality / limit Jacobians", 25: "contact Jacobians", 8: "row parameters"}
+        if os.environ.get("ROWS"):  # a -DMPCR_PROFILE_ROWS build (single-arm): the rows phase's sub-stamps
+            for i, p in rows.items():
+                print(f"    rows: {p:24s} {pw[i] / n / H:10.0f} cyc")
+            print(f"    rows: {'all':24s} {sum(pw[i] for i in rows) / n / H:10.0f} cyc")
+            res["rows_sub"] = {p: pw[i] / n / H for i, p in rows.items()}
+        elif any(pw[i] for i in sub):  # inside the polyhedron manifold (wave level, atomics per stamp)
             for i, p in sub.items():
                 print(f"    poly: {p:24s} {pw[i] / n / H:10.0f} cyc")
         for i, p in COUNTS.items():
