@@ -114,6 +114,9 @@ int mpcr_model_from_blob(const void* blob, size_t nbytes, mpcr_model** out);
 int mpcr_model_load(const char* path, double timestep, mpcr_model** out);
 int mpcr_model_set_timestep(mpcr_model* m, double timestep);
 int mpcr_model_info(const mpcr_model* m, int* nq, int* nv, int* nslot, int* nctrl, int* npair);
+/* The model's actuators: their number, and (nullable) ctrlrange[nu][2] and
+   limited[nu] (1 where the control is clamped to its range). */
+int mpcr_model_actuators(const mpcr_model* m, int* nu, double* ctrlrange, int* limited);
 void mpcr_model_free(mpcr_model* m);
 /* The support start table an engine builds for m's convex hulls (model
    format v9 dropped it from the blob; dev_model.h hull_start_table): R x R
@@ -254,6 +257,29 @@ int mpcr_rollout_cost_state(mpcr_engine* e, const float* input, int layout, int 
                             float* cost4, float* theta, float* thetadot, uint64_t* best_keys, int index_base,
                             int* status, int flags, void* stream);
 
+/* mpcr_rollout_cost_state with the actuator controls as an input of the call
+   (a backward-compatible addition; mpcr_rollout_cost_state is this call with
+   ctrl = NULL).  ctrl (nullable): device memory, nu floats in actuator order
+   (mpcr_model_actuators) per block.  Step t of problem p reads the block at
+   ctrl + p ctrl_stride + t ctrl_step_stride (strides in floats):
+   ctrl_stride = 0 is one block for every problem, ctrl_step_stride = 0 one
+   block for the whole horizon; a non-zero step stride is at least nu, and a
+   non-zero ctrl_stride holds what a problem reads (nu floats, or the H rows
+   of its schedule: ctrl_step_stride (H - 1) + nu).  Each value is clamped to
+   the actuator's ctrlrange where the model limits it, as the model's own
+   control is when an engine is built.  Read when the kernel runs
+   (graph-capturable; a replay sees new contents), never written.  Per
+   problem, not per candidate.  ctrl = NULL keeps the model's own controls.
+   MPCR_EINVAL: a model without actuators, host memory, a stride out of range.
+   MPCR_EMODEL: an implicitfast model with a velocity-dependent actuator gain
+   (gaintype affine, gainprm[2] != 0), whose implicit matrix is derived from
+   the controls once, when the engine is built. */
+int mpcr_rollout_cost_ctrl(mpcr_engine* e, const float* input, int layout, int nprob, int n_per,
+                           const float* params, const float* start, int start_stride, float* final_state,
+                           const float* ctrl, int ctrl_stride, int ctrl_step_stride, float* cost4, float* theta,
+                           float* thetadot, uint64_t* best_keys, int index_base, int* status, int flags,
+                           void* stream);
+
 /* Closed-loop plant: one environment of the model, stepped by the rollout
    kernel (fp32 state resident on the device).  Created at the template
    state (qpos_init, qvel_init, zero warm start). */
@@ -276,6 +302,10 @@ int mpcr_plant_step(mpcr_plant* p, const double* qvel_ctrl, int commit, void* st
    (mpcr_state_layout) to d_dst on stream: a planner's start state
    (mpcr_rollout_cost_state) without a host round trip. */
 int mpcr_plant_copy_state(mpcr_plant* p, float* d_dst, void* stream);
+/* The plant's actuator controls from now on: ctrl[nu], clamped to ctrlrange
+   where the model limits it; NULL restores the model's own.  Blocks until
+   done.  Errors as mpcr_rollout_cost_ctrl's for the model. */
+int mpcr_plant_set_ctrl(mpcr_plant* p, const double* ctrl);
 
 /* argmin over cost[i*stride] with NaN-first / first-index semantics
    (jnp.argmin).  key_out (device, nullable) receives the packed key. */

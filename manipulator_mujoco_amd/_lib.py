@@ -38,6 +38,9 @@ EXPORTS += _MULTI
 # planning from a state, likewise: absent from an older build
 _STATE = ("mpcr_state_layout", "mpcr_rollout_cost_state", "mpcr_plant_copy_state")
 EXPORTS += _STATE
+# actuator controls as a call input, likewise
+_CTRL = ("mpcr_rollout_cost_ctrl", "mpcr_plant_set_ctrl", "mpcr_model_actuators")
+EXPORTS += _CTRL
 # the wave-reduction self-test, likewise
 _SELFTEST = ("mpcr_selftest_reduce",)
 EXPORTS += _SELFTEST
@@ -136,11 +139,17 @@ def load():
     for name, at in state.items():
         if have_state:
             getattr(lib, name).argtypes = at
+    have_ctrl = hasattr(lib, _CTRL[0])
+    if have_ctrl:
+        lib.mpcr_rollout_cost_ctrl.argtypes = [vp, vp, i, i, i, vp, vp, i, vp, vp, i, i, vp, vp, vp, vp, i, vp, i, vp]
+        lib.mpcr_plant_set_ctrl.argtypes = [vp, P(d)]
+        lib.mpcr_model_actuators.argtypes = [vp, P(i), P(d), P(i)]
     have_selftest = hasattr(lib, _SELFTEST[0])
     if have_selftest:
         lib.mpcr_selftest_reduce.argtypes = [i, vp, i, vp]
     for name in EXPORTS + ("mpcr_rollout_trace", "mpcr_plant_step_debug", "mpcr_plant_dbg_size"):
         if (name in _MULTI and not have_multi) or (name in _STATE and not have_state) or (
+                name in _CTRL and not have_ctrl) or (
                 name in _SELFTEST and not have_selftest):
             continue
         if name not in _VOID:

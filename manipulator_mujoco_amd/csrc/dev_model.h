@@ -212,6 +212,48 @@ inline bool needs_wide(const mpcr_model_t& m, const DevModel& d) {
   return false;
 }
 
+// An actuator's control as the kernel multiplies it into the gain: clamped to
+// the model's range where it limits the control, rounded to fp32 (the kernel
+// clamps a call's control block to DevModel::act_ctrlrange the same way).
+inline float clamped_ctrl(const mpcr_model_t& m, int a, double ctrl) {
+  if (m.act_ctrllimited[a]) ctrl = std::fmin(std::fmax(ctrl, m.act_ctrlrange[a][0]), m.act_ctrlrange[a][1]);
+  return (float)ctrl;
+}
+
+// d force / d vel of actuator a through its gain, per unit of control: what
+// of implicitfast's D depends on the control.
+inline double act_gain_dvel(const mpcr_model_t& m, int a) {
+  return m.act_gaintype[a] == MPCR_GAIN_AFFINE ? m.act_gainprm[a][2] : 0.0;
+}
+
+// implicitfast: D = -qDeriv = damping + sum_a (-dforce/dvel) m m^T, nv x nv
+// row-major in fp64 (the device model rounds it), at the clamped controls
+// ctrl[nu].  Built once per engine on the host.
+inline void implicit_D(const mpcr_model_t& m, const float* ctrl, std::vector<double>& D) {
+  const bool no_passive = m.disableflags & MPCR_DSBL_PASSIVE;
+  D.assign((size_t)m.nv * m.nv, 0.0);
+  for (int i = 0; i < m.nv; i++) D[(size_t)i * m.nv + i] = no_passive ? 0.0 : m.dof_damping[i];
+  for (int a = 0; a < m.nu; a++) {
+    double dv = 0;
+    if (m.act_biastype[a] == MPCR_BIAS_AFFINE) dv += m.act_biasprm[a][2];
+    if (m.act_gaintype[a] == MPCR_GAIN_AFFINE) dv += act_gain_dvel(m, a) * (double)ctrl[a];
+    for (int k = 0; k < m.act_ntrn[a]; k++)
+      for (int l = 0; l < m.act_ntrn[a]; l++)
+        D[(size_t)m.act_dof[a][k] * m.nv + m.act_dof[a][l]] -= dv * m.act_moment[a][k] * m.act_moment[a][l];
+  }
+}
+
+// Whether the engine's D (above) would change with the controls: an
+// implicitfast model with a velocity-dependent gain.  Such a model cannot take
+// its controls as a call input or have them replaced in a plant, because D is
+// not rebuilt (no bundled model is one).
+inline bool implicit_D_reads_ctrl(const mpcr_model_t& m) {
+  if (m.integrator != MPCR_INT_IMPLICITFAST) return false;
+  for (int a = 0; a < m.nu; a++)
+    if (act_gain_dvel(m, a) != 0.0) return true;
+  return false;
+}
+
 // Fills d (its table pointers stay null: mpcr_engine_create sets them to the
 // uploaded DevTables) or returns the refusal's code with its message in err.
 // lutadr[ngeom]: hull_start_table's geom_adr.
@@ -535,7 +577,7 @@ inline int build_dev_model(const mpcr_model_t& m, const int32_t* lutadr, const D
       d.dof_actfrc[i][1] = (float)m.jnt_actfrcrange[j][1];
     }
   }
-  // actuators (ctrl constant: clamped once here)
+  // actuators (the model's own control: clamped once here)
   if (m.nu > DX_NU) return dev_fail(err, MPCR_EMODEL, "%d actuators > %d", m.nu, DX_NU);
   d.nu = m.nu;
   for (int a = 0; a < m.nu; a++) {
@@ -550,28 +592,22 @@ inline int build_dev_model(const mpcr_model_t& m, const int32_t* lutadr, const D
       d.dof_actm[v][d.dof_actn[v]] = (float)m.act_moment[a][k];
       d.dof_actn[v]++;
     }
-    double ctrl = m.act_ctrl[a];
-    if (m.act_ctrllimited[a]) ctrl = std::fmin(std::fmax(ctrl, m.act_ctrlrange[a][0]), m.act_ctrlrange[a][1]);
     d.act_gaffine[a] = m.act_gaintype[a] == MPCR_GAIN_AFFINE;
     d.act_baffine[a] = m.act_biastype[a] == MPCR_BIAS_AFFINE;
     for (int k = 0; k < 3; k++) { d.act_gain[a][k] = (float)m.act_gainprm[a][k]; d.act_bias[a][k] = (float)m.act_biasprm[a][k]; }
-    d.act_gain[a][3] = (float)ctrl;
+    d.act_gain[a][3] = clamped_ctrl(m, a, m.act_ctrl[a]);
+    d.act_ctrlrange[a][0] = m.act_ctrllimited[a] ? (float)m.act_ctrlrange[a][0] : -3e38f;
+    d.act_ctrlrange[a][1] = m.act_ctrllimited[a] ? (float)m.act_ctrlrange[a][1] : 3e38f;
     d.act_frc[a][0] = m.act_forcelimited[a] ? (float)m.act_forcerange[a][0] : -3e38f;
     d.act_frc[a][1] = m.act_forcelimited[a] ? (float)m.act_forcerange[a][1] : 3e38f;
   }
   // implicitfast: D = -qDeriv = damping + sum_a (-dforce/dvel) m m^T (fp64, then rounded)
   d.integrator = m.integrator;
   if (m.integrator == MPCR_INT_IMPLICITFAST) {
-    std::vector<double> D((size_t)m.nv * m.nv, 0.0);
-    for (int i = 0; i < m.nv; i++) D[(size_t)i * m.nv + i] = no_passive ? 0.0 : m.dof_damping[i];
-    for (int a = 0; a < m.nu; a++) {
-      double dv = 0;
-      if (m.act_biastype[a] == MPCR_BIAS_AFFINE) dv += m.act_biasprm[a][2];
-      if (m.act_gaintype[a] == MPCR_GAIN_AFFINE) dv += m.act_gainprm[a][2] * (double)d.act_gain[a][3];
-      for (int k = 0; k < m.act_ntrn[a]; k++)
-        for (int l = 0; l < m.act_ntrn[a]; l++)
-          D[(size_t)m.act_dof[a][k] * m.nv + m.act_dof[a][l]] -= dv * m.act_moment[a][k] * m.act_moment[a][l];
-    }
+    float ctrl[DX_NU];
+    for (int a = 0; a < m.nu; a++) ctrl[a] = d.act_gain[a][3];
+    std::vector<double> D;
+    implicit_D(m, ctrl, D);
     for (int i = 0; i < m.nv; i++)
       for (int j = 0; j < m.nv; j++) d.impl_D[i][j] = (float)D[(size_t)i * m.nv + j];
     d.impl_cross = 0;  // a transmission across trees keeps the implicit solve dense

@@ -8,6 +8,7 @@
 #include <atomic>
 #include <cmath>
 #include <cstdarg>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -310,6 +311,16 @@ extern "C" int mpcr_model_info(const mpcr_model* m, int* nq, int* nv, int* nslot
   return MPCR_OK;
 }
 
+extern "C" int mpcr_model_actuators(const mpcr_model* m, int* nu, double* ctrlrange, int* limited) {
+  if (!m) return fail(MPCR_EINVAL, "null model");
+  if (nu) *nu = m->m.nu;
+  for (int a = 0; a < m->m.nu; a++) {
+    if (ctrlrange) { ctrlrange[2 * a] = m->m.act_ctrlrange[a][0]; ctrlrange[2 * a + 1] = m->m.act_ctrlrange[a][1]; }
+    if (limited) limited[a] = m->m.act_ctrllimited[a] != 0;
+  }
+  return MPCR_OK;
+}
+
 extern "C" void mpcr_model_free(mpcr_model* m) { delete m; }
 
 // the support start table's scramble seed (dev_model.h hull_start_table; the
@@ -490,6 +501,9 @@ struct Launch {
   const float* start = nullptr;
   float* final_state = nullptr;
   int start_stride = 0;
+  // the call's control block per problem and, optionally, per step (strides in floats; StateArgs)
+  const float* ctrl = nullptr;
+  int ctrl_stride = 0, ctrl_step_stride = 0;
 };
 
 // the kernel's arguments for launch l of engine e (the one place they are filled)
@@ -531,9 +545,10 @@ static int rollout_args(const mpcr_engine* e, const Launch& l, RolloutArgs& a) {
   // bytes (rollout.h; null pointers when it has no state blocks) and never
   // parameter values, so has_state() cannot read those as pointers
   if (l.dpar) {
-    set_state_args(a, StateArgs{l.start, l.final_state, l.start_stride});
+    set_state_args(a, StateArgs{l.start, l.final_state, l.start_stride, l.ctrl_stride, l.ctrl_step_stride, l.ctrl});
   } else {
-    if (l.start || l.final_state) return fail(MPCR_EINVAL, "state blocks need a device parameter block");
+    if (l.start || l.final_state || l.ctrl)
+      return fail(MPCR_EINVAL, "state and control blocks need a device parameter block");
     std::memcpy(a.par, l.par, sizeof(a.par));
   }
   return MPCR_OK;
@@ -635,7 +650,8 @@ static int check_multi(int nprob, int n_per, int max_n) {
 static int rollout_dp(mpcr_engine* e, const float* input, int layout, int nprob, int n_per, const float* params,
                       float* cost4, float* theta, float* thetadot, uint64_t* best_keys, int index_base, int* status,
                       int flags, void* stream, const float* start = nullptr, int start_stride = 0,
-                      float* final_state = nullptr) {
+                      float* final_state = nullptr, const float* ctrl = nullptr, int ctrl_stride = 0,
+                      int ctrl_step_stride = 0) {
   if (layout != MPCR_LAYOUT_XI && layout != MPCR_LAYOUT_THETADOT) return fail(MPCR_EINVAL, "bad layout %d", layout);
   if (n_per == 0) return MPCR_OK;  // an empty batch: the buffers may be null
   if (!input || !params || !cost4) return fail(MPCR_EINVAL, "null argument");
@@ -648,6 +664,7 @@ static int rollout_dp(mpcr_engine* e, const float* input, int layout, int nprob,
   l.key = reinterpret_cast<unsigned long long*>(best_keys); l.status = status;
   l.reset_key = (flags & MPCR_F_RESET_BEST) != 0;
   l.start = start; l.start_stride = start_stride; l.final_state = final_state;
+  l.ctrl = ctrl; l.ctrl_stride = ctrl_stride; l.ctrl_step_stride = ctrl_step_stride;
   int rc = launch_rollout(e, l, st);
   if (rc) return rc;
   if (flags & MPCR_F_SYNC) HIPCHK(hipStreamSynchronize(st));
@@ -682,18 +699,58 @@ extern "C" int mpcr_state_layout(int* qpos, int* qvel, int* qacc_warmstart, int*
   return ST_N;
 }
 
-extern "C" int mpcr_rollout_cost_state(mpcr_engine* e, const float* input, int layout, int nprob, int n_per,
-                                       const float* params, const float* start, int start_stride, float* final_state,
-                                       float* cost4, float* theta, float* thetadot, uint64_t* best_keys,
-                                       int index_base, int* status, int flags, void* stream) {
+// Whether a model's controls can be replaced after its engine was built
+// (a call's control block, mpcr_plant_set_ctrl): it has actuators, and the
+// implicit integrator's D, built once, does not depend on them.
+static int check_ctrl_model(const mpcr_model_t& h) {
+  if (h.nu == 0) return fail(MPCR_EINVAL, "ctrl: the model has no actuators (nu = 0)");
+  if (implicit_D_reads_ctrl(h))
+    return fail(MPCR_EMODEL, "ctrl: an implicitfast model with a velocity-dependent actuator gain (gainprm[2] != 0) "
+                             "keeps the controls it was built with: its D is derived once, at engine creation");
+  return MPCR_OK;
+}
+
+extern "C" int mpcr_rollout_cost_ctrl(mpcr_engine* e, const float* input, int layout, int nprob, int n_per,
+                                      const float* params, const float* start, int start_stride, float* final_state,
+                                      const float* ctrl, int ctrl_stride, int ctrl_step_stride, float* cost4,
+                                      float* theta, float* thetadot, uint64_t* best_keys, int index_base, int* status,
+                                      int flags, void* stream) {
   if (!e) return fail(MPCR_EINVAL, "null argument");
   if (!(flags & MPCR_F_DEVICE_PTRS)) return fail(MPCR_EINVAL, "mpcr_rollout_cost_state takes device pointers");
   if (int rc = check_multi(nprob, n_per, e->max_n)) return rc;
   if (start && start_stride != 0 && start_stride < ST_N)
     return fail(MPCR_EINVAL, "start_stride=%d: 0 (one block for every problem) or at least the block's %d floats",
                 start_stride, (int)ST_N);
+  if (ctrl) {
+    const int nu = e->host.nu;
+    if (int rc = check_ctrl_model(e->host)) return rc;
+    if (ctrl_step_stride != 0 && ctrl_step_stride < nu)
+      return fail(MPCR_EINVAL, "ctrl_step_stride=%d: 0 (constant over the horizon) or at least nu=%d floats",
+                  ctrl_step_stride, nu);
+    const long long rows = ctrl_step_stride ? (long long)ctrl_step_stride * (e->H - 1) + nu : nu;  // floats one problem reads
+    if (ctrl_stride != 0 && ctrl_stride < rows)
+      return fail(MPCR_EINVAL, "ctrl_stride=%d: 0 (one block for every problem) or at least the %lld floats a problem "
+                               "reads (nu=%d, ctrl_step_stride=%d, H=%d)",
+                  ctrl_stride, rows, nu, ctrl_step_stride, e->H);
+    // read by the kernel when it runs: it must be device memory on the engine's device
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, ctrl) != hipSuccess || at.type != hipMemoryTypeDevice ||
+        at.device != e->device) {
+      (void)hipGetLastError();
+      return fail(MPCR_EINVAL, "ctrl must be device memory on the engine's device %d", e->device);
+    }
+  }
   return rollout_dp(e, input, layout, nprob, n_per, params, cost4, theta, thetadot, best_keys, index_base, status,
-                    flags, stream, start, start ? start_stride : 0, final_state);
+                    flags, stream, start, start ? start_stride : 0, final_state, ctrl, ctrl ? ctrl_stride : 0,
+                    ctrl ? ctrl_step_stride : 0);
+}
+
+extern "C" int mpcr_rollout_cost_state(mpcr_engine* e, const float* input, int layout, int nprob, int n_per,
+                                       const float* params, const float* start, int start_stride, float* final_state,
+                                       float* cost4, float* theta, float* thetadot, uint64_t* best_keys,
+                                       int index_base, int* status, int flags, void* stream) {
+  return mpcr_rollout_cost_ctrl(e, input, layout, nprob, n_per, params, start, start_stride, final_state, nullptr, 0, 0,
+                                cost4, theta, thetadot, best_keys, index_base, status, flags, stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -784,6 +841,23 @@ extern "C" int mpcr_plant_copy_state(mpcr_plant* p, float* d_dst, void* stream) 
     return fail(MPCR_EINVAL, "d_dst must be device memory on the plant's device %d", p->e->device);
   }
   HIPCHK(hipMemcpyAsync(d_dst, p->d_state, sizeof(float) * ST_N, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return MPCR_OK;
+}
+
+// The plant's controls: clamped here as build_dev_model clamps the model's
+// own, written into the plant's engine's device copy of act_gain[a][3] (the
+// plant owns that engine, and runs the kernels that read the control there).
+// NULL: the model's own again.
+extern "C" int mpcr_plant_set_ctrl(mpcr_plant* p, const double* ctrl) {
+  if (!p) return fail(MPCR_EINVAL, "null plant");
+  mpcr_engine* e = p->e;
+  const mpcr_model_t& h = e->host;
+  if (int rc = check_ctrl_model(h)) return rc;
+  HIPCHK(hipSetDevice(e->device));
+  for (int a = 0; a < h.nu; a++) e->dev.act_gain[a][3] = clamped_ctrl(h, a, ctrl ? ctrl[a] : h.act_ctrl[a]);
+  static_assert(sizeof(e->dev.act_gain) == sizeof(float) * 4 * DX_NU, "act_gain rows");
+  HIPCHK(hipMemcpy(reinterpret_cast<char*>(e->d_model) + offsetof(DevModel, act_gain), e->dev.act_gain,
+                   sizeof(e->dev.act_gain), hipMemcpyHostToDevice));
   return MPCR_OK;
 }
 

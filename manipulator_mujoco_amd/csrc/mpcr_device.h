@@ -196,6 +196,12 @@ struct DevModel {
   int ten_body[DX_NTEN][2], ten_limited[DX_NTEN];
   float ten_pos[DX_NTEN][2][4];
   float ten_range[DX_NTEN][2], ten_solref[DX_NTEN][2], ten_solimp[DX_NTEN][5], ten_margin[DX_NTEN], ten_invw[DX_NTEN];
+
+  // control range per actuator (+-3e38 where the model does not limit it): a
+  // call's control block (rollout.h StateArgs::ctrl) is clamped to it in the
+  // kernel as act_gain[a][3], the model's own control, was on the host.  Last,
+  // so every field above keeps its offset.
+  float act_ctrlrange[DX_NU][2];
 };
 
 }  // namespace mpcr

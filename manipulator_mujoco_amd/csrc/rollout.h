@@ -114,11 +114,21 @@ struct RolloutArgs {
 // plant holds after the same H steps.  Neither is plant mode: plant stays 0
 // and segments stay eligible.  Read by the STATE instantiations of
 // rollout_kernel, which the launchers pick when has_state().
+// ctrl (nullable): the actuator controls as an input of the call, nu floats
+// in actuator order, read when the kernel runs and clamped there to
+// DevModel::act_ctrlrange; null keeps the model's own (DevModel::act_gain[a][3]).
+// Step t (absolute, so segments agree) of problem p reads the block at ctrl +
+// p ctrl_stride + t ctrl_step_stride: stride 0 is one block for every problem,
+// step stride 0 one block for the whole horizon.  Per problem like start, so
+// group_args leaves it alone too.  Only the dual-arm class has actuators.
 struct StateArgs {
   const float* start;
   float* final_state;
   int start_stride;
+  int ctrl_stride, ctrl_step_stride;
+  const float* ctrl;
 };
+static_assert(sizeof(StateArgs) <= 40, "StateArgs: 40 of par's 80 bytes");
 static_assert(sizeof(StateArgs) <= sizeof(float) * PAR_N, "StateArgs inside par");
 __host__ __device__ inline StateArgs state_args(const RolloutArgs& a) {
   StateArgs s;
@@ -126,11 +136,11 @@ __host__ __device__ inline StateArgs state_args(const RolloutArgs& a) {
   return s;
 }
 inline void set_state_args(RolloutArgs& a, const StateArgs& s) { __builtin_memcpy(a.par, &s, sizeof(s)); }
-// whether a launch starts from, or returns, state blocks
+// whether a launch starts from, or returns, state blocks, or reads a control block
 inline bool has_state(const RolloutArgs& a) {
   if (!a.dpar) return false;
   const StateArgs s = state_args(a);
-  return s.start || s.final_state;
+  return s.start || s.final_state || s.ctrl;
 }
 
 // Per-block LDS image, sized by the kernel variant: NVW = dense-solve width

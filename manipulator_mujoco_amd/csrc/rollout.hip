@@ -2831,7 +2831,7 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
     rollout_kernel(RolloutArgs args, const DevModel* __restrict__ mptr) {
   static_assert(WPC == 1 || WPC == 2, "waves per candidate");
   static_assert(MULTI || !STATE, "the STATE instantiations look the problem's start block up");
-  StateArgs sa = {nullptr, nullptr, 0};
+  StateArgs sa = {nullptr, nullptr, 0, 0, 0, nullptr};
   if constexpr (STATE) sa = state_args(args);
   using S = typename std::conditional<WIDE, typename std::conditional<WPC == 2, SmemW2, SmemW>::type,
                                       typename std::conditional<WPC == 2, SmemN2, SmemN>::type>::type;
@@ -3075,6 +3075,13 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
   // this lane's controlled joint addresses, held across the horizon (read
   // every step; the per-step model launder would otherwise reload them)
   const int ctrl_qa = lane < nc ? m->ctrl_qposadr[lane] : 0, ctrl_da = lane < nc ? m->ctrl_dofadr[lane] : 0;
+  // STATE, dual-arm class: the problem's control block (StateArgs::ctrl;
+  // null: the model's own controls, act_gain[a][3]).  Wave-uniform, a scalar
+  // pair; the values themselves are loaded again every step.
+  const float* ctrl_p = nullptr;
+  if constexpr (STATE && S::WIDE) {
+    if (sa.ctrl) ctrl_p = sa.ctrl + (size_t)(args.prob_n ? (args.prob_off + b) / args.prob_n : 0) * sa.ctrl_stride;
+  }
   PROF_DECL
   unsigned* pace = nullptr;
   int pace_own = 0;
@@ -3450,6 +3457,11 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
     // ---- cinert, cdof (+ actuator forces) -------------------------------------
     if constexpr (S::WIDE) {
       if (lane < m->nu) {
+        // the call's control of this step (STATE), issued ahead of the
+        // transmission loop so the load overlaps its len / vel chain
+        float cv = 0.f;
+        if constexpr (STATE)
+          if (ctrl_p) cv = ctrl_p[(size_t)t * sa.ctrl_step_stride + lane];
         float len = 0.f, vel = 0.f;
         for (int k = 0; k < m->act_ntrn[lane]; k++) {
           len = fmaf(m->act_moment[lane][k], s.qpos[m->act_qadr[lane][k]], len);
@@ -3460,7 +3472,10 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
         float gain = g[0];
         if (m->act_gaffine[lane]) gain += g[1] * len + g[2] * vel;
         const float bias = m->act_baffine[lane] ? bp[0] + bp[1] * len + bp[2] * vel : 0.f;
-        s.actf[lane] = clampf(gain * g[3] + bias, m->act_frc[lane][0], m->act_frc[lane][1]);
+        float ctrl = g[3];
+        if constexpr (STATE)
+          if (ctrl_p) ctrl = clampf(cv, m->act_ctrlrange[lane][0], m->act_ctrlrange[lane][1]);
+        s.actf[lane] = clampf(gain * ctrl + bias, m->act_frc[lane][0], m->act_frc[lane][1]);
       }
     }
     if (lane < nb) {

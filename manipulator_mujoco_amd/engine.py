@@ -49,6 +49,29 @@ class Model:
         out = (adr[:self.compiled.ngeom], cells[:n])
         return out + (ex[:n].astype(bool),) if exact else out
 
+    def actuators(self):
+        """``mpcr_model_actuators``: (nu, ctrlrange (nu, 2), limited (nu,) bool)."""
+        lib = _lib.load()
+        nu = ctypes.c_int()
+        check(lib.mpcr_model_actuators(self.handle, ctypes.byref(nu), None, None))
+        rng = np.zeros((max(nu.value, 1), 2))
+        lim = np.zeros(max(nu.value, 1), dtype=np.int32)
+        check(lib.mpcr_model_actuators(self.handle, None, rng.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                       lim.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+        return nu.value, rng[:nu.value], lim[:nu.value].astype(bool)
+
+    def own_ctrl(self):
+        """The model's own controls (act_ctrl), nu values."""
+        nu = int(getattr(self.compiled, "nu", 0))
+        return np.asarray(getattr(self.compiled, "act_ctrl", np.zeros(nu)), dtype=np.float64).reshape(-1)[:nu].copy()
+
+    def clamp_ctrl(self, ctrl):
+        """``ctrl`` clamped to ctrlrange where the model limits it, as the
+        library and the kernel clamp it."""
+        nu, rng, lim = self.actuators()
+        c = np.array(ctrl, dtype=np.float64).reshape(-1)[:nu]
+        return np.where(lim, np.clip(c, rng[:, 0], rng[:, 1]), c)
+
     def __del__(self):
         try:
             if getattr(self, "handle", None):
@@ -98,6 +121,7 @@ class Engine:
         self.max_n = int(max_n)
         self.nctrl = int(compiled_model.nctrl)
         self.nslot = int(compiled_model.nslot)
+        self.nu = int(getattr(compiled_model, "nu", 0))
         pdot = np.ascontiguousarray(pdot, dtype=np.float32)
         if pdot.shape[0] != self.H:
             raise ValueError(f"pdot has {pdot.shape[0]} rows, expected num_steps={self.H}")
@@ -202,7 +226,7 @@ class Engine:
         return pack_state(self.model.compiled, qpos, qvel, qacc_warmstart)
 
     def _rollout_dp(self, nprob, inp, layout, params, cost4, theta, thetadot, best_keys, index_base, status,
-                    reset_best, stream, state=None):
+                    reset_best, stream, state=None, ctrl=None, ctrl_per_step=False):
         """nprob None: ``rollout_cost_dp`` (its own C entry, which takes an
         empty batch); else ``rollout_cost_multi`` or, with state = (start,
         final_state), ``rollout_cost_state``."""
@@ -237,11 +261,35 @@ class Engine:
             if final_state is not None and (final_state.numel() != n * blk or final_state.shape[-1] != blk):
                 raise ValueError(f"final_state must be ({n}, {blk})")
             fn, extra = lib.mpcr_rollout_cost_state, (ptr(start), stride, ptr(final_state))
+            if ctrl is not None:
+                extra += self._ctrl_args(ctrl, ctrl_per_step, nprob, inp.device)
+                fn = lib.mpcr_rollout_cost_ctrl
         st = stream if stream is not None else torch.cuda.current_stream(inp.device).cuda_stream
         flags = MPCR_F_DEVICE_PTRS | (MPCR_F_RESET_BEST if reset_best else 0)
         check(fn(self.handle, ptr(inp), layout, *shape, ptr(params), *extra, ptr(cost4), ptr(theta), ptr(thetadot),
                  ptr(best_keys), int(index_base), ptr(status), flags, ctypes.c_void_p(st)))
         return cost4
+
+    def _ctrl_args(self, ctrl, per_step, nprob, device):
+        """(pointer, problem stride, step stride) of a control tensor: (nu,),
+        (nprob, nu) or, per_step, (nprob, H, nu)."""
+        import torch
+        nu = self.nu
+        if (not isinstance(ctrl, torch.Tensor) or not ctrl.is_cuda or ctrl.dtype != torch.float32
+                or not ctrl.is_contiguous() or ctrl.device != device):
+            raise ValueError("ctrl must be a contiguous float32 CUDA tensor on the input's device")
+        if nu == 0:
+            shape_ok = True  # the library refuses it: the model has no actuators
+        elif per_step:
+            shape_ok = tuple(ctrl.shape) == (nprob, self.H, nu)
+        else:
+            shape_ok = tuple(ctrl.shape) in ((nu,), (nprob, nu))
+        if not shape_ok:
+            raise ValueError(f"ctrl must be ({nu},) or ({nprob}, {nu}), or with ctrl_per_step ({nprob}, {self.H}, {nu}); "
+                             f"got {tuple(ctrl.shape)}")
+        if per_step:
+            return ctypes.c_void_p(ctrl.data_ptr()), self.H * nu, nu
+        return ctypes.c_void_p(ctrl.data_ptr()), nu if ctrl.dim() == 2 and nprob > 1 else 0, 0
 
     def rollout_cost_dp(self, inp, layout: int, params, cost4, theta=None, thetadot=None, best_key=None,
                         index_base: int = 0, status=None, reset_best: bool = True, stream=None):
@@ -264,7 +312,7 @@ class Engine:
 
     def rollout_cost_state(self, inp, layout: int, params, nprob: int, cost4, start=None, final_state=None,
                            theta=None, thetadot=None, best_keys=None, index_base: int = 0, status=None,
-                           reset_best: bool = True, stream=None):
+                           reset_best: bool = True, stream=None, ctrl=None, ctrl_per_step: bool = False):
         """``rollout_cost_multi`` from a given full state and / or returning
         the final states (``mpcr_rollout_cost_state``).  ``start``: a device
         tensor of one state block (``pack_state``, ``Plant.copy_state``) shared
@@ -274,9 +322,14 @@ class Engine:
         device tensor (nprob * n_per, block) that receives, per candidate,
         what a plant holds after the same steps.  Both None:
         ``rollout_cost_multi``.  Graph-capturable; a replay reads ``start``
-        afresh."""
+        afresh.  ``ctrl`` (``mpcr_rollout_cost_ctrl``): the actuator controls
+        as a device tensor in actuator order, (nu,) for every problem or
+        (nprob, nu) with one block per problem, or with ``ctrl_per_step``
+        (nprob, H, nu), one row per step; clamped to the model's ctrlrange in
+        the kernel and read when it runs.  None keeps the model's own."""
         return self._rollout_dp(int(nprob), inp, layout, params, cost4, theta, thetadot, best_keys, index_base,
-                                status, reset_best, stream, state=(start, final_state))
+                                status, reset_best, stream, state=(start, final_state), ctrl=ctrl,
+                                ctrl_per_step=ctrl_per_step)
 
     def trace(self, inp, layout: int, q0, w, ptgt, qtgt):
         """Debug/parity run (host arrays): cost4, theta, per-step eef pose, masked slot distances."""
@@ -310,6 +363,8 @@ class Plant:
         self.model = Model(compiled_model)
         self.nq, self.nv = int(compiled_model.nq), int(compiled_model.nv)
         self.nctrl = int(compiled_model.nctrl)
+        self.nu = int(getattr(compiled_model, "nu", 0))
+        self._ctrl = None  # the controls applied (clamped); None: the model's own
         h = ctypes.c_void_p()
         check(lib.mpcr_plant_create(self.model.handle, int(device), ctypes.byref(h)))
         self.handle = h
@@ -342,6 +397,24 @@ class Plant:
                                                None if qv is None else qv.ctypes.data_as(dp),
                                                None if qw is None else qw.ctypes.data_as(dp)))
         self._pull()
+
+    def set_ctrl(self, ctrl):
+        """The plant's actuator controls from now on (``mpcr_plant_set_ctrl``):
+        nu values in actuator order, clamped to the model's ctrlrange; None
+        restores the model's own."""
+        c = None
+        if ctrl is not None:
+            c = np.ascontiguousarray(ctrl, dtype=np.float64).reshape(-1)
+            if c.size != self.nu:
+                raise ValueError(f"ctrl must hold nu={self.nu} values, got {c.size}")
+        check(_lib.load().mpcr_plant_set_ctrl(
+            self.handle, None if c is None else c.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+        self._ctrl = None if c is None else self.model.clamp_ctrl(c)
+
+    @property
+    def ctrl(self):
+        """The controls the plant applies (clamped), in actuator order."""
+        return self.model.clamp_ctrl(self.model.own_ctrl()) if self._ctrl is None else self._ctrl.copy()
 
     def copy_state(self, tensor, stream=None):
         """The plant's state block into ``tensor`` (float32, CUDA, contiguous,

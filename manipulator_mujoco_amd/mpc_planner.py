@@ -51,16 +51,47 @@ class _Bodies:
         return name in self._pos
 
 
+def hold_ctrl(model, num_dof, hold=True, gripper=None):
+    """A ``run_cem_planner(ctrl=...)`` callable for a compiled model.  hold:
+    every actuator whose single transmission dof is one of the planner's
+    ``num_dof`` controlled dofs gets the plant's current joint position, so a
+    position servo holds the pose the plan has reached instead of pulling back
+    to its compiled target.  gripper: the control of every actuator with a
+    two-dof transmission (the finger pairs).  The rest keep the model's own."""
+    nu = int(getattr(model, "nu", 0))
+    own = np.asarray(getattr(model, "act_ctrl", np.zeros(nu)), dtype=np.float64).reshape(-1)[:nu]
+    ntrn = np.asarray(model.act_ntrn)[:nu]
+    dof = np.asarray(model.act_dof).reshape(-1, 2)[:nu]
+    qadr = np.asarray(model.act_qadr).reshape(-1, 2)[:nu]
+    planned = set(int(v) for v in np.asarray(model.ctrl_dofadr)[:num_dof])
+    held = [a for a in range(nu) if ntrn[a] == 1 and int(dof[a, 0]) in planned] if hold else []
+    pairs = [a for a in range(nu) if ntrn[a] == 2] if gripper is not None else []
+
+    def ctrl(_tick, plant):
+        c = own.copy()
+        for a in held:
+            c[a] = plant.qpos[qadr[a, 0]]
+        for a in pairs:
+            c[a] = gripper
+        return c
+
+    return ctrl
+
+
 def run_cem_planner(num_dof=None, num_batch=None, num_steps=None, maxiter_cem=None, maxiter_projection=None,
                     w_pos=None, w_rot=None, w_col=None, num_elite=None, timestep=None, initial_qpos=None,
                     target_names=None, show_viewer=None, cam_distance=None, show_contact_points=None,
                     position_threshold=None, rotation_threshold=None, save_data=None, data_dir=None,
                     stop_at_final_target=None, *, max_ticks=100, model_path=None, device=None, graph=True,
-                    verbose=True, planner_kwargs=None, plan_from_state=False):
+                    verbose=True, planner_kwargs=None, plan_from_state=False, ctrl=None):
     """Run the CEM planner in closed loop for ``max_ticks`` ticks (headless).
     plan_from_state: every tick's rollouts start from the plant's full state
     (a device copy of its block) instead of the template state with the arm
-    joints set, which is the reference's behaviour and the default."""
+    joints set, which is the reference's behaviour and the default.
+    ctrl: the actuator controls, nu values in actuator order or a callable
+    ``(tick, plant) -> array`` (``hold_ctrl``), given every tick to the plant
+    and to the planner's rollouts; None keeps the model's own in both (the
+    reference never sets MjData.ctrl)."""
     if initial_qpos is None:
         initial_qpos = [1.5, -1.8, 1.75, -1.25, -1.6, 0]
     if target_names is None:
@@ -80,7 +111,8 @@ def run_cem_planner(num_dof=None, num_batch=None, num_steps=None, maxiter_cem=No
                       w_pos=w_pos, w_rot=w_rot, w_col=w_col, num_elite=num_elite, timestep=timestep,
                       maxiter_projection=maxiter_projection, model_path=model_path, device=device, graph=graph,
                       verbose=verbose, **({"return_rollouts": False} | (planner_kwargs or {})
-                                          | ({"plan_from_state": True} if plan_from_state else {})))
+                                          | ({"plan_from_state": True} if plan_from_state else {})
+                                          | ({"actuator_ctrl": True} if ctrl is not None else {})))
     log(f"Initialized CEM Planner: {round(time.time() - start_time, 2)}s")
 
     model = cem.model
@@ -99,12 +131,23 @@ def run_cem_planner(num_dof=None, num_batch=None, num_steps=None, maxiter_cem=No
     init_position = data.site_xpos_tcp
     init_rotation = data.xquat_hande
 
-    target_pos = bodies.pos(target_names[0])
-    target_rot = bodies.quat(target_names[0])
+    # ("home" is no body: the pose the loop started at, as in the loop below --
+    # the only target of a model without target bodies, such as the dual arm)
+    target_pos = bodies.pos(target_names[0]) if target_names[0] != "home" else init_position
+    target_rot = bodies.quat(target_names[0]) if target_names[0] != "home" else init_rotation
     start_time = time.time()
     from_plant = {"state": data} if plan_from_state else {}  # each tick plans from the plant's state
+
+    def apply_ctrl(tick):
+        """The tick's controls to the plant; the planner's argument for them."""
+        if ctrl is None:
+            return {}
+        c = np.asarray(ctrl(tick, data) if callable(ctrl) else ctrl, dtype=np.float64).reshape(-1)
+        data.set_ctrl(c)
+        return {"ctrl": c}
+
     _ = cem.compute_cem(xi_mean, data.qpos[ctrl_q], data.qvel[ctrl_v], data.qacc[ctrl_v], target_pos, target_rot,
-                        **from_plant)
+                        **from_plant, **apply_ctrl(0))
     log(f"Compute CEM: {round(time.time() - start_time, 2)}s")
 
     thetadot = np.zeros(num_dof)
@@ -127,7 +170,8 @@ def run_cem_planner(num_dof=None, num_batch=None, num_steps=None, maxiter_cem=No
             bodies.set("target_0", data.site_xpos_tcp, data.xquat_hande)
 
         cost, best_cost_g, best_cost_r, best_cost_c, best_vels, best_traj, xi_mean, _, _ = cem.compute_cem(
-            xi_mean, data.qpos[ctrl_q], data.qvel[ctrl_v], data.qacc[ctrl_v], target_pos, target_rot, **from_plant)
+            xi_mean, data.qpos[ctrl_q], data.qvel[ctrl_v], data.qacc[ctrl_v], target_pos, target_rot, **from_plant,
+            **apply_ctrl(_tick))
 
         thetadot = np.mean(best_vels[1:num_steps - 2], axis=0)
         data.step(thetadot)
@@ -208,7 +252,15 @@ def main(argv=None):  # SBP/mpc_planner.py:256-314
     parser.add_argument("--no_graph", action="store_true")
     parser.add_argument("--plan_from_state", action="store_true",
                         help="plan each tick from the plant's full state, not the template state")
+    parser.add_argument("--ctrl_hold", action="store_true",
+                        help="each tick, the servos of the planned joints get the plant's current joint positions")
+    parser.add_argument("--gripper", type=float, default=None, metavar="G",
+                        help="control of the actuators with a two-dof transmission (the finger pairs)")
     a = parser.parse_args(argv)
+    ctrl = None
+    if a.ctrl_hold or a.gripper is not None:
+        from .planner import _resolve_model
+        ctrl = hold_ctrl(_resolve_model(a.model, a.timestep), a.num_dof, hold=a.ctrl_hold, gripper=a.gripper)
     return run_cem_planner(num_dof=a.num_dof, num_batch=a.num_batch, num_steps=a.num_steps,
                            maxiter_cem=a.maxiter_cem, maxiter_projection=a.maxiter_projection, w_pos=a.w_pos,
                            w_rot=a.w_rot, w_col=a.w_col, num_elite=a.num_elite, timestep=a.timestep,
@@ -217,7 +269,8 @@ def main(argv=None):  # SBP/mpc_planner.py:256-314
                            position_threshold=a.position_threshold, rotation_threshold=a.rotation_threshold,
                            save_data=a.save_data, data_dir=a.data_dir,
                            stop_at_final_target=not a.continue_after_final, max_ticks=a.max_ticks,
-                           model_path=a.model, graph=not a.no_graph, plan_from_state=a.plan_from_state)
+                           model_path=a.model, graph=not a.no_graph, plan_from_state=a.plan_from_state,
+                           ctrl=ctrl)
 
 
 if __name__ == "__main__":

@@ -100,13 +100,18 @@ class cem_planner:  # noqa: N801 (reference name)
                         the default here.  The state lives in a static device
                         buffer, initialised to the template, that the
                         (captured) rollouts read each tick
+    actuator_ctrl       the rollouts read the actuator controls per problem
+                        from a static device buffer (``compute_cem(ctrl=...)``),
+                        initialised to the model's own, instead of the values
+                        the model was compiled with.  Independent of
+                        plan_from_state; both may be on
     """
 
     def __init__(self, num_dof=None, num_batch=None, num_steps=None, timestep=None, maxiter_cem=None,
                  num_elite=None, w_pos=None, w_rot=None, w_col=None, maxiter_projection=None, *,
                  model_path=None, device=None, seed=0, elite_from_filtered=False, graph=False, group=None,
                  gather_rollouts=False, return_rollouts=True, capture_exchange=True, verbose=True,
-                 num_problems=1, seed_step=0, plan_from_state=False):
+                 num_problems=1, seed_step=0, plan_from_state=False, actuator_ctrl=False):
         import torch
         import torch.distributed as tdist
 
@@ -189,6 +194,14 @@ class cem_planner:  # noqa: N801 (reference name)
         self._state = None
         if self.plan_from_state:
             self._state = torch.as_tensor(self.engine.pack_state()).to(self.device).repeat(B, 1).contiguous()
+        # one control block per problem (actuator order), the model's own until a tick stages another
+        self.actuator_ctrl = bool(actuator_ctrl)
+        self._ctrl = None
+        if self.actuator_ctrl:
+            own = self.engine.model.own_ctrl().astype(np.float32)
+            if own.size == 0:
+                raise ValueError("actuator_ctrl: the model has no actuators")
+            self._ctrl = torch.as_tensor(own).to(self.device).repeat(B, 1).contiguous()
         self._graphs = None
         if verbose and self.rank == 0:
             self.print_info()
@@ -220,9 +233,9 @@ class cem_planner:  # noqa: N801 (reference name)
                                       index_base=self.index_base)
         out = dict(theta=self._theta[it], thetadot=self._thetadot[it], best_keys=self._key if last else None,
                    index_base=self.index_base)
-        if self.plan_from_state:  # the same launch, reading each problem's start block
+        if self.plan_from_state or self.actuator_ctrl:  # the same launch, reading each problem's start / control block
             self.engine.rollout_cost_state(self._xf.view(B * n, self.nvar), MPCR_LAYOUT_XI, self._par, B,
-                                           self._costs[it], start=self._state, **out)
+                                           self._costs[it], start=self._state, ctrl=self._ctrl, **out)
         else:
             self.engine.rollout_cost_multi(self._xf.view(B * n, self.nvar), MPCR_LAYOUT_XI, self._par, B,
                                            self._costs[it], **out)
@@ -341,13 +354,35 @@ class cem_planner:  # noqa: N801 (reference name)
                     raise ValueError("a start state is a Plant or (qpos, qvel[, qacc_warmstart])")
                 self._state[p].copy_(torch.as_tensor(self.engine.pack_state(*st)))
 
+    def _stage_ctrls(self, ctrls):
+        """Each problem's actuator controls (nu values, actuator order) into
+        its block of the static buffer; None keeps what is staged.  Every rank
+        of a sharded planner stages the same block."""
+        import torch
+        if ctrls is None:
+            return
+        if not self.actuator_ctrl:
+            raise ValueError("actuator controls need a planner built with actuator_ctrl=True")
+        if len(ctrls) != self.num_problems:
+            raise ValueError(f"{len(ctrls)} control blocks for {self.num_problems} problem(s)")
+        nu = self._ctrl.shape[1]
+        for p, c in enumerate(ctrls):
+            if c is None:
+                continue
+            c = np.asarray(c, dtype=np.float32)
+            if c.shape != (nu,):
+                raise ValueError(f"a control block holds nu={nu} values, got shape {c.shape}")
+            self._ctrl[p].copy_(torch.as_tensor(np.ascontiguousarray(c)))
+
     def compute_cem(self, xi_mean, init_pos=(1.5, -1.8, 1.75, -1.25, -1.6, 0.0), init_vel=None, init_acc=None,
-                    target_pos=None, target_rot=None, state=None):
+                    target_pos=None, target_rot=None, state=None, ctrl=None):
         """One MPC tick of CEM (SBP/mjx_planner.py:364-406). Returns the reference 9-tuple (numpy).
         state (planners built with plan_from_state): the full state the
         rollouts start from, a ``Plant`` or ``(qpos, qvel[, qacc_warmstart])``;
         None keeps the one staged last (at first the template).  init_pos
-        still sets the arm joints."""
+        still sets the arm joints.  ctrl (planners built with actuator_ctrl):
+        the actuator controls of the rollouts, nu values; None keeps the ones
+        staged last (at first the model's own)."""
         import torch
 
         from . import dist as mdist
@@ -369,6 +404,7 @@ class cem_planner:  # noqa: N801 (reference name)
         self._stage(np.asarray(xi_mean, np.float32).reshape(1, self.nvar), init_pos[None], init_vel[None],
                     init_acc[None], target_pos[None], target_rot[None], [w])
         self._stage_states(None if state is None else [state])
+        self._stage_ctrls(None if ctrl is None else [ctrl])
         self._run_iterations()
 
         costs, theta, thetadot = self._costs, self._theta, self._thetadot
@@ -395,7 +431,7 @@ class cem_planner:  # noqa: N801 (reference name)
         return tuple(o.cpu().numpy() if isinstance(o, torch.Tensor) else o for o in out)
 
     def compute_cem_batch(self, xi_mean, init_pos, init_vel=None, init_acc=None, target_pos=None, target_rot=None,
-                          weights=None, states=None):
+                          weights=None, states=None, ctrls=None):
         """One MPC tick of ``num_problems`` independent CEM problems in one
         batched sequence of launches (each kernel of ``compute_cem`` once,
         over every problem): xi_mean (B, nvar), init_pos / init_vel /
@@ -406,7 +442,8 @@ class cem_planner:  # noqa: N801 (reference name)
         entry j of ``compute_cem`` on a planner with seed ``seed + p
         seed_step`` given problem p's arguments.  states (planners built with
         plan_from_state): one start state per problem, each as ``compute_cem``'s
-        ``state`` (a None entry keeps that problem's)."""
+        ``state`` (a None entry keeps that problem's).  ctrls (planners built
+        with actuator_ctrl): one control block per problem, likewise."""
         import torch
 
         B, d, H, n, it_n = self.num_problems, self.num_dof, self.num, self.n_local, self.maxiter_cem
@@ -431,6 +468,7 @@ class cem_planner:  # noqa: N801 (reference name)
 
         self._stage(xi_mean, init_pos, init_vel, init_acc, target_pos, target_rot, weights)
         self._stage_states(states)
+        self._stage_ctrls(ctrls)
         self._run_iterations()
 
         # each problem's best candidate of the last iteration: the low word of

@@ -1,0 +1,522 @@
+"""Actuator controls as an input of the call (``mpcr_rollout_cost_ctrl``,
+``Engine.rollout_cost_state(ctrl=)``, ``Plant.set_ctrl``,
+``cem_planner(actuator_ctrl=True)``, ``run_cem_planner(ctrl=)``).
+
+* a block holding the model's own controls gives bit for bit the call without;
+* under C1 (arm 1's servos holding the start pose, the Hand-E half closed, arm
+  2 sent to a pose) the dual arm's costs meet the parity bar of
+  tests/parity_util.py against the fp64 oracle of the model copied with
+  ``act_ctrl = C1`` -- and every cost is off the ``ctrl = NULL`` call's, which
+  is why this fails on a build that ignores the input;
+* the kernel clamps as the host does; a schedule over the steps is what a plant
+  does when ``set_ctrl`` is called before each step; horizon segments over
+  candidate groups, per-problem blocks and stride 0 equal the plain calls;
+* the ``hande_scene`` plant closes its fingers as the oracle does;
+* the planner: graph replay equals eager and reads controls staged since
+  capture, the model's own staged equals a planner without the flag, the
+  selected candidate costs what the oracle says at C1, two problems equal two
+  planners; argument errors; the closed loop with held servos.
+
+Every dual-arm rollout asserts the sync, non-finite and truncated status bits
+clear."""
+import copy
+import ctypes
+
+import numpy as np
+import pytest
+
+import oracle
+import parity_util as pu
+from manipulator_mujoco_amd import _lib, basis, models
+from manipulator_mujoco_amd.engine import MPCR_LAYOUT_THETADOT, MPCR_LAYOUT_XI, Engine, Plant, unpack_state
+from test_gpu_state import PARTS, _engine, _Out, _par_blocks, _same, _selected_matches_oracle, _two_wave, _xi, d1_state
+
+pytestmark = pytest.mark.gpu
+
+Q0 = pu.Q0
+NU = 14
+BAD_STATUS = 1 | 2 | (1 << 10)  # sync, non-finite, truncated (tests/test_gpu_state.py)
+
+
+def c1():
+    c = np.zeros(NU)
+    c[0:6] = Q0  # arm 1's servos hold the start pose
+    c[6] = 128.0  # Hand-E half closed
+    c[7:13] = (0.3, -0.4, 0.5, -0.2, 0.1, 0.2)  # arm 2 sent to a pose
+    c[13] = 0.0  # 2F-85 open (closed it fills 184 of the kernel's 200 rows)
+    return c
+
+
+def with_ctrl(m, ctrl):
+    """The model whose own controls are ctrl: what the oracle applies."""
+    mb = copy.deepcopy(m)
+    mb.act_ctrl = np.array(ctrl, dtype=np.float64)
+    return mb
+
+
+@pytest.fixture(scope="module")
+def torch_cuda():
+    import torch
+    assert torch.cuda.is_available(), "GPU tests need a GPU"
+    return torch
+
+
+def dev(torch, a):
+    return torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).cuda()
+
+
+def clean(torch, *outs):
+    for o in outs:
+        assert int((o.st & BAD_STATUS).sum()) == 0
+        assert torch.isfinite(o.c).all()
+
+
+# ---------------------------------------------------------------------------
+# 1. a block holding the model's own controls is the existing call
+
+
+@pytest.mark.parametrize("two_wave", [True, False])
+def test_own_controls_block_equals_the_call_without(torch_cuda, two_wave):
+    torch = torch_cuda
+    B, n_per, H = 2, 24, 12
+    n = B * n_per
+    m, e = _engine("dual_arm", H, n)
+    assert e.nu == NU
+    blk = e.state_layout()["size"]
+    xi, par = _xi(torch, n), _par_blocks(torch, B)
+    own = dev(torch, e.model.own_ctrl())
+    with _two_wave(two_wave):
+        ref, one, per, sched = (_Out(torch, n, H, B, blk) for _ in range(4))
+        e.rollout_cost_state(xi, MPCR_LAYOUT_XI, par, B, ref.c, **ref.kw())
+        e.rollout_cost_state(xi, MPCR_LAYOUT_XI, par, B, one.c, ctrl=own, **one.kw())
+        e.rollout_cost_state(xi, MPCR_LAYOUT_XI, par, B, per.c, ctrl=own.repeat(B, 1).contiguous(), **per.kw())
+        e.rollout_cost_state(xi, MPCR_LAYOUT_XI, par, B, sched.c, ctrl=own.repeat(B, H, 1).contiguous(),
+                             ctrl_per_step=True, **sched.kw())
+        torch.cuda.synchronize()
+    clean(torch, ref, one, per, sched)
+    for o in (one, per, sched):
+        ref.assert_equal(torch, o)
+
+
+# ---------------------------------------------------------------------------
+# 2. oracle parity under C1
+
+
+@pytest.fixture(scope="module")
+def c1_case():
+    """dual_arm, 64 x 12 uniform joint velocities, and the oracle's costs and
+    conditioning with act_ctrl = C1 (computed once)."""
+    m = models.load("dual_arm", 0.05)
+    n, H = 64, 12
+    td = np.random.default_rng(1).uniform(-0.6, 0.6, (n, 6 * H))
+    mb = with_ctrl(m, c1())
+    o, sens = pu.conditioning(mb, td, seed=1)
+    assert o["status"] == 0
+    return dict(m=m, mb=mb, n=n, H=H, td=td, o=o, sens=sens)
+
+
+@pytest.mark.parametrize("two_wave", [True, False])
+def test_c1_costs_meet_the_parity_bar(torch_cuda, c1_case, two_wave):
+    torch = torch_cuda
+    c = c1_case
+    n, H, m = c["n"], c["H"], c["m"]
+    _, _, Pd, _ = basis.planner_basis(H, 0.05)
+    e = Engine(m, H, n, Pd)
+    td = dev(torch, c["td"])
+    par = dev(torch, Engine.params(pu.Q0, pu.W, pu.PT, pu.QT))
+    cost, base = torch.zeros((n, 4), device="cuda"), torch.zeros((n, 4), device="cuda")
+    status, status0 = (torch.zeros(n, dtype=torch.int32, device="cuda") for _ in range(2))
+    with _two_wave(two_wave):
+        e.rollout_cost_state(td, MPCR_LAYOUT_THETADOT, par, 1, cost, ctrl=dev(torch, c1()), status=status)
+        e.rollout_cost_state(td, MPCR_LAYOUT_THETADOT, par, 1, base, status=status0)
+        torch.cuda.synchronize()
+    assert int((status & BAD_STATUS).sum()) == 0 and int((status0 & BAD_STATUS).sum()) == 0
+    g4, b4 = cost.cpu().numpy().astype(np.float64), base.cpu().numpy().astype(np.float64)
+    # the controls matter (oracle: minimum 1.7e-4, median 2.1e-2)
+    moved = np.abs(g4[:, 0] - b4[:, 0]) / np.abs(b4[:, 0])
+    print(f"C1 vs ctrl = NULL: relative cost change min {moved.min():.2e} median {np.median(moved):.2e}")
+    assert (moved > 1e-4).all() and np.median(moved) > 1e-2
+    label = f"ctrl C1 dual_arm {n}x{H} two_wave={two_wave}"
+    stats = pu.check(m, g4[:, 0], c["o"], c["sens"], label=label)
+    pu.check_components(m, g4, c["o"], label=label)
+    print(label, stats)
+    assert stats["well"] >= 58  # (64 of 64 on the oracle)
+
+
+# ---------------------------------------------------------------------------
+# 3. the clamp
+
+
+def test_kernel_clamps_to_ctrlrange_as_the_host_does(torch_cuda):
+    torch = torch_cuda
+    n, H = 16, 8
+    m, e = _engine("dual_arm", H, n)
+    assert m.act_ctrllimited[2] and m.act_ctrlrange[2][1] == 3.1415
+    blk = e.state_layout()["size"]
+    xi, par = _xi(torch, n), _par_blocks(torch, 1)
+    outs = []
+    for v in (9.0, 3.1415, 0.5 * Q0[2]):
+        c = c1()
+        c[2] = v
+        o = _Out(torch, n, H, 1, blk)
+        e.rollout_cost_state(xi, MPCR_LAYOUT_XI, par, 1, o.c, ctrl=dev(torch, c), **o.kw())
+        torch.cuda.synchronize()
+        outs.append(o)
+    clean(torch, *outs)
+    outs[0].assert_equal(torch, outs[1])
+    assert not torch.equal(outs[0].c, outs[2].c)  # (the entry is read at all)
+
+
+# ---------------------------------------------------------------------------
+# 4. the rollout is what a plant does
+
+
+def switched_schedule(H, at, shift=0.2):
+    """C1 up to step `at`; from there the Hand-E closed and arm 2's targets shifted."""
+    s = np.tile(c1(), (H, 1))
+    s[at:, 6] = 255.0
+    s[at:, 7:13] += shift
+    return s
+
+
+def test_scheduled_rollout_equals_plant_steps_with_set_ctrl_bitwise(torch_cuda):
+    torch = torch_cuda
+    n, H, picks = 8, 10, (0, 3, 7)
+    m, e = _engine("dual_arm", H, n)
+    blk = e.state_layout()["size"]
+    qa = np.asarray(m.ctrl_qposadr[:6])
+    qpos, qvel = d1_state(m)
+    qpos[qa] = Q0
+    plant = Plant(m)
+    plant.set_state(qpos=qpos, qvel=qvel)
+    plant.step(np.array([0.2, -0.3, 0.25, 0.1, -0.2, 0.3]))  # one step: a warm start that is not zero
+    start = plant.copy_state(torch.zeros(blk, device="cuda"))
+    torch.cuda.synchronize()
+    S = unpack_state(m, start)
+    sched = switched_schedule(H, 5)
+    td = np.random.default_rng(3).uniform(-0.6, 0.6, (n, 6 * H)).astype(np.float32)
+    td_d = dev(torch, td)
+    par = dev(torch, Engine.params(S["qpos"][qa], pu.W, pu.PT, pu.QT))
+    outs = []
+    for two_wave in (True, False):
+        with _two_wave(two_wave):
+            o = _Out(torch, n, H, 1, blk)
+            e.rollout_cost_state(td_d, MPCR_LAYOUT_THETADOT, par, 1, o.c, start=start, ctrl=dev(torch, sched[None]),
+                                 ctrl_per_step=True, **o.kw())
+            torch.cuda.synchronize()
+        outs.append(o)
+    clean(torch, *outs)
+    outs[0].assert_equal(torch, outs[1], msg="one wave against two")
+    theta, fin = outs[0].th.cpu().numpy(), unpack_state(m, outs[0].fin)
+    for i in picks:
+        plant.set_state(qpos=S["qpos"], qvel=S["qvel"], qacc_warmstart=S["qacc_warmstart"])
+        v = td[i].reshape(6, H)
+        for t in range(H):
+            plant.set_ctrl(sched[t])
+            np.testing.assert_array_equal(plant.ctrl, sched[t])
+            plant.step(v[:, t].astype(np.float64))
+            np.testing.assert_array_equal(plant.qpos[qa].astype(np.float32), theta[i].reshape(6, H)[:, t])
+        end = unpack_state(m, plant.copy_state(torch.zeros(blk, device="cuda")))
+        for k in PARTS:
+            np.testing.assert_array_equal(fin[k][i].view(np.int32), end[k].view(np.int32), err_msg=f"{i} {k}")
+    # the switch is seen: under C1 throughout the Hand-E's fingers (qpos 6, 7) end elsewhere
+    const = _Out(torch, n, H, 1, blk)
+    e.rollout_cost_state(td_d, MPCR_LAYOUT_THETADOT, par, 1, const.c, start=start, ctrl=dev(torch, c1()), **const.kw())
+    torch.cuda.synchronize()
+    clean(torch, const)
+    fin_c = unpack_state(m, const.fin)
+    gap = np.abs(fin["qpos"][:, 6:8] - fin_c["qpos"][:, 6:8]).max(axis=1)
+    print(f"final finger positions, switched against constant C1: differ by {gap.min():.2e} .. {gap.max():.2e}")
+    assert (gap > 1e-5).all()  # (oracle, another velocity: 7.8e-4)
+
+
+# ---------------------------------------------------------------------------
+# 5. horizon segments over candidate groups, 6. per problem
+
+
+def _ctrl_multi_equals_slices(torch, e, B, n_per, H, ctrl, per_step):
+    """The call over B problems reading ctrl[p] against B one-problem calls on the slices."""
+    blk, n = e.state_layout()["size"], B * n_per
+    xi, par = _xi(torch, n), _par_blocks(torch, B)
+    got = _Out(torch, n, H, B, blk)
+    e.rollout_cost_state(xi, MPCR_LAYOUT_XI, par, B, got.c, ctrl=ctrl, ctrl_per_step=per_step, **got.kw())
+    torch.cuda.synchronize()
+    clean(torch, got)
+    for p in range(B):
+        sl = slice(p * n_per, (p + 1) * n_per)
+        one = _Out(torch, n_per, H, 1, blk)
+        e.rollout_cost_state(xi[sl].contiguous(), MPCR_LAYOUT_XI, par[p].contiguous(), 1, one.c,
+                             ctrl=ctrl[p:p + 1].contiguous(), ctrl_per_step=per_step, **one.kw())
+        torch.cuda.synchronize()
+        got.assert_equal(torch, one, sl=sl, p=slice(p, p + 1), msg=f"problem {p}")
+    return got, xi, par
+
+
+def test_segmented_groups_read_the_schedule_by_absolute_step(torch_cuda):
+    """The segmented / grouped dual-arm launch found as
+    tests/test_gpu_state.py::test_segmented_groups_read_the_start_once_and_write_the_final_state
+    finds it, with H = 12: segments of 7 and 5 steps, the schedules switching
+    at step 10, inside the second one.  Each one-problem slice is a batch small
+    enough to run as one launch."""
+    torch = torch_cuda
+    B, H = 3, 12
+    m = models.load("dual_arm", 0.05)
+    _, _, Pd, _ = basis.planner_basis(H, 0.05)
+    probe = Engine(m, H, B * 1024, Pd)
+    lo, hi = 1, 1024
+    assert probe.dispatches(B * lo) == 1 and probe.dispatches(B * hi) > 1
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        lo, hi = (lo, mid) if probe.dispatches(B * mid) > 1 else (mid, hi)
+    n_per = hi
+
+    def straddles(n_per):
+        d = probe.dispatches(B * n_per)
+        G = d // 2  # two segments of H = 12
+        per = (B * n_per + G - 1) // G
+        return d > 1 and d % 2 == 0 and all((g * per) % n_per for g in range(1, G))
+
+    while not straddles(n_per) or probe.dispatches(B * n_per) < 4:
+        n_per += 1
+        assert n_per <= 1024
+    assert probe.dispatches(B * n_per) >= 4 and straddles(n_per) and probe.dispatches(n_per) == 1
+    del probe
+    e = Engine(m, H, B * n_per, Pd)
+    ctrl = dev(torch, np.stack([switched_schedule(H, 10, shift=0.1 + 0.05 * p) for p in range(B)]))
+    got, xi, par = _ctrl_multi_equals_slices(torch, e, B, n_per, H, ctrl, True)
+    # the step index is the horizon's: a schedule that never switches ends elsewhere
+    flat = _Out(torch, B * n_per, H, B, e.state_layout()["size"])
+    e.rollout_cost_state(xi, MPCR_LAYOUT_XI, par, B, flat.c, ctrl=dev(torch, np.tile(c1(), (B, H, 1))),
+                         ctrl_per_step=True, **flat.kw())
+    torch.cuda.synchronize()
+    f, f0 = unpack_state(m, got.fin)["qpos"], unpack_state(m, flat.fin)["qpos"]
+    assert (np.abs(f[:, 6:14] - f0[:, 6:14]).max(axis=1) > 1e-5).all()  # (fingers and arm 2; oracle: 1.6e-4, 4e-2)
+
+
+@pytest.mark.parametrize("two_wave", [True, False])
+def test_per_problem_blocks_equal_single_calls(torch_cuda, two_wave):
+    torch = torch_cuda
+    B, n_per, H = 2, 24, 8
+    m, e = _engine("dual_arm", H, B * n_per)
+    blk = e.state_layout()["size"]
+    other = c1()
+    other[6], other[7:13] = 20.0, other[7:13] - 0.3
+    ctrl = dev(torch, np.stack([c1(), other]))
+    with _two_wave(two_wave):
+        got, xi, par = _ctrl_multi_equals_slices(torch, e, B, n_per, H, ctrl, False)
+        # stride 0: one block for every problem is that block repeated
+        shared, twice = _Out(torch, B * n_per, H, B, blk), _Out(torch, B * n_per, H, B, blk)
+        e.rollout_cost_state(xi, MPCR_LAYOUT_XI, par, B, shared.c, ctrl=ctrl[1].contiguous(), **shared.kw())
+        e.rollout_cost_state(xi, MPCR_LAYOUT_XI, par, B, twice.c, ctrl=ctrl[1].repeat(B, 1).contiguous(), **twice.kw())
+        torch.cuda.synchronize()
+    clean(torch, shared, twice)
+    shared.assert_equal(torch, twice)
+    assert not torch.equal(shared.fin[:n_per], got.fin[:n_per])  # problem 0 read its own block
+    assert torch.equal(shared.fin[n_per:], got.fin[n_per:])
+
+
+# ---------------------------------------------------------------------------
+# 7. the hande_scene plant
+
+
+def test_hande_scene_plant_closes_its_fingers_as_the_oracle_does(torch_cuda):
+    """set_ctrl([255]) and 50 steps from the template state, re-synced to the
+    oracle's fp64 state every step as
+    tests/test_gpu_plant.py::test_plant_hande_scene_matches_oracle_step does,
+    and held to its tolerance on qpos (1e-5)."""
+    m = models.load("hande_scene")
+    mb = with_ctrl(m, [255.0])
+    fq = np.asarray(m.act_qadr).reshape(-1, 2)[0]  # the two finger joints
+    plant, untouched = Plant(m), Plant(m)
+    plant.set_ctrl([255.0])
+    np.testing.assert_array_equal(plant.ctrl, [255.0])
+    tpl = (np.array(m.qpos_init[:m.nq], dtype=np.float64), np.array(m.qvel_init[:m.nv], dtype=np.float64), np.zeros(m.nv))
+    qpos, qvel, ws = tpl
+    for t in range(50):
+        plant.set_state(qpos=qpos, qvel=qvel, qacc_warmstart=ws)
+        o = oracle.step(mb, qpos, qvel, ws)
+        plant.step()
+        qpos, qvel, ws = o["qpos"], o["qvel"], o["qacc_warmstart"]
+        np.testing.assert_allclose(plant.qpos, qpos, atol=1e-5, err_msg=f"step {t}")
+    print(f"fingers after 50 steps at ctrl 255: oracle {qpos[fq]}, plant {plant.qpos[fq]}")
+    assert (qpos[fq] > 0.015).all() and (plant.qpos[fq] > 0.015).all()  # (oracle: 0.01662; 3e-7 at ctrl 0)
+    # the model's own controls again: the untouched plant, bit for bit
+    plant.set_ctrl(None)
+    np.testing.assert_array_equal(plant.ctrl, [0.0])
+    plant.set_state(*tpl)
+    untouched.set_state(*tpl)
+    for _ in range(5):
+        plant.step()
+        untouched.step()
+        for a, b in ((plant.qpos, untouched.qpos), (plant.qvel, untouched.qvel), (plant.qacc, untouched.qacc)):
+            np.testing.assert_array_equal(a, b)
+    assert (np.abs(plant.qpos[fq]) < 1e-4).all()
+
+
+# ---------------------------------------------------------------------------
+# 8. the planner
+
+
+def _planner(**kw):
+    from manipulator_mujoco_amd.planner import cem_planner
+    args = dict(num_dof=6, num_batch=64, num_steps=12, timestep=0.05, maxiter_cem=2, num_elite=0.05, w_pos=20.0,
+                w_rot=3.0, w_col=80.0, maxiter_projection=10, verbose=False, model_path="dual_arm")
+    args.update(kw)
+    return cem_planner(**args)
+
+
+def test_planner_rolls_out_under_the_staged_controls(torch_cuda):
+    H = 12
+    graphed, eager = _planner(graph=True, actuator_ctrl=True), _planner(actuator_ctrl=True)
+    plain = _planner()
+    m = graphed.model
+    rng = np.random.default_rng(2)
+    tick = (rng.normal(0, 0.2, 66), Q0, np.zeros(6), np.zeros(6), pu.PT, pu.QT)
+    # the model's own controls staged (nothing passed yet): the planner without the flag
+    first = graphed.compute_cem(*tick)
+    _same(first, plain.compute_cem(*tick))
+    _same(first, eager.compute_cem(*tick))
+    assert graphed._graphs is not None and len(graphed._graphs) == 1
+    captured = graphed._graphs[0]
+    # C1 staged after capture: a replay of the same graph reads it
+    second = graphed.compute_cem(*tick, ctrl=c1())
+    assert graphed._graphs[0] is captured
+    assert not np.array_equal(second[0], first[0]) and not np.array_equal(second[5], first[5])
+    _same(second, eager.compute_cem(*tick, ctrl=c1()))
+    _same(second, graphed.compute_cem(*tick))  # None keeps what is staged
+    _selected_matches_oracle(with_ctrl(m, c1()), second, Q0, H)
+    with pytest.raises(ValueError, match="actuator_ctrl"):
+        plain.compute_cem(*tick, ctrl=c1())
+    with pytest.raises(ValueError, match="nu=14"):
+        graphed.compute_cem(*tick, ctrl=c1()[:13])
+
+
+def test_planner_batch_with_two_control_blocks_equals_two_planners(torch_cuda):
+    B = 2
+    batch = _planner(graph=True, actuator_ctrl=True, num_problems=B, seed_step=1, seed=5)
+    singles = [_planner(actuator_ctrl=True, seed=5 + p) for p in range(B)]
+    rng = np.random.default_rng(7)
+    other = c1()
+    other[6], other[7:13] = 20.0, other[7:13] - 0.3
+    blocks = [c1(), other]
+    tick = dict(xi_mean=rng.normal(0, 0.2, (B, 66)), init_pos=Q0 + rng.uniform(-0.05, 0.05, (B, 6)),
+                target_pos=pu.PT + rng.uniform(-0.1, 0.1, (B, 3)),
+                target_rot=np.array([[0.0, 1.0, 0.0, 0.0], [0.7071, 0.7071, 0.0, 0.0]]))
+    for ctrls in (blocks, None):  # (None: both blocks stay staged)
+        out = batch.compute_cem_batch(**tick, ctrls=ctrls)
+        for p in range(B):
+            ref = singles[p].compute_cem(tick["xi_mean"][p], tick["init_pos"][p], None, None, tick["target_pos"][p],
+                                         tick["target_rot"][p], ctrl=None if ctrls is None else blocks[p])
+            for j in range(9):
+                np.testing.assert_array_equal(np.asarray(out[j][p]), np.asarray(ref[j]), err_msg=f"entry {j} problem {p}")
+    with pytest.raises(ValueError, match="control blocks"):
+        batch.compute_cem_batch(**tick, ctrls=blocks[:1])
+
+
+# ---------------------------------------------------------------------------
+# 9. argument errors
+
+
+def test_ctrl_calls_validate_their_arguments(torch_cuda):
+    torch = torch_cuda
+    H, n = 8, 16
+    m, e = _engine("dual_arm", H, n)
+    lib = _lib.load()
+    z = lambda *s: torch.zeros(s, device="cuda")  # noqa: E731
+    xi, par, c, ctrl = z(n, 66), z(2, 20), z(n, 4), z(2, H, NU)
+    par[:] = dev(torch, Engine.params(Q0, pu.W, pu.PT, pu.QT))
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    F = _lib.MPCR_F_DEVICE_PTRS
+
+    def call(stride, step, eng=e, cp=None, flags=F):
+        return lib.mpcr_rollout_cost_ctrl(eng.handle, ptr(xi), MPCR_LAYOUT_XI, 2, n // 2, ptr(par), None, 0, None,
+                                          ptr(ctrl) if cp is None else cp, stride, step, ptr(c), None, None, None, 0,
+                                          None, flags, None)
+
+    EINVAL, EMODEL = -1, -2
+    assert call(0, 0) == 0 and call(NU, 0) == 0 and call(H * NU, NU) == 0 and call(0, NU) == 0
+    for bad in (1, NU - 1, -NU):
+        assert call(bad, 0) == EINVAL and b"ctrl_stride" in lib.mpcr_last_error()
+    for bad in (1, NU - 1, -NU):
+        assert call(0, bad) == EINVAL and b"ctrl_step_stride" in lib.mpcr_last_error()
+    # a schedule needs room for its H rows in the problem stride
+    for bad in (NU, (H - 1) * NU + NU - 1):
+        assert call(bad, NU) == EINVAL and b"ctrl_stride" in lib.mpcr_last_error()
+    host = np.zeros(2 * H * NU, dtype=np.float32)
+    assert call(0, 0, cp=host.ctypes.data_as(ctypes.c_void_p)) == EINVAL and b"device memory" in lib.mpcr_last_error()
+    assert call(0, 0, flags=0) == EINVAL and b"device pointers" in lib.mpcr_last_error()
+    torch.cuda.synchronize()
+    # a model without actuators
+    mn, en = _engine("scene_mjx", H, n)
+    assert en.nu == 0
+    assert call(0, 0, eng=en) == EINVAL and b"no actuators" in lib.mpcr_last_error()
+    with pytest.raises(_lib.MpcrError, match="no actuators"):
+        Plant(mn).set_ctrl(None)
+    # an implicitfast model whose D depends on the controls
+    mv = copy.deepcopy(m)
+    assert mv.integrator == 3 and mv.act_gaintype[6] == 1
+    mv.act_gainprm = np.array(mv.act_gainprm, dtype=np.float64)
+    mv.act_gainprm[6][2] = 0.5
+    _, _, Pd, _ = basis.planner_basis(H, 0.05)
+    ev = Engine(mv, H, n, Pd)
+    assert call(0, 0, eng=ev) == EMODEL and b"velocity-dependent" in lib.mpcr_last_error()
+    with pytest.raises(_lib.MpcrError, match="velocity-dependent"):
+        Plant(mv).set_ctrl(c1())
+    # shapes
+    for bad, kw in ((z(NU - 1), {}), (z(3, NU), {}), (z(2, H, NU), {}), (z(2, NU), dict(ctrl_per_step=True)),
+                    (z(2, H - 1, NU), dict(ctrl_per_step=True)), (np.zeros(NU, np.float32), {}),
+                    (torch.zeros(NU), {}), (z(NU).double(), {})):
+        with pytest.raises(ValueError, match="ctrl"):
+            e.rollout_cost_state(xi, MPCR_LAYOUT_XI, par, 2, c, ctrl=bad, **kw)
+    with pytest.raises(ValueError, match="nu=14"):
+        Plant(m).set_ctrl(np.zeros(NU + 1))
+    with pytest.raises(ValueError, match="no actuators"):
+        _planner(model_path="scene_mjx", actuator_ctrl=True)
+    torch.cuda.synchronize()
+
+
+# ---------------------------------------------------------------------------
+# 10. the closed loop
+
+
+def test_closed_loop_with_held_servos(torch_cuda):
+    """Three ticks of run_cem_planner on the dual arm, planning from the
+    plant's state with arm 1's servos given the plant's joint positions each
+    tick (--ctrl_hold): after every tick the plant's arm-1 joints are the first
+    step of a rollout of the applied velocity from the tick's state under the
+    tick's controls."""
+    torch = torch_cuda
+    from manipulator_mujoco_amd.mpc_planner import hold_ctrl, run_cem_planner
+    m = models.load("dual_arm", 0.05)
+    blk = Engine.state_layout()["size"]
+    hold = hold_ctrl(m, 6)
+    seen = {}
+
+    def ctrl(tick, plant):
+        c = hold(tick, plant)
+        seen[tick] = (plant.copy_state(torch.zeros(blk, device="cuda")), c.copy())
+        return c
+
+    ticks = 3
+    out = run_cem_planner(num_dof=6, num_batch=64, num_steps=12, maxiter_cem=2, maxiter_projection=10, w_pos=20.0,
+                          w_rot=3.0, w_col=80.0, num_elite=0.05, timestep=0.05, initial_qpos=list(Q0),
+                          target_names=["home"], show_viewer=False, save_data=False, max_ticks=ticks, verbose=False,
+                          model_path="dual_arm", plan_from_state=True, ctrl=ctrl, position_threshold=0.0)
+    assert len(out["theta"]) == ticks and sorted(seen) == list(range(ticks))
+    assert np.isfinite(np.asarray(out["theta"])).all() and np.isfinite(np.asarray(out["cost"], dtype=np.float64)).all()
+    qa = np.asarray(m.ctrl_qposadr[:6])
+    e = Engine(m, 1, 1, np.zeros((1, 11), dtype=np.float32))
+    for t in range(ticks):
+        start, c = seen[t]
+        S = unpack_state(m, start)
+        # the servos of the planned joints hold where the plant is, the rest keep the model's 0
+        np.testing.assert_array_equal(c[:6].astype(np.float32), S["qpos"][qa])
+        assert not c[6:].any()
+        o = _Out(torch, 1, 1, 1, blk)
+        par = dev(torch, Engine.params(S["qpos"][qa], pu.W, pu.PT, pu.QT))
+        e.rollout_cost_state(dev(torch, np.asarray(out["thetadot"][t]).reshape(1, 6)), MPCR_LAYOUT_THETADOT, par, 1, o.c,
+                             start=start, ctrl=dev(torch, c), **o.kw())
+        torch.cuda.synchronize()
+        clean(torch, o)
+        np.testing.assert_array_equal(np.asarray(out["theta"][t], dtype=np.float32), o.th.cpu().numpy()[0],
+                                      err_msg=f"tick {t}")

@@ -1,5 +1,10 @@
 """Time one libmpcr variant (path in argv[1]) on the C3 bench workload; prints
-median kernel ms over R repetitions (HIP events on the launch stream)."""
+median kernel ms over R repetitions (HIP events on the launch stream).
+MODEL / N / H choose the workload.  ENTRY=state times the device-parameter
+state entry (Engine.rollout_cost_state, one problem, no state blocks) instead
+of rollout_cost, with CTRL=none (no control block: runs on a library from
+before the control input too), const (one block of the model's own controls)
+or sched (one row per step)."""
 import os
 import sys
 
@@ -33,14 +38,28 @@ if os.environ.get("THETA", "1") == "0":  # traffic attribution: no theta / theta
     th = td = None
 key = torch.empty(1, dtype=torch.int64, device="cuda")
 args = (xi, MPCR_LAYOUT_XI, q0, (20., 3., 80.), (-0.3, -0.3, 0.5), (0., 1., 0., 0.))
+entry, ctrl_mode = os.environ.get("ENTRY", "cost"), os.environ.get("CTRL", "none")
+if entry == "state":
+    par = torch.as_tensor(Engine.params(*args[2:])).cuda()
+    ckw = {}
+    if ctrl_mode != "none":
+        own = torch.as_tensor(e.model.own_ctrl().astype(np.float32)).cuda()
+        ckw = dict(ctrl=own) if ctrl_mode == "const" else dict(ctrl=own.repeat(1, H, 1).contiguous(), ctrl_per_step=True)
+
+    def run(theta=None, thetadot=None, best_key=None, status=None):
+        e.rollout_cost_state(xi, MPCR_LAYOUT_XI, par, 1, c4, theta=theta, thetadot=thetadot, best_keys=best_key,
+                             status=status, **ckw)
+else:
+    def run(**kw):
+        e.rollout_cost(*args, cost4=c4, **kw)
 for _ in range(2):
-    e.rollout_cost(*args, cost4=c4, theta=th, thetadot=td, best_key=key)
+    run(theta=th, thetadot=td, best_key=key)
 torch.cuda.synchronize()
 ts = []
 for _ in range(int(os.environ.get("R", 10))):
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     a.record()
-    e.rollout_cost(*args, cost4=c4, theta=th, thetadot=td, best_key=key)
+    run(theta=th, thetadot=td, best_key=key)
     b.record()
     torch.cuda.synchronize()
     ts.append(a.elapsed_time(b))
@@ -53,11 +72,12 @@ if hasattr(lib, "mpcr_rollout_occupancy"):
     if lib.mpcr_rollout_occupancy(0, info) == 0:
         occ = (f" [narrow {info[0]} blocks/CU, {info[1]} B LDS, {info[2]} VGPR;"
                f" wide {info[3]} blocks/CU, {info[4]} B LDS, {info[5]} VGPR]")
-e.rollout_cost(*args, cost4=c4, theta=th, thetadot=td, best_key=key, status=st)
+run(theta=th, thetadot=td, best_key=key, status=st)
 sv = st.cpu().numpy()
 rows = f" rows/step {float((sv >> 11).mean()) / H:.1f} max-rows p50/p90/p99 " + "/".join(
     str(int(np.percentile((sv >> 2) & 255, q))) for q in (50, 90, 99))
-print(f"{os.path.basename(sys.argv[1])}{occ}{rows} {name} median {np.median(ts):.3f} ms min {np.min(ts):.3f} "
+tag = f" {entry}/ctrl={ctrl_mode}" if entry == "state" else ""
+print(f"{os.path.basename(sys.argv[1])}{tag}{occ}{rows} {name} {n}x{H} median {np.median(ts):.3f} ms min {np.min(ts):.3f} "
       f"-> {n / np.median(ts) * 1e3:.0f} rollouts/s  cost0 {float(c4[:, 0].sum()):.6e}")
 if os.environ.get("SAVE"):  # outputs of the last launch, for bitwise comparisons between variants
     np.savez(os.environ["SAVE"], c4=c4.cpu().numpy(), th=None if th is None else th.cpu().numpy(), st=sv)

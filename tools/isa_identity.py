@@ -9,7 +9,10 @@ that tree's own flags for the unit (hipcc --cuda-device-only -S), the lines
 naming __hip_cuid_ are dropped (the symbol hashes the source path: the only
 thing two builds of the same text differ in) and the rest is compared line by
 line.  Prints, per unit, `identical` or the first differing function and how
-many lines differ; exit status 1 on any difference.  No GPU needed.
+many lines differ; exit status 1 on any difference.  With --functions a unit
+that differs is also broken down by function: which ones differ, and whether
+in integer literals alone (a changed struct size or field offset folded into
+an instruction) or in their instructions.  No GPU needed.
 """
 import argparse
 import importlib.util
@@ -65,12 +68,63 @@ def first_function(old, new, old_path, new_path):
     return label, sum(ln[:1] in "<>" for ln in out.splitlines())
 
 
+_LABEL = re.compile(r"^([A-Za-z_$][\w.$]*):")
+_NUM = re.compile(r"(?<![\w.])(0x[0-9a-fA-F]+|\d+)(?![\w.])")
+
+
+def functions(lines):
+    """{label: its lines} for every global label of an assembly listing (local .L labels stay inside)."""
+    out, cur = {}, None
+    for ln in lines:
+        m = _LABEL.match(ln)
+        if m:
+            cur = m.group(1)
+            out[cur] = []
+        elif cur is not None:
+            out[cur].append(ln)
+    return out
+
+
+def per_function(old, new):
+    """Per function present in both listings and not line-for-line equal:
+    `literals` when the two differ in integer literals alone (same opcodes,
+    registers and order; the (old, new) literal pairs are listed), else
+    `DIFFERENT`.  Functions in only one listing are named."""
+    fo, fn = functions(old), functions(new)
+    rows = []
+    for name in fo:
+        if name not in fn:
+            rows.append((name, "only in old", ""))
+            continue
+        a, b = fo[name], fn[name]
+        if a == b:
+            continue
+        pairs = set()
+        same = len(a) == len(b)
+        for x, y in zip(a, b) if same else ():
+            if x == y:
+                continue
+            if _NUM.sub("#", x) != _NUM.sub("#", y):
+                same = False
+                break
+            pairs.update((p, q) for p, q in zip(_NUM.findall(x), _NUM.findall(y)) if p != q)
+        if same:
+            nd = sum(x != y for x, y in zip(a, b))
+            rows.append((name, "literals", f"{nd} of {len(a)} lines: " + ", ".join(f"{p}->{q}" for p, q in sorted(pairs))))
+        else:
+            rows.append((name, "DIFFERENT", f"{len(a)} vs {len(b)} lines"))
+    rows += [(name, "only in new", "") for name in fn if name not in fo]
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("old")
     ap.add_argument("new")
     ap.add_argument("--keep", help="write the assembly files here instead of a temporary directory")
     ap.add_argument("-j", type=int, default=3, help="compiles in flight")
+    ap.add_argument("--functions", action="store_true",
+                    help="for a unit that differs, also say per function how: integer literals alone, or more")
     a = ap.parse_args()
     old, new = unit_cmds(load_build(a.old)), unit_cmds(load_build(a.new))
     if len(old) != len(new):
@@ -90,6 +144,11 @@ def main():
                 label, ndiff = first_function(so, sn, os.path.join(d, f"old{i}.s"), os.path.join(d, f"new{i}.s"))
                 print(f"{names}: DIFFERENT, first in {label}, {ndiff} lines differ ({len(so)} vs {len(sn)} lines)")
                 bad = 1
+                if a.functions:
+                    rows = per_function(so, sn)
+                    for name, kind, detail in rows:
+                        print(f"  {name}: {kind}" + (f" ({detail})" if detail else ""))
+                    print(f"  every other function of the unit: identical")
     return bad
 
 
