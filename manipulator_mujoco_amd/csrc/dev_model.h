@@ -30,6 +30,7 @@ namespace mpcr {
 // compiler, at engine creation
 struct DevOptions {
   int newton_reuse = 1;             // MPCR_NEWTON_REUSE (0: the kernel's first Newton iteration recomputes)
+  int narrow_eager = 0;             // MPCR_NARROW_EAGER (1: contact geometry on every lane, not only the emitting ones)
   int m_slab = 0;                   // MPCR_M_SLAB (tests: the HBM-slab path on a model that fits)
   int w2_lead_max = W2_LEAD_MAX;    // MPCR_W2_LEAD_MAX
   uint64_t start_scramble = 0;      // mpcr_set_hull_start_scramble's seed (0: the extreme vertices)
@@ -279,7 +280,8 @@ inline int build_dev_model(const mpcr_model_t& m, const int32_t* lutadr, const D
   d.nctrl = m.nctrl;
   d.iterations = m.iterations;
   d.ls_iterations = m.ls_iterations;
-  d.disableflags = m.disableflags | (opt.newton_reuse ? 0 : DEV_NO_NEWTON_REUSE);
+  d.disableflags = m.disableflags | (opt.newton_reuse ? 0 : DEV_NO_NEWTON_REUSE) |
+                   (opt.narrow_eager ? DEV_NARROW_EAGER : 0);
   d.timestep = (float)m.timestep;
   d.tolerance = (float)m.tolerance;
   d.ls_tolerance = (float)m.ls_tolerance;

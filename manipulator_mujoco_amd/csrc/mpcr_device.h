@@ -55,6 +55,10 @@ enum { BK_STATIC = 0, BK_FREE = 1, BK_HINGE = 2, BK_SLIDE = 3, BK_WELD = 4 };
 // them, this engine-set one: Newton's first iteration recomputes what the
 // warm-start choice computed (rollout.hip; MPCR_NEWTON_REUSE=0, tests)
 constexpr int DEV_NO_NEWTON_REUSE = 1 << 30;
+// ... and this one: every lane with a capsule-box pair computes its contact
+// points and normals, not only the lanes that emit a contact (rollout.hip,
+// narrow_lane, single-arm kernels; MPCR_NARROW_EAGER=1, tests)
+constexpr int DEV_NARROW_EAGER = 1 << 29;
 
 struct DevModel {
   int nbody, njnt, nq, nv, ngeom, npair, neq, nslot;

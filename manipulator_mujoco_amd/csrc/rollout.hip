@@ -1742,16 +1742,25 @@ void poly_manifold_wave(const DevModel* __restrict__ m_, const S& s, PS& ps, con
 
 // per-lane narrow phase for plane/capsule/box-vs-capsule pairs (box-box is
 // wave-cooperative, below).  out: dist[4], pos[4][3], nrm[4][3]
+// Single-arm kernels: dist[] on every lane -- cost_c reads the distances --
+// and a capsule-box point's pos / nrm on demand: only where the point will be
+// emitted as a contact (its distance under the margin, contacts enabled); on
+// most steps no lane of the wave has one and the block is skipped.  With
+// DEV_NARROW_EAGER in the device model's flags (MPCR_NARROW_EAGER=1, tests)
+// every lane computes them.  rq: quads 0-1 of the pair's set-up record as the
+// chunk loop fetched them.
 template <class S>
 __device__ __forceinline__ int narrow_lane(const DevModel* __restrict__ m, const S& s, short* hints, int p, float dist[4],
-                            float pos[4][3], float nrm[4][3], float* dbg = nullptr) {
-  // single-arm kernels: function, geoms and both sizes from the pair's set-up
-  // record, three quads in one level (the model's arrays: pair -> geoms -> sizes)
+                            float pos[4][3], float nrm[4][3], float* dbg = nullptr,
+                            [[maybe_unused]] const float4* rq = nullptr) {
+  // single-arm kernels: function and geoms from the chunk loop's quads, both
+  // sizes from the record's other two (the model's arrays: pair -> geoms ->
+  // sizes; held from the chunk loop on they cost the one-wave kernel 6 VGPRs)
   [[maybe_unused]] float4 q0 = {0.f, 0.f, 0.f, 0.f};
   [[maybe_unused]] float sz1[3], sz2[3];
   if constexpr (kStepLoad<S>) {
     const StepPairSetup& ps = step_records(m)->pair[p];
-    q0 = recq(ps, 0);
+    q0 = rq[0];
     const float4 q2 = recq(ps, 2), q3 = recq(ps, 3);
     sz1[0] = q2.x; sz1[1] = q2.y; sz1[2] = q2.z;
     sz2[0] = q3.x; sz2[1] = q3.y; sz2[2] = q3.z;
@@ -1951,6 +1960,14 @@ __device__ __forceinline__ int narrow_lane(const DevModel* __restrict__ m, const
       for (int c = 0; c < 3; c++) pp[c] = a[c] + ts * dd[c];
       g = point_box(pp, h, nl, q);
     }
+    // which points get their pos / nrm (single-arm kernels; uniform parts first)
+    [[maybe_unused]] bool want_all = true, want_any = true;
+    [[maybe_unused]] float mg = 0.f;
+    if constexpr (!S::WIDE) {
+      want_all = (m->disableflags & DEV_NARROW_EAGER) != 0;
+      want_any = !(m->disableflags & 16);
+      mg = kStepLoad<S> ? rq[1].w : m->pair_margin[p];
+    }
     // the far end: on or in the box, the first point's face, the segment
     // clipped to the face's extent (the oracle's col_capsule_box, round 4);
     // outside, its own point_box
@@ -1990,14 +2007,27 @@ __device__ __forceinline__ int narrow_lane(const DevModel* __restrict__ m, const
           g = point_box(pp, h, nl, q);
         }
       }
-      float n[3], pl[3], tmp[3];
-      mv(n, R2, nl);
+      if constexpr (S::WIDE) {
+        float n[3], pl[3], tmp[3];
+        mv(n, R2, nl);
 #pragma unroll
-      for (int c = 0; c < 3; c++) pl[c] = 0.5f * (pp[c] + r * nl[c] + q[c]);
-      mv(tmp, R2, pl);
-      dist[k] = g - r;
+        for (int c = 0; c < 3; c++) pl[c] = 0.5f * (pp[c] + r * nl[c] + q[c]);
+        mv(tmp, R2, pl);
+        dist[k] = g - r;
 #pragma unroll
-      for (int c = 0; c < 3; c++) { pos[k][c] = tmp[c] + x2[c]; nrm[k][c] = n[c]; }
+        for (int c = 0; c < 3; c++) { pos[k][c] = tmp[c] + x2[c]; nrm[k][c] = n[c]; }
+      } else {
+        dist[k] = g - r;
+        if (want_all || (want_any && dist[k] < mg)) {
+          float n[3], pl[3], tmp[3];
+          mv(n, R2, nl);
+#pragma unroll
+          for (int c = 0; c < 3; c++) pl[c] = 0.5f * (pp[c] + r * nl[c] + q[c]);
+          mv(tmp, R2, pl);
+#pragma unroll
+          for (int c = 0; c < 3; c++) { pos[k][c] = tmp[c] + x2[c]; nrm[k][c] = n[c]; }
+        }
+      }
     }
     return 2;
   }
@@ -2414,16 +2444,16 @@ template <class S>
 __device__ __forceinline__ void emit_contacts(const DevModel* __restrict__ m, S& s, const RolloutArgs& args, int b,
                                               int t, int H, bool valid, int p, int nsl, const float dist[4],
                                               const float pos[4][3], const float nrm[4][3], float& cost_c,
-                                              SlotHist<S>& sh, int k) {
+                                              SlotHist<S>& sh, int k,
+                                              [[maybe_unused]] const float4* rq = nullptr) {
   int act = 0;
   if (valid) {
     // single-arm kernels: slot address, slot count and margin from the pair's
-    // set-up record, two quads fetched together
+    // set-up record, the two quads the chunk loop fetched (rq)
     float4 q0 = {0.f, 0.f, 0.f, 0.f}, q1 = q0;
     if constexpr (kStepLoad<S>) {
-      const StepPairSetup& ps = step_records(m)->pair[p];
-      q0 = recq(ps, 0);
-      q1 = recq(ps, 1);
+      q0 = rq[0];
+      q1 = rq[1];
     }
     const int sa = kStepLoad<S> ? __float_as_int(q0.y) : m->pair_slotadr[p];
     if (sa >= 0) {
@@ -3848,7 +3878,8 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
       const bool valid = p < m->npair;
       // single-arm kernels: the pair's set-up record (function, slot address,
       // geoms | geom types, bounding radii, margin), two quads fetched
-      // together in place of the chain pair -> geoms -> types / radii
+      // together in place of the chain pair -> geoms -> types / radii (the
+      // narrow phase and emit_contacts read these two as well)
       float4 ps0 = {0.f, 0.f, 0.f, 0.f}, ps1 = ps0;
       if constexpr (kStepLoad<S>) {
         if (valid) {
@@ -3912,10 +3943,11 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
       if (!do_narrow) continue;
       float dist[4] = {1e30f, 1e30f, 1e30f, 1e30f}, pos[4][3] = {}, nrm[4][3] = {};
       int nsl = 0;
-      if (run && func != 4 && !defer) nsl = narrow_lane(m, s, hx, p, dist, pos, nrm);
+      const float4 rq[2] = {ps0, ps1};
+      if (run && func != 4 && !defer) nsl = narrow_lane(m, s, hx, p, dist, pos, nrm, nullptr, rq);
       STAMP(11);
       const unsigned long long bbm = __ballot(run && func == 4);
-      emit_contacts(m, s, args, b, t, H, valid && func != 4 && !defer, p, nsl, dist, pos, nrm, cost_c, shist, k);
+      emit_contacts(m, s, args, b, t, H, valid && func != 4 && !defer, p, nsl, dist, pos, nrm, cost_c, shist, k, rq);
       STAMP(12);
       if (bbm && !(m->disableflags & 16)) {
         unsigned long long mm = bbm;

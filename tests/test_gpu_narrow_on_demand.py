@@ -1,0 +1,152 @@
+"""The single-arm kernels compute a pair's distances on every lane and a
+capsule-box point's contact position and normal only where the point is
+emitted as a contact (csrc/rollout.hip, narrow_lane).  An engine created with
+MPCR_NARROW_EAGER=1 computes them on every lane; both must give the same bits
+-- costs, theta, thetadot, status and final states -- on every single-arm
+scene and kernel variant.
+
+The candidates were chosen on the CPU with the fp64 oracle (oracle.rollout's
+slot distances) so that each batch holds candidate-steps in which a robot pair
+emits a contact (a slot distance under the pair's margin) and candidate-steps
+in which none does; the tests assert that on the engine's own traced slots."""
+import copy
+import os
+
+import numpy as np
+import pytest
+
+import parity_util as pu
+from manipulator_mujoco_amd import _lib, basis, models
+from manipulator_mujoco_amd.engine import MPCR_LAYOUT_THETADOT, MPCR_LAYOUT_XI, Engine
+from test_gpu_step_table import sine_thetadot
+
+pytestmark = pytest.mark.gpu
+
+Q0, W, PT, QT = pu.Q0, pu.W, pu.PT, pu.QT
+
+
+def _rows(*spans):
+    return np.concatenate([np.arange(a, b) for a, b in spans])
+
+
+# scene_mjx: rows of the bench's draw (4096 candidates, seed 20250632): the
+# first 233 whose oracle rollout has a robot contact and the batch's 23 that
+# have none (no slot within 1e-6 of its margin in either group)
+# (45, 67 and 117 among the first rows, the other 20 listed)
+SCENE_ROWS = np.concatenate([np.setdiff1d(np.arange(239), [74, 86, 136]),
+                             [265, 289, 498, 765, 871, 1280, 1466, 1524, 1800, 1824, 1856, 1938, 2498, 2697, 2985, 3032,
+                              3329, 3606, 3911, 4004]])
+# planner_scene: rows of 5 x sine_thetadot(512, 20, 0.05, 61), 64 with a contact and 64 without
+PLANNER_ROWS = _rows((0, 89), (103, 105), (110, 112), (115, 117), (118, 119), (123, 124), (128, 131), (135, 136),
+                     (139, 140), (143, 146), (154, 155), (156, 157), (158, 159), (161, 163), (174, 175), (177, 178),
+                     (182, 183), (186, 190), (191, 193), (200, 201), (209, 210), (221, 223), (224, 225), (232, 233),
+                     (238, 240), (243, 244))
+# ur5e_hande_mjx: rows of sine_thetadot(512, 20, 0.05, 67), 64 with a contact and 64 without
+UR5E_ROWS = _rows((0, 76), (81, 82), (83, 85), (90, 91), (92, 93), (94, 97), (98, 99), (102, 103), (108, 109), (116, 117),
+                  (119, 120), (125, 126), (134, 135), (140, 141), (148, 150), (152, 153), (156, 157), (161, 162),
+                  (163, 164), (171, 172), (176, 177), (180, 181), (191, 193), (194, 195), (203, 204), (227, 228),
+                  (229, 230), (231, 232), (233, 234), (237, 238), (240, 241), (242, 243), (245, 246), (257, 258),
+                  (271, 272), (275, 276), (284, 285), (288, 289), (292, 293), (302, 303), (305, 306), (309, 310),
+                  (314, 315), (318, 320), (322, 323), (327, 328), (334, 335))
+
+
+@pytest.fixture(scope="module")
+def torch_cuda():
+    import torch
+    assert torch.cuda.is_available(), "GPU tests need a GPU"
+    return torch
+
+
+@pytest.fixture(scope="module")
+def batches():
+    """name -> (input rows, layout, horizon), drawn once."""
+    import bench
+    out = {"scene_mjx": (bench.synthetic_xi(4096, 50, 20250629 + 3).numpy()[SCENE_ROWS], MPCR_LAYOUT_XI, 50),
+           "planner_scene": (5.0 * sine_thetadot(512, 20, 0.05, 61)[PLANNER_ROWS], MPCR_LAYOUT_THETADOT, 20),
+           "ur5e_hande_mjx": (sine_thetadot(512, 20, 0.05, 67)[UR5E_ROWS], MPCR_LAYOUT_THETADOT, 20)}
+    assert [v[0].shape[0] for v in out.values()] == [256, 128, 128]
+    return {k: (np.ascontiguousarray(v[0], dtype=np.float32),) + v[1:] for k, v in out.items()}
+
+
+def engine(m, H, n, eager):
+    """An engine with the geometry on demand (the default) or on every lane;
+    the variable is read when the engine is created."""
+    _, _, Pd, _ = basis.planner_basis(H, 0.05)
+    prev = os.environ.pop("MPCR_NARROW_EAGER", None)
+    try:
+        if eager:
+            os.environ["MPCR_NARROW_EAGER"] = "1"
+        return Engine(m, H, n, Pd)
+    finally:
+        os.environ.pop("MPCR_NARROW_EAGER", None)
+        if prev is not None:
+            os.environ["MPCR_NARROW_EAGER"] = prev
+
+
+def run(torch, e, inp, layout):
+    n, H = inp.shape[0], e.H
+    blk = e.state_layout()["size"]
+    c4 = torch.zeros((n, 4), device="cuda")
+    theta, thetadot = torch.zeros((n, 6 * H), device="cuda"), torch.zeros((n, 6 * H), device="cuda")
+    status = torch.zeros(n, dtype=torch.int32, device="cuda")
+    fin = torch.zeros((n, blk), device="cuda")
+    par = torch.as_tensor(Engine.params(Q0, W, PT, QT)).cuda()
+    e.rollout_cost_state(torch.as_tensor(inp).cuda(), layout, par, 1, c4, final_state=fin, theta=theta,
+                         thetadot=thetadot, status=status)
+    torch.cuda.synchronize()
+    return {"cost4": c4.cpu().numpy(), "theta": theta.cpu().numpy(), "thetadot": thetadot.cpu().numpy(),
+            "status": status.cpu().numpy(), "final_state": fin.cpu().numpy()}
+
+
+def slot_margins(m):
+    """The margin each cost slot's distance is held against (its pair's)."""
+    mg = np.zeros(m.nslot)
+    for p in range(m.npair):
+        sa = int(m.pair_slotadr[p])
+        if sa >= 0:
+            mg[sa:sa + int(m.pair_ncon[p])] = np.float32(m.pair_margin[p] - m.pair_gap[p])
+    return mg
+
+
+def both(torch, m, inp, layout, H, two_wave):
+    lib = _lib.load()
+    prev = lib.mpcr_set_two_wave_max_n(-1)
+    try:
+        lib.mpcr_set_two_wave_max_n(2048 if two_wave else 0)
+        lazy_e = engine(m, H, inp.shape[0], False)
+        lazy = run(torch, lazy_e, inp, layout)
+        eager = run(torch, engine(m, H, inp.shape[0], True), inp, layout)
+        slots = lazy_e.trace(inp, layout, Q0, W, PT, QT)["slots"]
+    finally:
+        lib.mpcr_set_two_wave_max_n(prev)
+    for k in lazy:
+        np.testing.assert_array_equal(lazy[k].view(np.int32), eager[k].view(np.int32), err_msg=k)
+    assert np.isfinite(lazy["cost4"]).all()
+    return lazy, slots
+
+
+@pytest.mark.parametrize("two_wave", [False, True])
+@pytest.mark.parametrize("name", ["scene_mjx", "planner_scene", "ur5e_hande_mjx"])
+def test_on_demand_is_bitwise(torch_cuda, batches, name, two_wave):
+    inp, layout, H = batches[name]
+    m = models.load(name, 0.05)
+    _, slots = both(torch_cuda, m, inp, layout, H, two_wave)
+    emits = (slots < slot_margins(m)).any(axis=2)  # (candidate, step): some robot pair emits a contact
+    print(f"{name}: {int(emits.sum())} of {emits.size} candidate-steps emit a robot contact, "
+          f"{int(emits.any(axis=1).sum())} of {emits.shape[0]} candidates")
+    # both paths are taken: a step in which a lane computes the geometry and a step that skips it
+    assert emits.any() and not emits.all(), (int(emits.sum()), emits.size)
+
+
+def test_contacts_off_keeps_the_slot_cost(torch_cuda, batches):
+    """disableflags & 16 (contacts off, cost slots on): no lane emits, so the
+    geometry is never computed; cost_c (cost4's last column) -- and every other
+    output -- equals the eager engine's, the slots still cost something, and
+    the rollouts are not those of the model with its contacts on."""
+    inp, layout, H = batches["scene_mjx"]
+    m = copy.deepcopy(models.load("scene_mjx", 0.05))
+    m.disableflags = int(m.disableflags) | 16
+    lazy, slots = both(torch_cuda, m, inp, layout, H, False)
+    assert (slots < slot_margins(m)).any() and (lazy["cost4"][:, 3] > 0).any()
+    on, _ = both(torch_cuda, models.load("scene_mjx", 0.05), inp[:16], layout, H, False)
+    assert not np.array_equal(on["cost4"], lazy["cost4"][:16])
