@@ -2458,6 +2458,33 @@ __device__ __forceinline__ void emit_contacts(const DevModel* __restrict__ m, S&
     const int sa = kStepLoad<S> ? __float_as_int(q0.y) : m->pair_slotadr[p];
     if (sa >= 0) {
       const int ns = kStepLoad<S> ? __float_as_int(q1.x) >> 16 : m->pair_ncon[p];
+      if constexpr (SlotHist<S>::NC == 2) {
+        // single-arm kernels: the chunk index is the wave's, so a scalar branch
+        // names the chunk's history registers (hv; null: the slab) where
+        // per-slot selects over k read and wrote them
+        auto slots = [&](float* hv) {
+#pragma unroll
+          for (int c = 0; c < 4; c++) {
+            if (c < ns) {
+              const float d = dist[c];
+              if (d < 0.f) cost_c += 1.f;
+              if (hv) {
+                if (t > 0) cost_c += fmaxf(hv[c] * (1.f - 0.005f) - d, 0.f);
+                hv[c] = d;
+              } else {
+                float* cp = args.slot_prev + (size_t)b * m->nslot;
+                if (t > 0) cost_c += fmaxf(cp[sa + c] * (1.f - 0.005f) - d, 0.f);
+                cp[sa + c] = d;
+              }
+              if (args.trace_slots && b < args.n) args.trace_slots[((size_t)b * H + t) * m->nslot + sa + c] = d;
+            }
+          }
+        };
+        const int ku = __builtin_amdgcn_readfirstlane(k);
+        if (ku == 0) slots(sh.v[0]);
+        else if (ku == 1) slots(sh.v[1]);
+        else slots(nullptr);
+      } else {
 #pragma unroll
       for (int c = 0; c < 4; c++) {
         if (c < ns) {
@@ -2477,6 +2504,7 @@ __device__ __forceinline__ void emit_contacts(const DevModel* __restrict__ m, S&
           }
           if (args.trace_slots && b < args.n) args.trace_slots[((size_t)b * H + t) * m->nslot + sa + c] = d;
         }
+      }
       }
     }
     if (!(m->disableflags & 16)) {
