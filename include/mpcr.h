@@ -117,6 +117,13 @@ int mpcr_model_info(const mpcr_model* m, int* nq, int* nv, int* nslot, int* nctr
 /* The model's actuators: their number, and (nullable) ctrlrange[nu][2] and
    limited[nu] (1 where the control is clamped to its range). */
 int mpcr_model_actuators(const mpcr_model* m, int* nu, double* ctrlrange, int* limited);
+/* The model's collision geoms as the device model orders them (the order of a
+   geom-pose block's rows, mpcr_rollout_cost_world): their number and, each
+   nullable, the model's own block[ngeom][8] (x y z 0 | qw qx qy qz, the world
+   pose of a static geom exactly as an engine of this model holds it; a moving
+   geom's row is 0 0 0 0 | 1 0 0 0 and is never read), model_geom_id[ngeom]
+   (row -> geom index in the model) and is_static[ngeom]. */
+int mpcr_model_geom_poses(const mpcr_model* m, int* ngeom, float* block, int* model_geom_id, int* is_static);
 void mpcr_model_free(mpcr_model* m);
 /* The support start table an engine builds for m's convex hulls (model
    format v9 dropped it from the blob; dev_model.h hull_start_table): R x R
@@ -280,6 +287,32 @@ int mpcr_rollout_cost_ctrl(mpcr_engine* e, const float* input, int layout, int n
                            float* thetadot, uint64_t* best_keys, int index_base, int* status, int flags,
                            void* stream);
 
+/* mpcr_rollout_cost_ctrl with the static collision geoms' world poses as an
+   input of the call (a backward-compatible addition; mpcr_rollout_cost_ctrl
+   is this call with geom_pose = NULL).  geom_pose (nullable): device memory,
+   16-byte aligned, blocks of ngeom rows of 8 floats in the order of
+   mpcr_model_geom_poses, row i = x y z 0 | qw qx qy qz: world position and
+   unit world quaternion, used as they are.  Only rows of static geoms are
+   read.  Step t of problem p reads the block at geom_pose + p geom_stride +
+   t geom_step_stride (strides in floats, multiples of 4): geom_stride = 0 is
+   one block for every problem, geom_step_stride = 0 one block for the whole
+   horizon; a non-zero step stride is at least 8 ngeom, and a non-zero
+   geom_stride holds what a problem reads (8 ngeom floats, or the H blocks of
+   its schedule: geom_step_stride (H - 1) + 8 ngeom).  What moves is the
+   collision geometry; tendon sites and equality anchors on static bodies
+   keep their model pose.  Read when the kernel runs (graph-capturable; a
+   replay sees new contents), never written.  Per problem, not per candidate.
+   A block holding the model's own values (mpcr_model_geom_poses) is bitwise
+   the call without one; a block taken from an edited model is bitwise an
+   engine made from that model.  geom_pose = NULL keeps the model's poses.
+   MPCR_EINVAL: a model without a static collision geom, host memory, a
+   misaligned pointer or stride, a stride out of range. */
+int mpcr_rollout_cost_world(mpcr_engine* e, const float* input, int layout, int nprob, int n_per,
+                            const float* params, const float* start, int start_stride, float* final_state,
+                            const float* ctrl, int ctrl_stride, int ctrl_step_stride, const float* geom_pose,
+                            int geom_stride, int geom_step_stride, float* cost4, float* theta, float* thetadot,
+                            uint64_t* best_keys, int index_base, int* status, int flags, void* stream);
+
 /* Closed-loop plant: one environment of the model, stepped by the rollout
    kernel (fp32 state resident on the device).  Created at the template
    state (qpos_init, qvel_init, zero warm start). */
@@ -306,6 +339,11 @@ int mpcr_plant_copy_state(mpcr_plant* p, float* d_dst, void* stream);
    where the model limits it; NULL restores the model's own.  Blocks until
    done.  Errors as mpcr_rollout_cost_ctrl's for the model. */
 int mpcr_plant_set_ctrl(mpcr_plant* p, const double* ctrl);
+/* The plant's static geom poses from now on: the static rows of a host
+   geom-pose block (mpcr_model_geom_poses' layout), used as they are; NULL
+   restores the model's own.  Blocks until done.  MPCR_EINVAL: a model without
+   a static collision geom. */
+int mpcr_plant_set_geom_poses(mpcr_plant* p, const float* block);
 
 /* argmin over cost[i*stride] with NaN-first / first-index semantics
    (jnp.argmin).  key_out (device, nullable) receives the packed key. */

@@ -41,6 +41,9 @@ EXPORTS += _STATE
 # actuator controls as a call input, likewise
 _CTRL = ("mpcr_rollout_cost_ctrl", "mpcr_plant_set_ctrl", "mpcr_model_actuators")
 EXPORTS += _CTRL
+# static geom poses as a call input, likewise
+_WORLD = ("mpcr_rollout_cost_world", "mpcr_plant_set_geom_poses", "mpcr_model_geom_poses")
+EXPORTS += _WORLD
 # the wave-reduction self-test, likewise
 _SELFTEST = ("mpcr_selftest_reduce",)
 EXPORTS += _SELFTEST
@@ -144,12 +147,18 @@ def load():
         lib.mpcr_rollout_cost_ctrl.argtypes = [vp, vp, i, i, i, vp, vp, i, vp, vp, i, i, vp, vp, vp, vp, i, vp, i, vp]
         lib.mpcr_plant_set_ctrl.argtypes = [vp, P(d)]
         lib.mpcr_model_actuators.argtypes = [vp, P(i), P(d), P(i)]
+    have_world = hasattr(lib, _WORLD[0])
+    if have_world:
+        lib.mpcr_rollout_cost_world.argtypes = [vp, vp, i, i, i, vp, vp, i, vp, vp, i, i, vp, i, i, vp, vp, vp, vp, i,
+                                                vp, i, vp]
+        lib.mpcr_plant_set_geom_poses.argtypes = [vp, P(f)]
+        lib.mpcr_model_geom_poses.argtypes = [vp, P(i), P(f), P(i), P(i)]
     have_selftest = hasattr(lib, _SELFTEST[0])
     if have_selftest:
         lib.mpcr_selftest_reduce.argtypes = [i, vp, i, vp]
     for name in EXPORTS + ("mpcr_rollout_trace", "mpcr_plant_step_debug", "mpcr_plant_dbg_size"):
         if (name in _MULTI and not have_multi) or (name in _STATE and not have_state) or (
-                name in _CTRL and not have_ctrl) or (
+                name in _CTRL and not have_ctrl) or (name in _WORLD and not have_world) or (
                 name in _SELFTEST and not have_selftest):
             continue
         if name not in _VOID:

@@ -255,6 +255,45 @@ inline bool implicit_D_reads_ctrl(const mpcr_model_t& m) {
   return false;
 }
 
+// World pose of static geom g (its body is welded to the world: f.dmap < 0)
+// as the kernel reads it: the body's constant world frame composed with the
+// geom's local pose in fp64, rounded once.  pos[0..2], quat[0..3].  The device
+// model's geom_pos / geom_quat rows and a call's geom-pose block
+// (model_geom_poses) both come from here.
+inline void static_geom_pose(const mpcr_model_t& m, const ModelFrames& f, int g, float* pos, float* quat) {
+  const int b = m.geom_bodyid[g];
+  double r[3], q[4];
+  step_detail::rot(r, f.wquat[b], m.geom_pos[g]);
+  step_detail::qmul(q, f.wquat[b], m.geom_quat[g]);
+  for (int k = 0; k < 3; k++) pos[k] = (float)(f.wpos[b][k] + r[k]);
+  for (int k = 0; k < 4; k++) quat[k] = (float)q[k];
+}
+
+// The model's own geom-pose block (rollout.h StateArgs::geom_pose): per
+// collision geom, in the device model's order (pair_geom_map), x y z 0 | qw qx
+// qy qz for a static geom and zeros | 1 0 0 0 for a moving one (never read).
+// block[ng][8], model_geom_id[ng], is_static[ng], each nullable; returns ng,
+// or -1 when the model exceeds the blob's capacities.
+inline int model_geom_poses(const mpcr_model_t& m, float* block, int* model_geom_id, int* is_static) {
+  ModelFrames f;
+  if (model_frames(m, f) != 0) return -1;
+  int gmap[MPCR_MAX_GEOM];
+  const int ng = pair_geom_map(m, gmap);
+  for (int g = 0; g < m.ngeom; g++) {
+    const int i = gmap[g];
+    if (i < 0) continue;
+    const bool fixed = f.dmap[m.geom_bodyid[g]] < 0;
+    if (model_geom_id) model_geom_id[i] = g;
+    if (is_static) is_static[i] = fixed;
+    if (!block) continue;
+    float* row = block + 8 * (size_t)i;
+    for (int k = 0; k < 8; k++) row[k] = 0.f;
+    row[4] = 1.f;
+    if (fixed) static_geom_pose(m, f, g, row, row + 4);
+  }
+  return ng;
+}
+
 // Fills d (its table pointers stay null: mpcr_engine_create sets them to the
 // uploaded DevTables) or returns the refusal's code with its message in err.
 // lutadr[ngeom]: hull_start_table's geom_adr.
@@ -482,11 +521,7 @@ inline int build_dev_model(const mpcr_model_t& m, const int32_t* lutadr, const D
       for (int k = 0; k < 4; k++) d.geom_quat[i][k] = (float)m.geom_quat[g][k];
     } else {  // static geom: store its world pose
       d.geom_body[i] = -1;
-      double r[3], q[4];
-      step_detail::rot(r, f.wquat[b], m.geom_pos[g]);
-      step_detail::qmul(q, f.wquat[b], m.geom_quat[g]);
-      for (int k = 0; k < 3; k++) d.geom_pos[i][k] = (float)(f.wpos[b][k] + r[k]);
-      for (int k = 0; k < 4; k++) d.geom_quat[i][k] = (float)q[k];
+      static_geom_pose(m, f, g, d.geom_pos[i], d.geom_quat[i]);
     }
   }
   // pairs

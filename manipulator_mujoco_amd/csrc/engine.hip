@@ -321,6 +321,15 @@ extern "C" int mpcr_model_actuators(const mpcr_model* m, int* nu, double* ctrlra
   return MPCR_OK;
 }
 
+extern "C" int mpcr_model_geom_poses(const mpcr_model* m, int* ngeom, float* block, int* model_geom_id,
+                                     int* is_static) {
+  if (!m) return fail(MPCR_EINVAL, "null model");
+  const int ng = model_geom_poses(m->m, block, model_geom_id, is_static);
+  if (ng < 0) return fail(MPCR_EMODEL, "model exceeds blob capacity");
+  if (ngeom) *ngeom = ng;
+  return MPCR_OK;
+}
+
 extern "C" void mpcr_model_free(mpcr_model* m) { delete m; }
 
 // the support start table's scramble seed (dev_model.h hull_start_table; the
@@ -505,6 +514,9 @@ struct Launch {
   // the call's control block per problem and, optionally, per step (strides in floats; StateArgs)
   const float* ctrl = nullptr;
   int ctrl_stride = 0, ctrl_step_stride = 0;
+  // the call's geom-pose block, addressed likewise (StateArgs)
+  const float* geom_pose = nullptr;
+  int geom_stride = 0, geom_step_stride = 0;
 };
 
 // the kernel's arguments for launch l of engine e (the one place they are filled)
@@ -546,10 +558,11 @@ static int rollout_args(const mpcr_engine* e, const Launch& l, RolloutArgs& a) {
   // bytes (rollout.h; null pointers when it has no state blocks) and never
   // parameter values, so has_state() cannot read those as pointers
   if (l.dpar) {
-    set_state_args(a, StateArgs{l.start, l.final_state, l.start_stride, l.ctrl_stride, l.ctrl_step_stride, l.ctrl});
+    set_state_args(a, StateArgs{l.start, l.final_state, l.start_stride, l.ctrl_stride, l.ctrl_step_stride, l.ctrl,
+                                l.geom_pose, l.geom_stride, l.geom_step_stride});
   } else {
-    if (l.start || l.final_state || l.ctrl)
-      return fail(MPCR_EINVAL, "state and control blocks need a device parameter block");
+    if (l.start || l.final_state || l.ctrl || l.geom_pose)
+      return fail(MPCR_EINVAL, "state, control and geom-pose blocks need a device parameter block");
     std::memcpy(a.par, l.par, sizeof(a.par));
   }
   return MPCR_OK;
@@ -652,7 +665,8 @@ static int rollout_dp(mpcr_engine* e, const float* input, int layout, int nprob,
                       float* cost4, float* theta, float* thetadot, uint64_t* best_keys, int index_base, int* status,
                       int flags, void* stream, const float* start = nullptr, int start_stride = 0,
                       float* final_state = nullptr, const float* ctrl = nullptr, int ctrl_stride = 0,
-                      int ctrl_step_stride = 0) {
+                      int ctrl_step_stride = 0, const float* geom_pose = nullptr, int geom_stride = 0,
+                      int geom_step_stride = 0) {
   if (layout != MPCR_LAYOUT_XI && layout != MPCR_LAYOUT_THETADOT) return fail(MPCR_EINVAL, "bad layout %d", layout);
   if (n_per == 0) return MPCR_OK;  // an empty batch: the buffers may be null
   if (!input || !params || !cost4) return fail(MPCR_EINVAL, "null argument");
@@ -666,6 +680,7 @@ static int rollout_dp(mpcr_engine* e, const float* input, int layout, int nprob,
   l.reset_key = (flags & MPCR_F_RESET_BEST) != 0;
   l.start = start; l.start_stride = start_stride; l.final_state = final_state;
   l.ctrl = ctrl; l.ctrl_stride = ctrl_stride; l.ctrl_step_stride = ctrl_step_stride;
+  l.geom_pose = geom_pose; l.geom_stride = geom_stride; l.geom_step_stride = geom_step_stride;
   int rc = launch_rollout(e, l, st);
   if (rc) return rc;
   if (flags & MPCR_F_SYNC) HIPCHK(hipStreamSynchronize(st));
@@ -711,11 +726,20 @@ static int check_ctrl_model(const mpcr_model_t& h) {
   return MPCR_OK;
 }
 
-extern "C" int mpcr_rollout_cost_ctrl(mpcr_engine* e, const float* input, int layout, int nprob, int n_per,
-                                      const float* params, const float* start, int start_stride, float* final_state,
-                                      const float* ctrl, int ctrl_stride, int ctrl_step_stride, float* cost4,
-                                      float* theta, float* thetadot, uint64_t* best_keys, int index_base, int* status,
-                                      int flags, void* stream) {
+// Whether a device model has a static collision geom: a row a geom-pose block
+// (a call's, mpcr_plant_set_geom_poses') could replace.
+static int check_geom_pose_model(const DevModel& d) {
+  for (int i = 0; i < d.ngeom; i++)
+    if (d.geom_body[i] < 0) return MPCR_OK;
+  return fail(MPCR_EINVAL, "geom_pose: the model has no static collision geom");
+}
+
+extern "C" int mpcr_rollout_cost_world(mpcr_engine* e, const float* input, int layout, int nprob, int n_per,
+                                       const float* params, const float* start, int start_stride, float* final_state,
+                                       const float* ctrl, int ctrl_stride, int ctrl_step_stride,
+                                       const float* geom_pose, int geom_stride, int geom_step_stride, float* cost4,
+                                       float* theta, float* thetadot, uint64_t* best_keys, int index_base, int* status,
+                                       int flags, void* stream) {
   if (!e) return fail(MPCR_EINVAL, "null argument");
   if (!(flags & MPCR_F_DEVICE_PTRS)) return fail(MPCR_EINVAL, "mpcr_rollout_cost_state takes device pointers");
   if (int rc = check_multi(nprob, n_per, e->max_n)) return rc;
@@ -741,9 +765,44 @@ extern "C" int mpcr_rollout_cost_ctrl(mpcr_engine* e, const float* input, int la
       return fail(MPCR_EINVAL, "ctrl must be device memory on the engine's device %d", e->device);
     }
   }
+  if (geom_pose) {
+    const int blk = 8 * e->dev.ngeom;  // floats of one block
+    if (int rc = check_geom_pose_model(e->dev)) return rc;
+    if ((reinterpret_cast<uintptr_t>(geom_pose) & 15) || (geom_stride & 3) || (geom_step_stride & 3))
+      return fail(MPCR_EINVAL, "geom_pose=%p, geom_stride=%d, geom_step_stride=%d: rows are 16-byte aligned "
+                               "(strides are multiples of 4 floats)",
+                  (const void*)geom_pose, geom_stride, geom_step_stride);
+    if (geom_step_stride != 0 && geom_step_stride < blk)
+      return fail(MPCR_EINVAL, "geom_step_stride=%d: 0 (constant over the horizon) or at least a block's 8 ngeom=%d "
+                               "floats",
+                  geom_step_stride, blk);
+    const long long rows = geom_step_stride ? (long long)geom_step_stride * (e->H - 1) + blk : blk;  // floats one problem reads
+    if (geom_stride != 0 && geom_stride < rows)
+      return fail(MPCR_EINVAL, "geom_stride=%d: 0 (one block for every problem) or at least the %lld floats a "
+                               "problem reads (ngeom=%d, geom_step_stride=%d, H=%d)",
+                  geom_stride, rows, e->dev.ngeom, geom_step_stride, e->H);
+    // read by the kernel when it runs: it must be device memory on the engine's device
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, geom_pose) != hipSuccess || at.type != hipMemoryTypeDevice ||
+        at.device != e->device) {
+      (void)hipGetLastError();
+      return fail(MPCR_EINVAL, "geom_pose must be device memory on the engine's device %d", e->device);
+    }
+  }
   return rollout_dp(e, input, layout, nprob, n_per, params, cost4, theta, thetadot, best_keys, index_base, status,
                     flags, stream, start, start ? start_stride : 0, final_state, ctrl, ctrl ? ctrl_stride : 0,
-                    ctrl ? ctrl_step_stride : 0);
+                    ctrl ? ctrl_step_stride : 0, geom_pose, geom_pose ? geom_stride : 0,
+                    geom_pose ? geom_step_stride : 0);
+}
+
+extern "C" int mpcr_rollout_cost_ctrl(mpcr_engine* e, const float* input, int layout, int nprob, int n_per,
+                                      const float* params, const float* start, int start_stride, float* final_state,
+                                      const float* ctrl, int ctrl_stride, int ctrl_step_stride, float* cost4,
+                                      float* theta, float* thetadot, uint64_t* best_keys, int index_base, int* status,
+                                      int flags, void* stream) {
+  return mpcr_rollout_cost_world(e, input, layout, nprob, n_per, params, start, start_stride, final_state, ctrl,
+                                 ctrl_stride, ctrl_step_stride, nullptr, 0, 0, cost4, theta, thetadot, best_keys,
+                                 index_base, status, flags, stream);
 }
 
 extern "C" int mpcr_rollout_cost_state(mpcr_engine* e, const float* input, int layout, int nprob, int n_per,
@@ -859,6 +918,31 @@ extern "C" int mpcr_plant_set_ctrl(mpcr_plant* p, const double* ctrl) {
   static_assert(sizeof(e->dev.act_gain) == sizeof(float) * 4 * DX_NU, "act_gain rows");
   HIPCHK(hipMemcpy(reinterpret_cast<char*>(e->d_model) + offsetof(DevModel, act_gain), e->dev.act_gain,
                    sizeof(e->dev.act_gain), hipMemcpyHostToDevice));
+  return MPCR_OK;
+}
+
+// The plant's static geom poses: the static rows of a geom-pose block written
+// into the plant's engine's device copy of geom_pos / geom_quat, which the
+// kernels that step the plant read.  NULL: the model's own again.
+extern "C" int mpcr_plant_set_geom_poses(mpcr_plant* p, const float* block) {
+  if (!p) return fail(MPCR_EINVAL, "null plant");
+  mpcr_engine* e = p->e;
+  if (int rc = check_geom_pose_model(e->dev)) return rc;
+  float own[8 * DX_NG];
+  if (!block) {
+    if (model_geom_poses(e->host, own, nullptr, nullptr) != e->dev.ngeom) return fail(MPCR_EMODEL, "geom count");
+    block = own;
+  }
+  HIPCHK(hipSetDevice(e->device));
+  for (int i = 0; i < e->dev.ngeom; i++) {
+    if (e->dev.geom_body[i] >= 0) continue;
+    for (int k = 0; k < 3; k++) e->dev.geom_pos[i][k] = block[8 * i + k];
+    for (int k = 0; k < 4; k++) e->dev.geom_quat[i][k] = block[8 * i + 4 + k];
+  }
+  static_assert(offsetof(DevModel, geom_quat) == offsetof(DevModel, geom_pos) + sizeof(e->dev.geom_pos),
+                "geom_pos | geom_quat adjacent");
+  HIPCHK(hipMemcpy(reinterpret_cast<char*>(e->d_model) + offsetof(DevModel, geom_pos), e->dev.geom_pos,
+                   sizeof(e->dev.geom_pos) + sizeof(e->dev.geom_quat), hipMemcpyHostToDevice));
   return MPCR_OK;
 }
 

@@ -121,14 +121,24 @@ struct RolloutArgs {
 // p ctrl_stride + t ctrl_step_stride: stride 0 is one block for every problem,
 // step stride 0 one block for the whole horizon.  Per problem like start, so
 // group_args leaves it alone too.  Only the dual-arm class has actuators.
+// geom_pose (nullable): the static collision geoms' world poses as an input
+// of the call, a block of DevModel::ngeom rows of 8 floats in the device
+// model's geom order, x y z 0 | qw qx qy qz, rows 16-byte aligned; only rows
+// of static geoms (geom_body < 0) are read, and used as they are where the
+// kernel otherwise takes DevModel::geom_pos / geom_quat.  Addressed like
+// ctrl: step t (absolute) of problem p reads the block at geom_pose + p
+// geom_stride + t geom_step_stride (floats, multiples of 4).  Per problem, so
+// group_args leaves it alone.
 struct StateArgs {
   const float* start;
   float* final_state;
   int start_stride;
   int ctrl_stride, ctrl_step_stride;
   const float* ctrl;
+  const float* geom_pose;
+  int geom_stride, geom_step_stride;
 };
-static_assert(sizeof(StateArgs) <= 40, "StateArgs: 40 of par's 80 bytes");
+static_assert(sizeof(StateArgs) <= 56, "StateArgs: 56 of par's 80 bytes");
 static_assert(sizeof(StateArgs) <= sizeof(float) * PAR_N, "StateArgs inside par");
 __host__ __device__ inline StateArgs state_args(const RolloutArgs& a) {
   StateArgs s;
@@ -136,11 +146,12 @@ __host__ __device__ inline StateArgs state_args(const RolloutArgs& a) {
   return s;
 }
 inline void set_state_args(RolloutArgs& a, const StateArgs& s) { __builtin_memcpy(a.par, &s, sizeof(s)); }
-// whether a launch starts from, or returns, state blocks, or reads a control block
+// whether a launch starts from, or returns, state blocks, or reads a control
+// or geom-pose block
 inline bool has_state(const RolloutArgs& a) {
   if (!a.dpar) return false;
   const StateArgs s = state_args(a);
-  return s.start || s.final_state || s.ctrl;
+  return s.start || s.final_state || s.ctrl || s.geom_pose;
 }
 
 // Per-block LDS image, sized by the kernel variant: NVW = dense-solve width

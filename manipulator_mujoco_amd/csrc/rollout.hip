@@ -2889,7 +2889,7 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
     rollout_kernel(RolloutArgs args, const DevModel* __restrict__ mptr) {
   static_assert(WPC == 1 || WPC == 2, "waves per candidate");
   static_assert(MULTI || !STATE, "the STATE instantiations look the problem's start block up");
-  StateArgs sa = {nullptr, nullptr, 0, 0, 0, nullptr};
+  StateArgs sa = {nullptr, nullptr, 0, 0, 0, nullptr, nullptr, 0, 0};
   if constexpr (STATE) sa = state_args(args);
   using S = typename std::conditional<WIDE, typename std::conditional<WPC == 2, SmemW2, SmemW>::type,
                                       typename std::conditional<WPC == 2, SmemN2, SmemN>::type>::type;
@@ -3140,6 +3140,14 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
   if constexpr (STATE && S::WIDE) {
     if (sa.ctrl) ctrl_p = sa.ctrl + (size_t)(args.prob_n ? (args.prob_off + b) / args.prob_n : 0) * sa.ctrl_stride;
   }
+  // STATE: the problem's geom-pose block (StateArgs::geom_pose; null: the
+  // model's own static poses, geom_pos / geom_quat).  Wave-uniform, a scalar
+  // pair; the rows themselves are loaded again every step.
+  const float* gpose_p = nullptr;
+  if constexpr (STATE) {
+    if (sa.geom_pose)
+      gpose_p = sa.geom_pose + (size_t)(args.prob_n ? (args.prob_off + b) / args.prob_n : 0) * sa.geom_stride;
+  }
   PROF_DECL
   unsigned* pace = nullptr;
   int pace_own = 0;
@@ -3275,6 +3283,21 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
 
     STAMP(0);
     STOP_AT(0)
+    // the call's pose of this lane's static geom for this step (STATE): in the
+    // single-arm kernels its two rows are issued ahead of the kinematics and
+    // consumed in the geom phase after them; the dual-arm kernels, at their
+    // register limit, load them there (measured: no change against the parent,
+    // where the early load cost them 0.3 - 0.6 % at 4096 x 50)
+    float4 gpp = {0.f, 0.f, 0.f, 0.f}, gpq = {1.f, 0.f, 0.f, 0.f};
+    bool gp_row = false;
+    if constexpr (STATE && !S::WIDE) {
+      if (gpose_p && lane < m->ngeom && m->geom_body[lane] < 0) {
+        const float4* row = reinterpret_cast<const float4*>(gpose_p + (size_t)t * sa.geom_step_stride) + 2 * lane;
+        gpp = row[0];
+        gpq = row[1];
+        gp_row = true;
+      }
+    }
     // ---- kinematics: local pose per body, then pointer jumping ----------------
     {
       float q[4] = {1.f, 0.f, 0.f, 0.f}, p[3] = {0.f, 0.f, 0.f};
@@ -3406,11 +3429,25 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
     if (lane < m->ngeom) {
       const int gb = m->geom_body[lane];
       float gq[4] = {m->geom_quat[lane][0], m->geom_quat[lane][1], m->geom_quat[lane][2], m->geom_quat[lane][3]};
+      if constexpr (STATE && S::WIDE) {
+        if (gpose_p && gb < 0) {
+          const float4* row = reinterpret_cast<const float4*>(gpose_p + (size_t)t * sa.geom_step_stride) + 2 * lane;
+          gpp = row[0];
+          gpq = row[1];
+          gp_row = true;
+        }
+      }
+      if constexpr (STATE) {
+        if (gp_row) { gq[0] = gpq.x; gq[1] = gpq.y; gq[2] = gpq.z; gq[3] = gpq.w; }  // the call's, as it is
+      }
       float Rg[9];
       q2m(Rg, gq);
       if (gb < 0) {
         s.gxpos[lane][0] = m->geom_pos[lane][0]; s.gxpos[lane][1] = m->geom_pos[lane][1];
         s.gxpos[lane][2] = m->geom_pos[lane][2];
+        if constexpr (STATE) {
+          if (gp_row) { s.gxpos[lane][0] = gpp.x; s.gxpos[lane][1] = gpp.y; s.gxpos[lane][2] = gpp.z; }
+        }
 #pragma unroll
         for (int k = 0; k < 9; k++) s.gxmat[lane][k] = Rg[k];
       } else {

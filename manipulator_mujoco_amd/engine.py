@@ -72,6 +72,54 @@ class Model:
         c = np.array(ctrl, dtype=np.float64).reshape(-1)[:nu]
         return np.where(lim, np.clip(c, rng[:, 0], rng[:, 1]), c)
 
+    def geom_poses(self):
+        """``mpcr_model_geom_poses``: (block (ng, 8) float32, model_geom_ids
+        (ng,), is_static (ng,) bool) -- the model's own geom-pose block in the
+        device model's geom order, row ``x y z 0 | qw qx qy qz``, exactly the
+        static poses an engine of this model holds."""
+        lib = _lib.load()
+        ng = ctypes.c_int()
+        check(lib.mpcr_model_geom_poses(self.handle, ctypes.byref(ng), None, None, None))
+        n = max(ng.value, 1)
+        block = np.zeros((n, 8), dtype=np.float32)
+        ids, fixed = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        ip = ctypes.POINTER(ctypes.c_int)
+        check(lib.mpcr_model_geom_poses(self.handle, None, _f32p(block), ids.ctypes.data_as(ip),
+                                        fixed.ctypes.data_as(ip)))
+        return block[:ng.value], ids[:ng.value], fixed[:ng.value].astype(bool)
+
+    def geom_row(self, name_or_id):
+        """The geom-pose block's row of a model geom, by name or model geom id."""
+        g = name_or_id
+        if isinstance(g, str):
+            names = self.compiled.names["geom"]
+            found = [i for i, n in (names.items() if isinstance(names, dict) else enumerate(names)) if n == g]
+            if not found:
+                raise KeyError(f"no geom named {g!r}")
+            g = int(found[0])
+        _, ids, _ = self.geom_poses()
+        rows = np.nonzero(ids == int(g))[0]
+        if rows.size == 0:
+            raise KeyError(f"geom {name_or_id!r} is in no collision pair: it has no row")
+        return int(rows[0])
+
+    def pose_rows(self, block, poses):
+        """A copy of ``block`` (..., ng, 8) with the rows of ``poses`` = {geom
+        name or id: (pos, quat)} replaced: the world position and quaternion
+        (w x y z), normalised in fp64 and rounded to fp32 once.  Only static
+        geoms have a row that is read."""
+        out = np.array(block, dtype=np.float32, copy=True)
+        _, _, fixed = self.geom_poses()
+        for key, (pos, quat) in poses.items():
+            r = self.geom_row(key)
+            if not fixed[r]:
+                raise ValueError(f"geom {key!r} is not static: its row is not read")
+            q = np.asarray(quat, dtype=np.float64).reshape(4)
+            out[..., r, 0:3] = np.asarray(pos, dtype=np.float64).reshape(3)
+            out[..., r, 3] = 0.0
+            out[..., r, 4:8] = q / np.sqrt(np.sum(q * q))
+        return out
+
     def __del__(self):
         try:
             if getattr(self, "handle", None):
@@ -122,6 +170,7 @@ class Engine:
         self.nctrl = int(compiled_model.nctrl)
         self.nslot = int(compiled_model.nslot)
         self.nu = int(getattr(compiled_model, "nu", 0))
+        self._ngeom = None
         pdot = np.ascontiguousarray(pdot, dtype=np.float32)
         if pdot.shape[0] != self.H:
             raise ValueError(f"pdot has {pdot.shape[0]} rows, expected num_steps={self.H}")
@@ -226,7 +275,8 @@ class Engine:
         return pack_state(self.model.compiled, qpos, qvel, qacc_warmstart)
 
     def _rollout_dp(self, nprob, inp, layout, params, cost4, theta, thetadot, best_keys, index_base, status,
-                    reset_best, stream, state=None, ctrl=None, ctrl_per_step=False):
+                    reset_best, stream, state=None, ctrl=None, ctrl_per_step=False, geom_pose=None,
+                    geom_pose_per_step=False):
         """nprob None: ``rollout_cost_dp`` (its own C entry, which takes an
         empty batch); else ``rollout_cost_multi`` or, with state = (start,
         final_state), ``rollout_cost_state``."""
@@ -264,6 +314,11 @@ class Engine:
             if ctrl is not None:
                 extra += self._ctrl_args(ctrl, ctrl_per_step, nprob, inp.device)
                 fn = lib.mpcr_rollout_cost_ctrl
+            if geom_pose is not None:
+                if ctrl is None:
+                    extra += (None, 0, 0)
+                extra += self._geom_pose_args(geom_pose, geom_pose_per_step, nprob, inp.device)
+                fn = lib.mpcr_rollout_cost_world
         st = stream if stream is not None else torch.cuda.current_stream(inp.device).cuda_stream
         flags = MPCR_F_DEVICE_PTRS | (MPCR_F_RESET_BEST if reset_best else 0)
         check(fn(self.handle, ptr(inp), layout, *shape, ptr(params), *extra, ptr(cost4), ptr(theta), ptr(thetadot),
@@ -291,6 +346,32 @@ class Engine:
             return ctypes.c_void_p(ctrl.data_ptr()), self.H * nu, nu
         return ctypes.c_void_p(ctrl.data_ptr()), nu if ctrl.dim() == 2 and nprob > 1 else 0, 0
 
+    @property
+    def ngeom(self):
+        """The device model's collision geoms: the rows of a geom-pose block."""
+        if self._ngeom is None:
+            self._ngeom = int(self.model.geom_poses()[0].shape[0])
+        return self._ngeom
+
+    def _geom_pose_args(self, gp, per_step, nprob, device):
+        """(pointer, problem stride, step stride) of a geom-pose tensor: (ng, 8),
+        (nprob, ng, 8) or, per_step, (nprob, H, ng, 8)."""
+        import torch
+        if (not isinstance(gp, torch.Tensor) or not gp.is_cuda or gp.dtype != torch.float32
+                or not gp.is_contiguous() or gp.device != device):
+            raise ValueError("geom_pose must be a contiguous float32 CUDA tensor on the input's device")
+        ng = self.ngeom
+        if per_step:
+            shape_ok = tuple(gp.shape) == (nprob, self.H, ng, 8)
+        else:
+            shape_ok = tuple(gp.shape) in ((ng, 8), (nprob, ng, 8))
+        if not shape_ok:
+            raise ValueError(f"geom_pose must be ({ng}, 8) or ({nprob}, {ng}, 8), or with geom_pose_per_step "
+                             f"({nprob}, {self.H}, {ng}, 8); got {tuple(gp.shape)}")
+        if per_step:
+            return ctypes.c_void_p(gp.data_ptr()), self.H * ng * 8, ng * 8
+        return ctypes.c_void_p(gp.data_ptr()), ng * 8 if gp.dim() == 3 and nprob > 1 else 0, 0
+
     def rollout_cost_dp(self, inp, layout: int, params, cost4, theta=None, thetadot=None, best_key=None,
                         index_base: int = 0, status=None, reset_best: bool = True, stream=None):
         """``rollout_cost`` with the per-call arguments in a device tensor
@@ -312,7 +393,8 @@ class Engine:
 
     def rollout_cost_state(self, inp, layout: int, params, nprob: int, cost4, start=None, final_state=None,
                            theta=None, thetadot=None, best_keys=None, index_base: int = 0, status=None,
-                           reset_best: bool = True, stream=None, ctrl=None, ctrl_per_step: bool = False):
+                           reset_best: bool = True, stream=None, ctrl=None, ctrl_per_step: bool = False,
+                           geom_pose=None, geom_pose_per_step: bool = False):
         """``rollout_cost_multi`` from a given full state and / or returning
         the final states (``mpcr_rollout_cost_state``).  ``start``: a device
         tensor of one state block (``pack_state``, ``Plant.copy_state``) shared
@@ -326,10 +408,17 @@ class Engine:
         as a device tensor in actuator order, (nu,) for every problem or
         (nprob, nu) with one block per problem, or with ``ctrl_per_step``
         (nprob, H, nu), one row per step; clamped to the model's ctrlrange in
-        the kernel and read when it runs.  None keeps the model's own."""
+        the kernel and read when it runs.  None keeps the model's own.
+        ``geom_pose`` (``mpcr_rollout_cost_world``): the static collision
+        geoms' world poses as a device tensor of geom-pose blocks
+        (``Model.geom_poses``, ``Model.pose_rows``), (ng, 8) for every problem
+        or (nprob, ng, 8) with one block per problem, or with
+        ``geom_pose_per_step`` (nprob, H, ng, 8), one block per step; used as
+        it is and read when the kernel runs.  None keeps the model's poses."""
         return self._rollout_dp(int(nprob), inp, layout, params, cost4, theta, thetadot, best_keys, index_base,
                                 status, reset_best, stream, state=(start, final_state), ctrl=ctrl,
-                                ctrl_per_step=ctrl_per_step)
+                                ctrl_per_step=ctrl_per_step, geom_pose=geom_pose,
+                                geom_pose_per_step=geom_pose_per_step)
 
     def trace(self, inp, layout: int, q0, w, ptgt, qtgt):
         """Debug/parity run (host arrays): cost4, theta, per-step eef pose, masked slot distances."""
@@ -365,6 +454,7 @@ class Plant:
         self.nctrl = int(compiled_model.nctrl)
         self.nu = int(getattr(compiled_model, "nu", 0))
         self._ctrl = None  # the controls applied (clamped); None: the model's own
+        self._geom_poses = None  # the geom-pose block applied; None: the model's own
         h = ctypes.c_void_p()
         check(lib.mpcr_plant_create(self.model.handle, int(device), ctypes.byref(h)))
         self.handle = h
@@ -415,6 +505,25 @@ class Plant:
     def ctrl(self):
         """The controls the plant applies (clamped), in actuator order."""
         return self.model.clamp_ctrl(self.model.own_ctrl()) if self._ctrl is None else self._ctrl.copy()
+
+    def set_geom_poses(self, block):
+        """The plant's static geom poses from now on
+        (``mpcr_plant_set_geom_poses``): a host geom-pose block (ng, 8)
+        (``Model.geom_poses``, ``Model.pose_rows``) whose static rows are used
+        as they are; None restores the model's own."""
+        b = None
+        if block is not None:
+            own = self.model.geom_poses()[0]
+            b = np.ascontiguousarray(block.cpu() if hasattr(block, "cpu") else block, dtype=np.float32)
+            if b.shape != own.shape:
+                raise ValueError(f"block must be {own.shape}, got {b.shape}")
+        check(_lib.load().mpcr_plant_set_geom_poses(self.handle, None if b is None else _f32p(b)))
+        self._geom_poses = None if b is None else b.copy()
+
+    @property
+    def geom_poses(self):
+        """The geom-pose block the plant applies, (ng, 8) float32."""
+        return self.model.geom_poses()[0] if self._geom_poses is None else self._geom_poses.copy()
 
     def copy_state(self, tensor, stream=None):
         """The plant's state block into ``tensor`` (float32, CUDA, contiguous,

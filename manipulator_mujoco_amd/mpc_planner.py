@@ -78,12 +78,38 @@ def hold_ctrl(model, num_dof, hold=True, gripper=None):
     return ctrl
 
 
+def moving_obstacle(model, name, velocity, num_steps, timestep):
+    """A ``run_cem_planner(geom_poses=...)`` callable for a compiled model:
+    static collision geom ``name`` moves at the constant world ``velocity``
+    (m/s) from its model pose.  At tick k the plant gets the pose at the tick's
+    time, k timestep, and the planner the ``num_steps`` predicted poses of its
+    horizon: step j of a rollout, like the plant's step j ticks later, finds
+    the geom at (k + j) timestep."""
+    from .engine import Model
+    mod = Model(model)
+    own, ids, fixed = mod.geom_poses()
+    row = mod.geom_row(name)
+    if not fixed[row]:
+        raise ValueError(f"geom {name!r} is not static")
+    gid = int(ids[row])
+    p0, quat = own[row, :3].astype(np.float64), own[row, 4:].astype(np.float64)
+    v = np.asarray(velocity, dtype=np.float64).reshape(3)
+
+    def at(k):
+        return mod.pose_rows(own, {gid: (p0 + v * (k * timestep), quat)})
+
+    def poses(tick, _plant):
+        return at(tick), np.stack([at(tick + j) for j in range(num_steps)])
+
+    return poses
+
+
 def run_cem_planner(num_dof=None, num_batch=None, num_steps=None, maxiter_cem=None, maxiter_projection=None,
                     w_pos=None, w_rot=None, w_col=None, num_elite=None, timestep=None, initial_qpos=None,
                     target_names=None, show_viewer=None, cam_distance=None, show_contact_points=None,
                     position_threshold=None, rotation_threshold=None, save_data=None, data_dir=None,
                     stop_at_final_target=None, *, max_ticks=100, model_path=None, device=None, graph=True,
-                    verbose=True, planner_kwargs=None, plan_from_state=False, ctrl=None):
+                    verbose=True, planner_kwargs=None, plan_from_state=False, ctrl=None, geom_poses=None):
     """Run the CEM planner in closed loop for ``max_ticks`` ticks (headless).
     plan_from_state: every tick's rollouts start from the plant's full state
     (a device copy of its block) instead of the template state with the arm
@@ -91,7 +117,13 @@ def run_cem_planner(num_dof=None, num_batch=None, num_steps=None, maxiter_cem=No
     ctrl: the actuator controls, nu values in actuator order or a callable
     ``(tick, plant) -> array`` (``hold_ctrl``), given every tick to the plant
     and to the planner's rollouts; None keeps the model's own in both (the
-    reference never sets MjData.ctrl)."""
+    reference never sets MjData.ctrl).
+    geom_poses: the static collision geoms' world poses, a geom-pose block
+    (ng, 8) (``Model.geom_poses``, ``Model.pose_rows``) or a callable ``(tick,
+    plant) -> block`` (``moving_obstacle``), given every tick to the plant and
+    to the planner's rollouts; the callable may return ``(block, schedule)``
+    with a per-step schedule (num_steps, ng, 8) for the planner's horizon.
+    None keeps the model's poses in both."""
     if initial_qpos is None:
         initial_qpos = [1.5, -1.8, 1.75, -1.25, -1.6, 0]
     if target_names is None:
@@ -112,7 +144,8 @@ def run_cem_planner(num_dof=None, num_batch=None, num_steps=None, maxiter_cem=No
                       maxiter_projection=maxiter_projection, model_path=model_path, device=device, graph=graph,
                       verbose=verbose, **({"return_rollouts": False} | (planner_kwargs or {})
                                           | ({"plan_from_state": True} if plan_from_state else {})
-                                          | ({"actuator_ctrl": True} if ctrl is not None else {})))
+                                          | ({"actuator_ctrl": True} if ctrl is not None else {})
+                                          | ({"geom_poses": "per_step"} if geom_poses is not None else {})))
     log(f"Initialized CEM Planner: {round(time.time() - start_time, 2)}s")
 
     model = cem.model
@@ -146,8 +179,17 @@ def run_cem_planner(num_dof=None, num_batch=None, num_steps=None, maxiter_cem=No
         data.set_ctrl(c)
         return {"ctrl": c}
 
+    def apply_geom_poses(tick):
+        """The tick's geom poses to the plant; the planner's argument for them."""
+        if geom_poses is None:
+            return {}
+        g = geom_poses(tick, data) if callable(geom_poses) else geom_poses
+        block, sched = g if isinstance(g, tuple) else (g, g)
+        data.set_geom_poses(block)
+        return {"geom_pose": sched}
+
     _ = cem.compute_cem(xi_mean, data.qpos[ctrl_q], data.qvel[ctrl_v], data.qacc[ctrl_v], target_pos, target_rot,
-                        **from_plant, **apply_ctrl(0))
+                        **from_plant, **apply_ctrl(0), **apply_geom_poses(0))
     log(f"Compute CEM: {round(time.time() - start_time, 2)}s")
 
     thetadot = np.zeros(num_dof)
@@ -171,7 +213,7 @@ def run_cem_planner(num_dof=None, num_batch=None, num_steps=None, maxiter_cem=No
 
         cost, best_cost_g, best_cost_r, best_cost_c, best_vels, best_traj, xi_mean, _, _ = cem.compute_cem(
             xi_mean, data.qpos[ctrl_q], data.qvel[ctrl_v], data.qacc[ctrl_v], target_pos, target_rot, **from_plant,
-            **apply_ctrl(_tick))
+            **apply_ctrl(_tick), **apply_geom_poses(_tick))
 
         thetadot = np.mean(best_vels[1:num_steps - 2], axis=0)
         data.step(thetadot)
@@ -256,7 +298,15 @@ def main(argv=None):  # SBP/mpc_planner.py:256-314
                         help="each tick, the servos of the planned joints get the plant's current joint positions")
     parser.add_argument("--gripper", type=float, default=None, metavar="G",
                         help="control of the actuators with a two-dof transmission (the finger pairs)")
+    parser.add_argument("--obstacle", nargs=4, default=None, metavar=("NAME", "VX", "VY", "VZ"),
+                        help="a named static geom moves at this constant world velocity (m/s): the plant gets its "
+                             "pose at each tick's time, the planner the predicted poses of its horizon")
     a = parser.parse_args(argv)
+    geom_poses = None
+    if a.obstacle is not None:
+        from .planner import _resolve_model
+        geom_poses = moving_obstacle(_resolve_model(a.model, a.timestep), a.obstacle[0],
+                                     [float(x) for x in a.obstacle[1:]], a.num_steps, a.timestep)
     ctrl = None
     if a.ctrl_hold or a.gripper is not None:
         from .planner import _resolve_model
@@ -270,7 +320,7 @@ def main(argv=None):  # SBP/mpc_planner.py:256-314
                            save_data=a.save_data, data_dir=a.data_dir,
                            stop_at_final_target=not a.continue_after_final, max_ticks=a.max_ticks,
                            model_path=a.model, graph=not a.no_graph, plan_from_state=a.plan_from_state,
-                           ctrl=ctrl)
+                           ctrl=ctrl, geom_poses=geom_poses)
 
 
 if __name__ == "__main__":

@@ -105,13 +105,21 @@ class cem_planner:  # noqa: N801 (reference name)
                         initialised to the model's own, instead of the values
                         the model was compiled with.  Independent of
                         plan_from_state; both may be on
+    geom_poses          the rollouts read the static collision geoms' world
+                        poses per problem from a static device buffer
+                        (``compute_cem(geom_pose=...)``), initialised to the
+                        model's own (``Model.geom_poses``), instead of the
+                        poses the model was compiled with: True, one block
+                        (ng, 8) per problem; "per_step", one block per step of
+                        the horizon (H, ng, 8), an obstacle that moves during
+                        it.  Independent of the two above
     """
 
     def __init__(self, num_dof=None, num_batch=None, num_steps=None, timestep=None, maxiter_cem=None,
                  num_elite=None, w_pos=None, w_rot=None, w_col=None, maxiter_projection=None, *,
                  model_path=None, device=None, seed=0, elite_from_filtered=False, graph=False, group=None,
                  gather_rollouts=False, return_rollouts=True, capture_exchange=True, verbose=True,
-                 num_problems=1, seed_step=0, plan_from_state=False, actuator_ctrl=False):
+                 num_problems=1, seed_step=0, plan_from_state=False, actuator_ctrl=False, geom_poses=False):
         import torch
         import torch.distributed as tdist
 
@@ -202,6 +210,17 @@ class cem_planner:  # noqa: N801 (reference name)
             if own.size == 0:
                 raise ValueError("actuator_ctrl: the model has no actuators")
             self._ctrl = torch.as_tensor(own).to(self.device).repeat(B, 1).contiguous()
+        # one geom-pose block per problem, or per problem and step: the model's own until a tick stages another
+        if geom_poses not in (False, True, "per_step"):
+            raise ValueError(f"geom_poses={geom_poses!r}: False, True or 'per_step'")
+        self.geom_poses = geom_poses
+        self._gpose = None
+        if geom_poses:
+            own, _, fixed = self.engine.model.geom_poses()
+            if not fixed.any():
+                raise ValueError("geom_poses: the model has no static collision geom")
+            rep = (B, H, 1, 1) if geom_poses == "per_step" else (B, 1, 1)
+            self._gpose = torch.as_tensor(own).to(self.device).repeat(*rep).contiguous()
         self._graphs = None
         if verbose and self.rank == 0:
             self.print_info()
@@ -233,9 +252,12 @@ class cem_planner:  # noqa: N801 (reference name)
                                       index_base=self.index_base)
         out = dict(theta=self._theta[it], thetadot=self._thetadot[it], best_keys=self._key if last else None,
                    index_base=self.index_base)
-        if self.plan_from_state or self.actuator_ctrl:  # the same launch, reading each problem's start / control block
+        if self.plan_from_state or self.actuator_ctrl or self.geom_poses:
+            # the same launch, reading each problem's start / control / geom-pose block
             self.engine.rollout_cost_state(self._xf.view(B * n, self.nvar), MPCR_LAYOUT_XI, self._par, B,
-                                           self._costs[it], start=self._state, ctrl=self._ctrl, **out)
+                                           self._costs[it], start=self._state, ctrl=self._ctrl,
+                                           geom_pose=self._gpose, geom_pose_per_step=self.geom_poses == "per_step",
+                                           **out)
         else:
             self.engine.rollout_cost_multi(self._xf.view(B * n, self.nvar), MPCR_LAYOUT_XI, self._par, B,
                                            self._costs[it], **out)
@@ -374,15 +396,41 @@ class cem_planner:  # noqa: N801 (reference name)
                 raise ValueError(f"a control block holds nu={nu} values, got shape {c.shape}")
             self._ctrl[p].copy_(torch.as_tensor(np.ascontiguousarray(c)))
 
+    def _stage_geom_poses(self, blocks):
+        """Each problem's geom-pose block into the static buffer: (ng, 8) or,
+        for a planner built with geom_poses="per_step", also (H, ng, 8), one
+        block per step (a single block is held over the horizon).  None keeps
+        what is staged.  Every rank of a sharded planner stages the same
+        block."""
+        import torch
+        if blocks is None:
+            return
+        if not self.geom_poses:
+            raise ValueError("geom poses need a planner built with geom_poses=True or 'per_step'")
+        if len(blocks) != self.num_problems:
+            raise ValueError(f"{len(blocks)} geom-pose blocks for {self.num_problems} problem(s)")
+        full = tuple(self._gpose.shape[1:])
+        for p, g in enumerate(blocks):
+            if g is None:
+                continue
+            g = np.asarray(g.cpu() if hasattr(g, "cpu") else g, dtype=np.float32)
+            if g.shape != full and g.shape != full[-2:]:
+                raise ValueError(f"a geom-pose block is {full[-2:]}"
+                                 + (f" or {full}" if len(full) == 3 else "") + f", got {g.shape}")
+            self._gpose[p].copy_(torch.as_tensor(np.broadcast_to(g, full).copy()))
+
     def compute_cem(self, xi_mean, init_pos=(1.5, -1.8, 1.75, -1.25, -1.6, 0.0), init_vel=None, init_acc=None,
-                    target_pos=None, target_rot=None, state=None, ctrl=None):
+                    target_pos=None, target_rot=None, state=None, ctrl=None, geom_pose=None):
         """One MPC tick of CEM (SBP/mjx_planner.py:364-406). Returns the reference 9-tuple (numpy).
         state (planners built with plan_from_state): the full state the
         rollouts start from, a ``Plant`` or ``(qpos, qvel[, qacc_warmstart])``;
         None keeps the one staged last (at first the template).  init_pos
         still sets the arm joints.  ctrl (planners built with actuator_ctrl):
         the actuator controls of the rollouts, nu values; None keeps the ones
-        staged last (at first the model's own)."""
+        staged last (at first the model's own).  geom_pose (planners built
+        with geom_poses): the static geoms' poses of the rollouts, a
+        geom-pose block (ng, 8) or, "per_step", (H, ng, 8); None keeps the
+        one staged last (at first the model's own)."""
         import torch
 
         from . import dist as mdist
@@ -405,6 +453,7 @@ class cem_planner:  # noqa: N801 (reference name)
                     init_acc[None], target_pos[None], target_rot[None], [w])
         self._stage_states(None if state is None else [state])
         self._stage_ctrls(None if ctrl is None else [ctrl])
+        self._stage_geom_poses(None if geom_pose is None else [geom_pose])
         self._run_iterations()
 
         costs, theta, thetadot = self._costs, self._theta, self._thetadot
@@ -431,7 +480,7 @@ class cem_planner:  # noqa: N801 (reference name)
         return tuple(o.cpu().numpy() if isinstance(o, torch.Tensor) else o for o in out)
 
     def compute_cem_batch(self, xi_mean, init_pos, init_vel=None, init_acc=None, target_pos=None, target_rot=None,
-                          weights=None, states=None, ctrls=None):
+                          weights=None, states=None, ctrls=None, geom_poses=None):
         """One MPC tick of ``num_problems`` independent CEM problems in one
         batched sequence of launches (each kernel of ``compute_cem`` once,
         over every problem): xi_mean (B, nvar), init_pos / init_vel /
@@ -443,7 +492,9 @@ class cem_planner:  # noqa: N801 (reference name)
         seed_step`` given problem p's arguments.  states (planners built with
         plan_from_state): one start state per problem, each as ``compute_cem``'s
         ``state`` (a None entry keeps that problem's).  ctrls (planners built
-        with actuator_ctrl): one control block per problem, likewise."""
+        with actuator_ctrl): one control block per problem, likewise.
+        geom_poses (planners built with geom_poses): one geom-pose block per
+        problem, likewise."""
         import torch
 
         B, d, H, n, it_n = self.num_problems, self.num_dof, self.num, self.n_local, self.maxiter_cem
@@ -469,6 +520,7 @@ class cem_planner:  # noqa: N801 (reference name)
         self._stage(xi_mean, init_pos, init_vel, init_acc, target_pos, target_rot, weights)
         self._stage_states(states)
         self._stage_ctrls(ctrls)
+        self._stage_geom_poses(geom_poses)
         self._run_iterations()
 
         # each problem's best candidate of the last iteration: the low word of
