@@ -36,8 +36,8 @@ namespace mpcr {
   } while (0)
 // (a candidate's second wave, WPC = 2, into slots 32..63: per-wave critical paths)
 #define PROF_FLUSH                                                          \
-  if (lane == 0 && args.prof)                                               \
-    for (int i_ = 0; i_ < 32; i_++) atomicAdd(&args.prof[i_ + 32 * (threadIdx.x >> 6)], prof_acc[i_]);
+  if (lane == 0 && KA->prof)                                               \
+    for (int i_ = 0; i_ < 32; i_++) atomicAdd(&KA->prof[i_ + 32 * (threadIdx.x >> 6)], prof_acc[i_]);
 // wave-level event counter (first active lane adds 1; -DMPCR_PROFILE_COUNTS
 // only: the shared atomics distort the cycle shares)
 #ifdef MPCR_PROFILE_COUNTS
@@ -2440,8 +2440,68 @@ __device__ __forceinline__ void put_contacts(const DevModel* __restrict__ m, S& 
   }
 }
 
+// How a kernel reads its RolloutArgs (KA->field).  The dual-arm kernels read
+// the by-value argument itself, as ever.  The single-arm kernels read each
+// field where it is used, from the kernarg segment (RolloutArgs is the first
+// kernel argument: offset 0), through a pointer laundered at every read: a
+// by-value field is loaded in the prologue and, when it is needed once a step
+// or only in the epilogue, held in scalar registers across the whole horizon
+// loop -- with the masks and model scalars the loop needs that was more than
+// the 106 SGPRs, and the register allocator kept the surplus in VGPR lanes
+// (v_writelane / v_readlane: VALU instructions, and a VALU -> SALU wait in
+// front of every use).  The segment stays in the constant address space, so
+// the reads are s_load from the scalar cache.
+typedef const __attribute__((address_space(4))) RolloutArgs* KernargArgs;
+// Which optional outputs a call asked for (ARGS_HAS): the single-arm kernels
+// keep the answers as bits of one scalar (aflags), taken from the by-value
+// argument in the prologue, and read a pointer only behind its bit.
+enum { AF_TRACE_SLOTS = 1, AF_TRACE_EEF = 2, AF_THETA = 4, AF_TDOUT = 8 };  // AF_TDOUT: thetadot, theta-dot input layout
+// KA->field: the by-value argument (dual-arm kernels) or the laundered kernarg
+// segment (single-arm kernels); `args` is the kernel's by-value parameter or,
+// in a device function, a reference to it
+// The choice is the translation unit's (rollout_wide.hip defines
+// MPCR_ARGS_BY_VALUE before it includes this file; each unit instantiates
+// its own class only): with it the macros below are the text the kernels
+// had, and the dual-arm unit compiles to the code it had.
+#ifdef MPCR_ARGS_BY_VALUE
+#define KA (&args)
+#define KSA (&sa)
+#define ARGS_HAS(f, expr) (expr)
+#define ARGS_LAST_STEP_FIRST(t, H) true
+#else
+__device__ __forceinline__ KernargArgs karg() {
+  KernargArgs p = (KernargArgs)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(p));
+  return p;
+}
+#define KA karg()
+__device__ __forceinline__ unsigned args_flags(const RolloutArgs& a) {
+  return (a.trace_slots ? AF_TRACE_SLOTS : 0) | (a.trace_eef ? AF_TRACE_EEF : 0) | (a.theta ? AF_THETA : 0) |
+         (a.layout != 0 && a.thetadot ? AF_TDOUT : 0);
+}
+// ARGS_HAS(bit, the by-value units' own test): laundering the word at the
+// test, so that a bit's test is not hoisted out of the horizon loop as a lane
+// mask, does not compile (inside a divergent region the word may sit in a
+// vector register)
+#define ARGS_HAS(f, expr) ((aflags & (f)) != 0)
+// a test of an argument on the last step only: the step first, the read behind it
+#define ARGS_LAST_STEP_FIRST(t, H) ((t) == (H) - 1)
+// StateArgs the same way (KSA->field; the STATE kernels read it in the
+// kernarg segment, where it lives in RolloutArgs::par's bytes)
+static_assert(offsetof(RolloutArgs, par) % 8 == 0, "StateArgs' pointers aligned inside the kernarg segment");
+typedef const __attribute__((address_space(4))) StateArgs* KernargState;
+__device__ __forceinline__ KernargState ksarg() {
+  const __attribute__((address_space(4))) char* p =
+      (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(p));
+  return (KernargState)(p + offsetof(RolloutArgs, par));
+}
+#define KSA ksarg()
+#endif
+
 template <class S>
-__device__ __forceinline__ void emit_contacts(const DevModel* __restrict__ m, S& s, const RolloutArgs& args, int b,
+__device__ __forceinline__ void emit_contacts(const DevModel* __restrict__ m, S& s, const RolloutArgs& args,
+                                              [[maybe_unused]] unsigned aflags, int b,
                                               int t, int H, bool valid, int p, int nsl, const float dist[4],
                                               const float pos[4][3], const float nrm[4][3], float& cost_c,
                                               SlotHist<S>& sh, int k,
@@ -2472,11 +2532,11 @@ __device__ __forceinline__ void emit_contacts(const DevModel* __restrict__ m, S&
                 if (t > 0) cost_c += fmaxf(hv[c] * (1.f - 0.005f) - d, 0.f);
                 hv[c] = d;
               } else {
-                float* cp = args.slot_prev + (size_t)b * m->nslot;
+                float* cp = KA->slot_prev + (size_t)b * m->nslot;
                 if (t > 0) cost_c += fmaxf(cp[sa + c] * (1.f - 0.005f) - d, 0.f);
                 cp[sa + c] = d;
               }
-              if (args.trace_slots && b < args.n) args.trace_slots[((size_t)b * H + t) * m->nslot + sa + c] = d;
+              if (ARGS_HAS(AF_TRACE_SLOTS, KA->trace_slots && b < KA->n)) KA->trace_slots[((size_t)b * H + t) * m->nslot + sa + c] = d;
             }
           }
         };
@@ -2498,11 +2558,11 @@ __device__ __forceinline__ void emit_contacts(const DevModel* __restrict__ m, S&
 #pragma unroll
             for (int j = 0; j < SlotHist<S>::NC; j++) sh.v[j][c] = j == k ? d : sh.v[j][c];
           } else {
-            float* cp = args.slot_prev + (size_t)b * m->nslot;
+            float* cp = KA->slot_prev + (size_t)b * m->nslot;
             if (t > 0) cost_c += fmaxf(cp[sa + c] * (1.f - 0.005f) - d, 0.f);
             cp[sa + c] = d;
           }
-          if (args.trace_slots && b < args.n) args.trace_slots[((size_t)b * H + t) * m->nslot + sa + c] = d;
+          if (ARGS_HAS(AF_TRACE_SLOTS, KA->trace_slots && b < KA->n)) KA->trace_slots[((size_t)b * H + t) * m->nslot + sa + c] = d;
         }
       }
       }
@@ -2762,6 +2822,15 @@ __device__ __forceinline__ void ls_add(LsPtT<T>& p, float c0, float c1, float c2
 // The dual-arm kernel too: 256 -> 241 VGPRs, scratch 304 -> 144 B, C4 49.7 -> 48.6 ms.
 // (Once per step only: launders at the phase boundaries as well were not kept.)
 #define LAUNDER_LANE() asm volatile("" : "+v"(lane))
+// The debug dump's test (candidate 0's last step, RolloutArgs::dbg given).  The
+// single-arm kernels test the step and the candidate first, values the loop
+// holds anyway, and read the pointer only behind them: no register and no
+// load for the dump in any other step.
+#ifdef MPCR_ARGS_BY_VALUE
+#define DBG_LAST() (KA->dbg && b == 0 && t == H - 1)
+#else
+#define DBG_LAST() (t == H - 1 && b == 0 && KA->dbg)
+#endif
 
 // ---------------------------------------------------------------------------
 // J row access: rows < JL in LDS, the rest in the block's HBM slab gx.  The
@@ -2889,8 +2958,14 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
     rollout_kernel(RolloutArgs args, const DevModel* __restrict__ mptr) {
   static_assert(WPC == 1 || WPC == 2, "waves per candidate");
   static_assert(MULTI || !STATE, "the STATE instantiations look the problem's start block up");
+#ifdef MPCR_ARGS_BY_VALUE
   StateArgs sa = {nullptr, nullptr, 0, 0, 0, nullptr, nullptr, 0, 0};
   if constexpr (STATE) sa = state_args(args);
+  constexpr unsigned aflags = 0;
+#else
+  // (this unit reads the arguments where it uses them: KA, KSA, ARGS_HAS)
+  const unsigned aflags = args_flags(args);
+#endif
   using S = typename std::conditional<WIDE, typename std::conditional<WPC == 2, SmemW2, SmemW>::type,
                                       typename std::conditional<WPC == 2, SmemN2, SmemN>::type>::type;
   const int wv = WPC == 2 ? (int)(threadIdx.x >> 6) : 0;
@@ -2901,21 +2976,21 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
   const DevModel* __restrict__ m = m0;
   int lane = threadIdx.x & (WAVE - 1);  // laundered per step (LAUNDER_LANE)
   const int b = blockIdx.x;
-  if (b >= args.n) return;
-  const int H = args.H;
+  if (b >= KA->n) return;
+  const int H = KA->H;
   // horizon segment of this launch (dual-arm one-wave variant only)
   constexpr bool SEG = WIDE && WPC == 1;
-  const int t_begin = SEG ? args.t0 : 0, t_end = SEG ? args.t1 : H;
+  const int t_begin = SEG ? KA->t0 : 0, t_end = SEG ? KA->t1 : H;
   const bool resume = SEG && t_begin > 0, suspend = SEG && t_end < H;
-  float* const segs = SEG ? args.seg_state + (size_t)b * SEG_STRIDE : nullptr;
+  float* const segs = SEG ? KA->seg_state + (size_t)b * SEG_STRIDE : nullptr;
   const int nv = m->nv, nb = m->nbody, nc = m->nctrl;
-  float* const gx = S::JL < S::MAXEFC ? args.jx + (size_t)b * (S::MAXEFC - S::JL) * S::LDJ : nullptr;
-  short* const hx = S::WIDE ? args.hints + (size_t)b * S::NHINT * 2 : nullptr;
+  float* const gx = S::JL < S::MAXEFC ? KA->jx + (size_t)b * (S::MAXEFC - S::JL) * S::LDJ : nullptr;
+  short* const hx = S::WIDE ? KA->hints + (size_t)b * S::NHINT * 2 : nullptr;
   // mass matrix: the dense LDS image (single-arm variants), the compact LDS
   // rows of the dual-arm class (DevModel::mc_row: row i holds its tree's
   // columns; the others are 0 and rows past nv the identity), or -- a
   // dual-arm-class model whose compact M does not fit -- the candidate's HBM slab
-  float* const mrow0 = S::M_SLAB ? args.mslab + (size_t)b * NVW * S::LD : nullptr;
+  float* const mrow0 = S::M_SLAB ? KA->mslab + (size_t)b * NVW * S::LD : nullptr;
   const bool mcomp = S::M_SLAB && m->mc_n > 0;
   constexpr int MCW = S::MCW;
   auto m_get = [&](int i, int j) -> float {
@@ -3037,18 +3112,18 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
   //      (plant mode: the caller's state, no init_pos override; a batch's start
   //      state, StateArgs::start: qpos | qvel | qacc_warmstart of the problem's
   //      block in the template's place, everything else as from the template)
-  const bool from_state = (args.plant & 1) != 0;
+  const bool from_state = (KA->plant & 1) != 0;
   if (run_main) {  // (WPC = 2: wave 0 sets the image up, wave 1 waits at the barrier below)
   const float* st_in = nullptr;  // STATE: the problem's start block (null: the template)
   if constexpr (MULTI) {
     // the candidate's problem (mpcr_rollout_cost_multi): wave-uniform, scalar
-    const int pr = args.prob_n ? (args.prob_off + b) / args.prob_n : 0;
-    const float* dp = args.dpar + (size_t)pr * PAR_N;
+    const int pr = KA->prob_n ? (KA->prob_off + b) / KA->prob_n : 0;
+    const float* dp = KA->dpar + (size_t)pr * PAR_N;
     if (lane < PAR_N) s.par[lane] = dp[lane];
     if constexpr (STATE)
-      if (sa.start) st_in = sa.start + (size_t)pr * sa.start_stride;
+      if (KSA->start) st_in = KSA->start + (size_t)pr * KSA->start_stride;
   } else {
-    if (lane < PAR_N) s.par[lane] = args.dpar ? args.dpar[lane] : args.par[lane];
+    if (lane < PAR_N) s.par[lane] = KA->dpar ? KA->dpar[lane] : KA->par[lane];
   }
   if constexpr (S::SPLIT)
     if (lane == 0) s.ctok_[0] = 0;  // no step's pair cull posted yet
@@ -3056,7 +3131,7 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
     // a rollout starts its hull climbs afresh; the plant keeps them across
     // steps (reset by mpcr_plant_set_state), so k plant steps = a k-step rollout
     if (!from_state && !resume) {
-      int* h = reinterpret_cast<int*>(args.hints + (size_t)b * S::NHINT * 2);
+      int* h = reinterpret_cast<int*>(KA->hints + (size_t)b * S::NHINT * 2);
       for (int i = lane; i < S::NHINT; i += WAVE) h[i] = -1;  // both sides -1
     }
   }
@@ -3070,7 +3145,7 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
   } else {
   // the block to start from, if any: the plant's own, or (STATE) the problem's
   const bool from_blk = STATE ? st_in != nullptr : from_state;
-  const float* const blk = STATE ? st_in : args.state;
+  const float* const blk = STATE ? st_in : KA->state;
   for (int i = lane; i < S::NQW; i += WAVE)
     s.qpos[i] = i < m->nq ? (from_blk ? blk[ST_QPOS + i] : m->qpos_init[i]) : 0.f;
   if (lane < NVW) {
@@ -3097,16 +3172,16 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
   // thetadot output (or a scratch row); each step then reads its value with a
   // load issued one step ahead, so no per-step basis latency is exposed
   const float* tdp;
-  if (args.layout == 0) {
-    float* tdw = (args.thetadot ? args.thetadot : args.tdscratch) + (size_t)b * nc * H;
+  if (KA->layout == 0) {
+    float* tdw = (KA->thetadot ? KA->thetadot : KA->tdscratch) + (size_t)b * nc * H;
     for (int idx = lane; run_main && !resume && idx < nc * H; idx += WAVE) {
       const int j = idx / H, tt = idx - j * H;
-      const float* pd = args.pdot + (size_t)tt * args.nbasis;
-      const float* xj = args.input + ((size_t)b * nc + j) * args.nbasis;
+      const float* pd = KA->pdot + (size_t)tt * KA->nbasis;
+      const float* xj = KA->input + ((size_t)b * nc + j) * KA->nbasis;
       float v = 0.f;
 #pragma unroll
       for (int k = 0; k < 12; k++)
-        if (k < args.nbasis) v = fmaf(pd[k], xj[k], v);
+        if (k < KA->nbasis) v = fmaf(pd[k], xj[k], v);
       tdw[idx] = v;
     }
     __threadfence_block();
@@ -3114,7 +3189,7 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
     if constexpr (WPC == 2) block_sync();
     tdp = tdw;
   } else {
-    tdp = args.input + (size_t)b * nc * H;
+    tdp = KA->input + (size_t)b * nc * H;
   }
   float vnext = lane < nc ? tdp[lane * H + t_begin] : 0.f;
   float cost_g = 0.f, cost_r = 0.f, cost_c = 0.f;
@@ -3138,26 +3213,26 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
   // pair; the values themselves are loaded again every step.
   const float* ctrl_p = nullptr;
   if constexpr (STATE && S::WIDE) {
-    if (sa.ctrl) ctrl_p = sa.ctrl + (size_t)(args.prob_n ? (args.prob_off + b) / args.prob_n : 0) * sa.ctrl_stride;
+    if (KSA->ctrl) ctrl_p = KSA->ctrl + (size_t)(KA->prob_n ? (KA->prob_off + b) / KA->prob_n : 0) * KSA->ctrl_stride;
   }
   // STATE: the problem's geom-pose block (StateArgs::geom_pose; null: the
   // model's own static poses, geom_pos / geom_quat).  Wave-uniform, a scalar
   // pair; the rows themselves are loaded again every step.
   const float* gpose_p = nullptr;
   if constexpr (STATE) {
-    if (sa.geom_pose)
-      gpose_p = sa.geom_pose + (size_t)(args.prob_n ? (args.prob_off + b) / args.prob_n : 0) * sa.geom_stride;
+    if (KSA->geom_pose)
+      gpose_p = KSA->geom_pose + (size_t)(KA->prob_n ? (KA->prob_off + b) / KA->prob_n : 0) * KSA->geom_stride;
   }
   PROF_DECL
   unsigned* pace = nullptr;
   int pace_own = 0;
   unsigned pace_v = ~0u;
-  if (WPC == 1 && args.pace) {
+  if (WPC == 1 && KA->pace) {
     const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | 4);  // HW_ID
     const unsigned xcc = __builtin_amdgcn_s_getreg((3 << 11) | 20);  // XCC_ID[3:0]
     const unsigned grp = ((((xcc & 7u) * 8u + ((hw >> 13) & 7u)) * 2u + ((hw >> 12) & 1u)) * 16u + ((hw >> 8) & 15u)) *
                              4u + ((hw >> 4) & 3u);
-    pace = args.pace + grp * 16u;
+    pace = KA->pace + grp * 16u;
     pace_own = (int)(hw & 15u);
   }
 #ifdef MPCR_WAVETIME
@@ -3277,7 +3352,7 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
       const float v = vnext;
       if (t + 1 < H) vnext = tdp[lane * H + t + 1];  // next step's, in flight during this one
       s.qvel[ctrl_da] = v;
-      if (args.layout != 0 && args.thetadot) args.thetadot[(size_t)b * nc * H + lane * H + t] = v;
+      if (ARGS_HAS(AF_TDOUT, KA->layout != 0 && KA->thetadot)) KA->thetadot[(size_t)b * nc * H + lane * H + t] = v;
     }
     sync();
 
@@ -3292,7 +3367,7 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
     bool gp_row = false;
     if constexpr (STATE && !S::WIDE) {
       if (gpose_p && lane < m->ngeom && m->geom_body[lane] < 0) {
-        const float4* row = reinterpret_cast<const float4*>(gpose_p + (size_t)t * sa.geom_step_stride) + 2 * lane;
+        const float4* row = reinterpret_cast<const float4*>(gpose_p + (size_t)t * KSA->geom_step_stride) + 2 * lane;
         gpp = row[0];
         gpq = row[1];
         gp_row = true;
@@ -3431,7 +3506,7 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
       float gq[4] = {m->geom_quat[lane][0], m->geom_quat[lane][1], m->geom_quat[lane][2], m->geom_quat[lane][3]};
       if constexpr (STATE && S::WIDE) {
         if (gpose_p && gb < 0) {
-          const float4* row = reinterpret_cast<const float4*>(gpose_p + (size_t)t * sa.geom_step_stride) + 2 * lane;
+          const float4* row = reinterpret_cast<const float4*>(gpose_p + (size_t)t * KSA->geom_step_stride) + 2 * lane;
           gpp = row[0];
           gpq = row[1];
           gp_row = true;
@@ -3529,12 +3604,13 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
       float qn = sqrtf(eq[0] * eq[0] + eq[1] * eq[1] + eq[2] * eq[2] + eq[3] * eq[3]);
       float dq = fabsf((eq[0] * qt[0] + eq[1] * qt[1] + eq[2] * qt[2] + eq[3] * qt[3]) / qn);
       cost_r += 2.f * acosf(clampf(dq, -1.f, 1.f));
-      if (args.trace_eef) {
-        float* e = args.trace_eef + ((size_t)b * H + t) * 7;
+      if (ARGS_HAS(AF_TRACE_EEF, KA->trace_eef)) {
+        float* e = KA->trace_eef + ((size_t)b * H + t) * 7;
         e[0] = ep[0]; e[1] = ep[1]; e[2] = ep[2]; e[3] = eq[0]; e[4] = eq[1]; e[5] = eq[2]; e[6] = eq[3];
       }
-      if ((STATE ? sa.final_state != nullptr : args.plant != 0) && t == H - 1) {  // the last step's pre-integration pose
-        float* e = (STATE ? sa.final_state + (size_t)b * ST_N : args.state) + ST_EEF;
+      // the last step's pre-integration pose (single-arm kernels: the step first, the argument read behind it)
+      if (ARGS_LAST_STEP_FIRST(t, H) && (STATE ? KSA->final_state != nullptr : KA->plant != 0) && t == H - 1) {
+        float* e = (STATE ? KSA->final_state + (size_t)b * ST_N : KA->state) + ST_EEF;
         e[0] = ep[0]; e[1] = ep[1]; e[2] = ep[2]; e[3] = eq[0]; e[4] = eq[1]; e[5] = eq[2]; e[6] = eq[3];
       }
     }
@@ -3556,7 +3632,7 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
         // transmission loop so the load overlaps its len / vel chain
         float cv = 0.f;
         if constexpr (STATE)
-          if (ctrl_p) cv = ctrl_p[(size_t)t * sa.ctrl_step_stride + lane];
+          if (ctrl_p) cv = ctrl_p[(size_t)t * KSA->ctrl_step_stride + lane];
         float len = 0.f, vel = 0.f;
         for (int k = 0; k < m->act_ntrn[lane]; k++) {
           len = fmaf(m->act_moment[lane][k], s.qpos[m->act_qadr[lane][k]], len);
@@ -3880,8 +3956,22 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
       blk_solve<NVW>(m, [&](int i, int j) { return m_get(i, j); }, s.qfs, s.qas, lane, &s.xpos[0][0]);
     } else {
       float Lm[NVW];
+      if constexpr (!S::M_SLAB) {
+        // single-arm kernels: the row under one predicate, as quads (an
+        // element at a time, each select was an exec region of its own)
+#pragma unroll
+        for (int j = 0; j < NVW; j++) Lm[j] = 0.f;
+        if (lane < NVW) {
+#pragma unroll
+          for (int q = 0; q < NVW / 4; q++) {
+            const float4 v = m_quad(lane, q);
+            Lm[4 * q] = v.x; Lm[4 * q + 1] = v.y; Lm[4 * q + 2] = v.z; Lm[4 * q + 3] = v.w;
+          }
+        }
+      } else {
 #pragma unroll
       for (int j = 0; j < NVW; j++) Lm[j] = lane < NVW ? m_get(lane, j) : 0.f;
+      }
       // the dynamics region (xpos..fvec) is dead once M is assembled
       float x;
       if constexpr (NVW == 16) {
@@ -4012,7 +4102,7 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
       if (run && func != 4 && !defer) nsl = narrow_lane(m, s, hx, p, dist, pos, nrm, nullptr, rq);
       STAMP(11);
       const unsigned long long bbm = __ballot(run && func == 4);
-      emit_contacts(m, s, args, b, t, H, valid && func != 4 && !defer, p, nsl, dist, pos, nrm, cost_c, shist, k, rq);
+      emit_contacts(m, s, args, aflags, b, t, H, valid && func != 4 && !defer, p, nsl, dist, pos, nrm, cost_c, shist, k, rq);
       STAMP(12);
       if (bbm && !(m->disableflags & 16)) {
         unsigned long long mm = bbm;
@@ -4073,7 +4163,7 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
       if (split && wv == 1 && s.ncvx <= m->w2_lead_max) {
         const bool v = lane < s.ncvx;
         lpc = v ? s.cvx[lane] : 0;
-        lsl = v ? narrow_lane(m, s, hx, lpc, ld, lp, ln, (args.dbg && b == 0 && t == H - 1) ? args.dbg : nullptr)
+        lsl = v ? narrow_lane(m, s, hx, lpc, ld, lp, ln, (DBG_LAST()) ? KA->dbg : nullptr)
                 : 0;
         STAMP(21);
         for (unsigned long long pm = __ballot(lsl == kPendingManifold); pm; pm &= pm - 1) {
@@ -4145,7 +4235,7 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
             }
             lsl = __float_as_int(o[28]);
           }
-          emit_contacts(m, s, args, b, t, H, lane < ncv, lpc, lsl, ld, lp, ln, cost_c, shist, -1);
+          emit_contacts(m, s, args, aflags, b, t, H, lane < ncv, lpc, lsl, ld, lp, ln, cost_c, shist, -1);
         }
         STAMP(18);
       }
@@ -4157,7 +4247,7 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
         const bool v = mine && i < ncv;
         const int pc = v ? s.cvx[i] : 0;
         float cd[4] = {1e30f, 1e30f, 1e30f, 1e30f}, cp[4][3] = {}, cn[4][3] = {};
-        int cn_sl = v ? narrow_lane(m, s, hx, pc, cd, cp, cn, (args.dbg && b == 0 && t == H - 1) ? args.dbg
+        int cn_sl = v ? narrow_lane(m, s, hx, pc, cd, cp, cn, (DBG_LAST()) ? KA->dbg
                                                                                            : nullptr)
                       : 0;
         STAMP(21);
@@ -4197,7 +4287,7 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
           ncon_w += tot;
           block_sync();  // jcnt is the next round's
         } else if (mine) {
-          emit_contacts(m, s, args, b, t, H, v, pc, cn_sl, cd, cp, cn, cost_c, shist, -1);
+          emit_contacts(m, s, args, aflags, b, t, H, v, pc, cn_sl, cd, cp, cn, cost_c, shist, -1);
         }
         STAMP(18);
       }
@@ -4574,8 +4664,8 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
           const float R = fmaxf((1.f - imp) / imp * a2.y, kMinVal);
           s.efc_D[r] = 1.f / R;
           s.efc_aref[r] = -a1.w * vel - a1.z * imp * dpos;
-          if (args.dbg && b == 0 && t == H - 1 && r < DBG_MAXROW) {
-            float* o = args.dbg + DBG_ROW + 3 * r;
+          if (DBG_LAST() && r < DBG_MAXROW) {
+            float* o = KA->dbg + DBG_ROW + 3 * r;
             o[0] = s.efc_D[r]; o[1] = s.efc_aref[r]; o[2] = vel;
           }
         }
@@ -4658,15 +4748,15 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
         }
         s.efc_D[r] = 1.f / R;
         s.efc_aref[r] = -B * vel - K * imp * (efric ? 0.f : pos - margin);
-        if (args.dbg && b == 0 && t == H - 1 && r < DBG_MAXROW) {
-          float* o = args.dbg + DBG_ROW + 3 * r;
+        if (DBG_LAST() && r < DBG_MAXROW) {
+          float* o = KA->dbg + DBG_ROW + 3 * r;
           o[0] = s.efc_D[r]; o[1] = s.efc_aref[r]; o[2] = vel;
         }
       }
-      if (args.dbg && b == 0 && t == H - 1 && run_main) {
-        if (lane == 0) { args.dbg[DBG_NCON] = (float)s.ncon; args.dbg[DBG_NEFC] = (float)s.nefc; }
+      if (DBG_LAST() && run_main) {
+        if (lane == 0) { KA->dbg[DBG_NCON] = (float)s.ncon; KA->dbg[DBG_NEFC] = (float)s.nefc; }
         if (lane < s.ncon && lane < DBG_MAXCON) {
-          float* o = args.dbg + DBG_CON + 8 * lane;
+          float* o = KA->dbg + DBG_CON + 8 * lane;
           o[0] = s.con_pos[lane][0]; o[1] = s.con_pos[lane][1]; o[2] = s.con_pos[lane][2];
           o[3] = s.con_dist[lane]; o[4] = (float)s.con_pair[lane];
           o[5] = s.con_frame[lane][0]; o[6] = s.con_frame[lane][1]; o[7] = s.con_frame[lane][2];
@@ -4719,7 +4809,7 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
         coupled = s.pad_ != 0;
       }
     }
-    if (args.dbg && b == 0 && t == H - 1 && lane < NVW) args.dbg[DBG_QAS + lane] = s.qas[lane];
+    if (DBG_LAST() && lane < NVW) KA->dbg[DBG_QAS + lane] = s.qas[lane];
     nefc_sum += s.nefc;
     nefc_max = max(nefc_max, s.nefc);
 
@@ -4785,10 +4875,10 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
             ws_gw = ws_won ? gws : 0.f;  // (the Gauss term at qacc_smooth is 0)
             ws_cost = ws_won ? costw : costs;
           }
-          if (args.dbg && b == 0 && t == H - 1 && lane == 0) {
-            args.dbg[DBG_INFO + 0] = costw < costs ? 1.f : 0.f;
-            args.dbg[DBG_INFO + 1] = costw;
-            args.dbg[DBG_INFO + 2] = costs;
+          if (DBG_LAST() && lane == 0) {
+            KA->dbg[DBG_INFO + 0] = costw < costs ? 1.f : 0.f;
+            KA->dbg[DBG_INFO + 1] = costw;
+            KA->dbg[DBG_INFO + 2] = costs;
           }
         }
         if (lane < NVW) s.qacc[lane] = qacc_l;
@@ -4944,9 +5034,9 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
             }
           }
           const float search = lane < nv ? -mg : 0.f;
-          if (args.dbg && b == 0 && t == H - 1 && it == 0 && lane < NVW) {
-            args.dbg[DBG_GRAD + lane] = grad;
-            args.dbg[DBG_SRCH + lane] = search;
+          if (DBG_LAST() && it == 0 && lane < NVW) {
+            KA->dbg[DBG_GRAD + lane] = grad;
+            KA->dbg[DBG_SRCH + lane] = search;
           }
           STAMP(14);
           if (lane < NVW) s.srch[lane] = search;
@@ -4990,7 +5080,7 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
 #ifdef MPCR_WAVETIME
             wt_ls++;
 #endif
-            if (args.dbg && b == 0 && t == H - 1 && lane == 0 && it == 0) args.dbg[DBG_INFO + 5] = (float)ls;
+            if (DBG_LAST() && lane == 0 && it == 0) KA->dbg[DBG_INFO + 5] = (float)ls;
             if (lo.d0 < 0.f && lo.d0 > -gtol) break;
             if (hi.d0 > 0.f && hi.d0 < gtol) break;
             // bracket closed to fp32 resolution: further passes only move alpha
@@ -5025,12 +5115,12 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
           if constexpr (!LSQ0) ls_finish(s, lane, qg, lo, hi);
           const bool improved = lo.cost < p0.cost || hi.cost < p0.cost;
           const LT alpha = lo.cost < hi.cost ? lo.alpha : hi.alpha;
-          if (args.dbg && b == 0 && t == H - 1 && lane == 0 && it == 0) {
-            args.dbg[DBG_INFO + 3] = (float)p0.cost;
-            args.dbg[DBG_INFO + 4] = (float)alpha;
-            args.dbg[DBG_INFO + 6] = (float)(lo.cost < hi.cost ? lo.cost : hi.cost);
+          if (DBG_LAST() && lane == 0 && it == 0) {
+            KA->dbg[DBG_INFO + 3] = (float)p0.cost;
+            KA->dbg[DBG_INFO + 4] = (float)alpha;
+            KA->dbg[DBG_INFO + 6] = (float)(lo.cost < hi.cost ? lo.cost : hi.cost);
           }
-          if (args.dbg && b == 0 && t == H - 1 && lane == 0) args.dbg[DBG_INFO + 7] = (float)(it + 1);
+          if (DBG_LAST() && lane == 0) KA->dbg[DBG_INFO + 7] = (float)(it + 1);
           if (improved && lane < NVW) s.qacc[lane] = (float)((LT)s.qacc[lane] + alpha * (LT)s.srch[lane]);
           prev_cost = cost;
           ws_keep = false;
@@ -5043,7 +5133,7 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
       }
     }
 
-    if (args.dbg && b == 0 && t == H - 1 && lane < NVW) args.dbg[DBG_QACC + lane] = s.qacc[lane];
+    if (DBG_LAST() && lane < NVW) KA->dbg[DBG_QACC + lane] = s.qacc[lane];
     STAMP(9);
     STOP_AT(9)
     // ---- implicitfast (dual-arm class): (M + dt D) a = qfrc_smooth + J^T f at
@@ -5136,7 +5226,7 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
         }
       }
       sync();
-      if (lane < nc && args.theta) args.theta[(size_t)b * nc * H + lane * H + t] = s.qpos[ctrl_qa];
+      if (lane < nc && ARGS_HAS(AF_THETA, KA->theta)) KA->theta[(size_t)b * nc * H + lane * H + t] = s.qpos[ctrl_qa];
     }
   }
 
@@ -5145,11 +5235,11 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
   // the state after the last step, with that step's qacc: the single
   // environment's block (plant; advanced only when plant & 2) or candidate b's
   // block of a batch's final states (STATE; written by the segment that ends at H)
-  const bool wr_state = STATE ? sa.final_state != nullptr && !suspend : args.plant != 0;
-  float* const sout = STATE ? sa.final_state + (size_t)b * ST_N : args.state;
+  const bool wr_state = STATE ? KSA->final_state != nullptr && !suspend : KA->plant != 0;
+  float* const sout = STATE ? KSA->final_state + (size_t)b * ST_N : KA->state;
   if (wr_state && run_main) {
     if (lane < nv) sout[ST_QACC + lane] = s.qacc[lane];
-    if (STATE || (args.plant & 2)) {
+    if (STATE || (KA->plant & 2)) {
       if (lane < m->nq) sout[ST_QPOS + lane] = s.qpos[lane];
       if (lane < nv) {
         sout[ST_QVEL + lane] = s.qvel[lane];
@@ -5191,36 +5281,36 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
     // keeps it out of the argmin and the elites (a NaN would win the argmin)
     const float cost = (status & (1 << 10)) ? __builtin_inff()
                                             : s.par[PAR_W] * cost_g + s.par[PAR_W + 1] * cost_r + s.par[PAR_W + 2] * cost_c;
-    args.cost4[4 * (size_t)b + 0] = cost;
-    args.cost4[4 * (size_t)b + 1] = cost_g;
-    args.cost4[4 * (size_t)b + 2] = cost_r;
-    args.cost4[4 * (size_t)b + 3] = cost_c;
-    if (args.status) args.status[b] = status | (min(nefc_max, 255) << 2) | (nefc_sum << 11);
-    if (args.best_key) {
+    KA->cost4[4 * (size_t)b + 0] = cost;
+    KA->cost4[4 * (size_t)b + 1] = cost_g;
+    KA->cost4[4 * (size_t)b + 2] = cost_r;
+    KA->cost4[4 * (size_t)b + 3] = cost_c;
+    if (KA->status) KA->status[b] = status | (min(nefc_max, 255) << 2) | (nefc_sum << 11);
+    if (KA->best_key) {
       const uint32_t u = __float_as_uint(cost);
       uint32_t key = isnan(cost) ? 0u : ((u & 0x80000000u) ? ~u : (u | 0x80000000u));
       if constexpr (MULTI) {  // problem pr's key, the index within the problem
-        const int gi = args.prob_off + b, pr = args.prob_n ? gi / args.prob_n : 0;
-        const int li = args.prob_n ? gi - pr * args.prob_n : gi;
-        const unsigned long long k64 = ((unsigned long long)key << 32) | (uint32_t)(args.index_base + li);
-        atomicMin(args.best_key + pr, k64);
+        const int gi = KA->prob_off + b, pr = KA->prob_n ? gi / KA->prob_n : 0;
+        const int li = KA->prob_n ? gi - pr * KA->prob_n : gi;
+        const unsigned long long k64 = ((unsigned long long)key << 32) | (uint32_t)(KA->index_base + li);
+        atomicMin(KA->best_key + pr, k64);
       } else {
-        const unsigned long long k64 = ((unsigned long long)key << 32) | (uint32_t)(args.index_base + b);
-        atomicMin(args.best_key, k64);
+        const unsigned long long k64 = ((unsigned long long)key << 32) | (uint32_t)(KA->index_base + b);
+        atomicMin(KA->best_key, k64);
       }
     }
   }
   if (pace && lane == pace_own) __hip_atomic_store(pace + lane, ~0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 #ifdef MPCR_WAVETIME
-  if (lane == 0 && args.prof) {
+  if (lane == 0 && KA->prof) {
     const unsigned long long c1 = __builtin_amdgcn_s_memtime(), t1 = __builtin_amdgcn_s_memrealtime();
     const unsigned hwid = __builtin_amdgcn_s_getreg((31 << 11) | 4), xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20);
-    args.prof[4 * (size_t)b + 0] = wt_t0;
-    args.prof[4 * (size_t)b + 1] = t1;
-    args.prof[4 * (size_t)b + 2] = c1 - wt_c0;
-    args.prof[4 * (size_t)b + 3] = ((unsigned long long)xcc << 32) | hwid;
-    args.prof[4 * (size_t)args.n + 2 * (size_t)b] = ((unsigned long long)wt_ls << 32) | wt_newton;
-    args.prof[4 * (size_t)args.n + 2 * (size_t)b + 1] = wt_cvx;
+    KA->prof[4 * (size_t)b + 0] = wt_t0;
+    KA->prof[4 * (size_t)b + 1] = t1;
+    KA->prof[4 * (size_t)b + 2] = c1 - wt_c0;
+    KA->prof[4 * (size_t)b + 3] = ((unsigned long long)xcc << 32) | hwid;
+    KA->prof[4 * (size_t)KA->n + 2 * (size_t)b] = ((unsigned long long)wt_ls << 32) | wt_newton;
+    KA->prof[4 * (size_t)KA->n + 2 * (size_t)b + 1] = wt_cvx;
   }
 #endif
 }

@@ -4,6 +4,9 @@
 // latency-bound dual arm pays ~5 % and its fp32 rollouts stay within the
 // scalar fp32 restatement's drift (C4 shard well-conditioned misses 22 -> 8,
 // worst 4.8e-3 -> 7.8e-4).
+// the dual-arm kernels read their arguments from the by-value parameter, as
+// ever (rollout.hip, KA / KSA): this unit's device code stays what it was
+#define MPCR_ARGS_BY_VALUE 1
 #include "rollout.hip"
 
 namespace mpcr {
