@@ -313,6 +313,53 @@ int mpcr_rollout_cost_world(mpcr_engine* e, const float* input, int layout, int 
                             int geom_stride, int geom_step_stride, float* cost4, float* theta, float* thetadot,
                             uint64_t* best_keys, int index_base, int* status, int flags, void* stream);
 
+/* Fold the costs of candidates that were rolled out in several scenarios
+   (world hypotheses) into one row each.  cost4_scen holds nprob nscen n_per
+   rows of 4 (a rollout's cost4: total | goal | rotation | collision):
+   candidate i of problem p in scenario s is row (p nscen + s) n_per + i.
+   Among a candidate's nscen rows the `worst` with the largest total are
+   selected -- NaN above everything, then descending, -0 == +0, ties to the
+   lower scenario -- and each column of cost4[(p n_per + i) 4 ..] is the fp32
+   sum of that column over the selected rows, added in ascending scenario
+   order one after the other starting from the first, divided (IEEE) by
+   (float)worst.  worst = nscen is the mean, worst = 1 the worst scenario's
+   own row, values between them the mean of the worst few (a CVaR).
+   best_keys (nullable, nprob entries) receives the atomic minimum of the
+   packed key of the aggregated total, NaN first, low word index_base + i
+   (mpcr_best_key_decode; the key mpcr_argmin computes over the column);
+   MPCR_F_RESET_BEST resets all nprob keys first.  1 <= worst <= nscen <= 64,
+   nprob nscen n_per <= max_n.  Device pointers only, both arrays 16-byte
+   aligned; no allocation, graph-capturable. */
+int mpcr_scenario_reduce(mpcr_engine* e, const float* cost4_scen, int nprob, int nscen, int n_per, int worst,
+                         float* cost4, uint64_t* best_keys, int index_base, int flags, void* stream);
+
+/* One set of candidates priced in several scenarios (a backward-compatible
+   addition like the *_multi calls): mpcr_rollout_cost_world over nprob nscen
+   rollout problems, r = p nscen + s being scenario s of problem p, followed
+   by mpcr_scenario_reduce.  Rollout problem r is an ordinary problem of that
+   call -- its own block params + 20 r, its own start, ctrl and geom-pose
+   block (the strides are per rollout problem) and its own n_per rows of
+   cost4_scen, status and final_state (nprob nscen n_per rows each) -- except
+   that the nscen scenarios of problem p all read rows [p n_per, (p + 1)
+   n_per) of input (nprob n_per rows), so the samples exist once.  theta and
+   thetadot (nullable, nprob n_per rows) are written by scenario 0, the
+   nominal one: thetadot depends on the input alone, theta is scenario 0's
+   trajectory.  cost4_scen is required.  cost4 (nullable, nprob n_per rows of
+   4) receives the fold with `worst`; NULL skips that launch.  best_keys
+   (nullable, nprob entries; needs cost4) comes from the fold.  Each
+   scenario's slice is bitwise what mpcr_rollout_cost_world computes for that
+   scenario's blocks alone, and nscen = 1 is bitwise that call in every
+   output, with cost4 equal to cost4_scen.  Two launches on the caller's
+   stream; graph-capturable.  MPCR_EINVAL: nscen outside [1, 64], worst
+   outside [1, nscen], nprob nscen n_per > max_n, host pointers, best_keys
+   without cost4, and whatever mpcr_rollout_cost_world refuses. */
+int mpcr_rollout_cost_scenarios(mpcr_engine* e, const float* input, int layout, int nprob, int nscen, int worst,
+                                int n_per, const float* params, const float* start, int start_stride,
+                                float* final_state, const float* ctrl, int ctrl_stride, int ctrl_step_stride,
+                                const float* geom_pose, int geom_stride, int geom_step_stride, float* cost4_scen,
+                                float* cost4, float* theta, float* thetadot, uint64_t* best_keys, int index_base,
+                                int* status, int flags, void* stream);
+
 /* Closed-loop plant: one environment of the model, stepped by the rollout
    kernel (fp32 state resident on the device).  Created at the template
    state (qpos_init, qvel_init, zero warm start). */

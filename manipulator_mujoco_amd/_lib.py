@@ -47,6 +47,9 @@ EXPORTS += _WORLD
 # the wave-reduction self-test, likewise
 _SELFTEST = ("mpcr_selftest_reduce",)
 EXPORTS += _SELFTEST
+# scenarios (one set of candidates, several worlds), likewise
+_SCEN = ("mpcr_rollout_cost_scenarios", "mpcr_scenario_reduce")
+EXPORTS += _SCEN
 _VOID = ("mpcr_last_error", "mpcr_model_free", "mpcr_engine_free", "mpcr_best_key_decode", "mpcr_cem_free",
          "mpcr_plant_free", "mpcr_comm_free")
 
@@ -156,10 +159,15 @@ def load():
     have_selftest = hasattr(lib, _SELFTEST[0])
     if have_selftest:
         lib.mpcr_selftest_reduce.argtypes = [i, vp, i, vp]
+    have_scen = hasattr(lib, _SCEN[0])
+    if have_scen:
+        lib.mpcr_rollout_cost_scenarios.argtypes = [vp, vp, i, i, i, i, i, vp, vp, i, vp, vp, i, i, vp, i, i, vp, vp, vp,
+                                                    vp, vp, i, vp, i, vp]
+        lib.mpcr_scenario_reduce.argtypes = [vp, vp, i, i, i, i, vp, vp, i, i, vp]
     for name in EXPORTS + ("mpcr_rollout_trace", "mpcr_plant_step_debug", "mpcr_plant_dbg_size"):
         if (name in _MULTI and not have_multi) or (name in _STATE and not have_state) or (
                 name in _CTRL and not have_ctrl) or (name in _WORLD and not have_world) or (
-                name in _SELFTEST and not have_selftest):
+                name in _SELFTEST and not have_selftest) or (name in _SCEN and not have_scen):
             continue
         if name not in _VOID:
             getattr(lib, name).restype = i

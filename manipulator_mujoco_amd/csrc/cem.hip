@@ -520,4 +520,95 @@ __global__ void __launch_bounds__(1024) cem_update_kernel(const float* __restric
   if (tid < nv) mean[tid] = mnew[tid];
 }
 
+// ---------------------------------------------------------------------------
+// scenario fold (mpcr_scenario_reduce): candidate i of problem p was rolled
+// out in nscen worlds, rows cs[(p nscen + s) n + i] = total | goal | rot |
+// collision; its aggregated row is the mean of the `worst` rows with the
+// largest total.  Order of the selection: NaN above everything, then
+// descending, -0 == +0, ties to the lower scenario.  Each column: the selected
+// rows added in ascending scenario order, one after the other from the first,
+// then one IEEE division by (float)worst -- worst = nscen the mean, 1 the
+// worst scenario's row itself, between them a CVaR.  One thread per
+// candidate, the problem on the grid's y: a wave's row loads are 64
+// consecutive 16-byte rows.  The rows are read again per pass rather than held
+// (nscen <= 64 of them): they stay in L1 / L2.
+constexpr int SCEN_MAX = 64, SCEN_BLOCK = 256;
+
+__device__ __forceinline__ uint32_t ord_key_nanfirst_desc(float c) {  // larger key = selected earlier
+  if (isnan(c)) return 0xFFFFFFFFu;
+  const uint32_t u = __float_as_uint(c + 0.0f);  // -0 -> +0
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// a / b correctly rounded: this unit divides by reciprocal (build.py's
+// -freciprocal-math, 2.5 ulp fp32 division), so the IEEE sequence is spelled
+// out -- the scaled Newton iteration of the compiler's own expansion
+__device__ __forceinline__ float div_ieee(float a, float b) {
+  bool vcc_d, vcc_n;
+  const float d = __builtin_amdgcn_div_scalef(a, b, false, &vcc_d);
+  const float n = __builtin_amdgcn_div_scalef(a, b, true, &vcc_n);
+  const float r0 = __builtin_amdgcn_rcpf(d);
+  const float e0 = __builtin_fmaf(-d, r0, 1.0f);
+  const float r1 = __builtin_fmaf(e0, r0, r0);
+  const float q0 = n * r1;
+  const float e1 = __builtin_fmaf(-d, q0, n);
+  const float q1 = __builtin_fmaf(e1, r1, q0);
+  const float e2 = __builtin_fmaf(-d, q1, n);
+  return __builtin_amdgcn_div_fixupf(__builtin_amdgcn_div_fmasf(e2, r1, q1, vcc_n), b, a);
+}
+
+__global__ void __launch_bounds__(SCEN_BLOCK) scenario_reduce_kernel(const float4* __restrict__ cs, int nscen, int n,
+                                                                      int worst, float4* __restrict__ out,
+                                                                      unsigned long long* keys, int index_base) {
+  const int i = blockIdx.x * SCEN_BLOCK + threadIdx.x, p = blockIdx.y;
+  const bool live = i < n;
+  unsigned long long k64 = ~0ull;
+  if (live) {
+    const float4* rows = cs + (size_t)p * nscen * n + i;  // scenario s: rows[s n]
+    unsigned long long sel = nscen == 64 ? ~0ull : (1ull << nscen) - 1ull;
+    if (worst < nscen) {
+      // `worst` passes, each taking the largest row not yet taken (a strict
+      // comparison keeps the lower scenario of a tie)
+      sel = 0ull;
+      for (int k = 0; k < worst; k++) {
+        int best = -1;
+        uint32_t bk = 0u;
+        for (int s = 0; s < nscen; s++) {
+          if ((sel >> s) & 1ull) continue;
+          const uint32_t key = ord_key_nanfirst_desc(reinterpret_cast<const float*>(rows + (size_t)s * n)[0]);
+          if (best < 0 || key > bk) { best = s; bk = key; }
+        }
+        sel |= 1ull << best;
+      }
+    }
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    bool first = true;
+    for (int s = 0; s < nscen; s++) {
+      if (!((sel >> s) & 1ull)) continue;
+      const float4 r = rows[(size_t)s * n];
+      if (first) {
+        acc = r;
+        first = false;
+      } else {
+        acc.x += r.x; acc.y += r.y; acc.z += r.z; acc.w += r.w;
+      }
+    }
+    const float w = (float)worst;
+    acc.x = div_ieee(acc.x, w); acc.y = div_ieee(acc.y, w); acc.z = div_ieee(acc.z, w); acc.w = div_ieee(acc.w, w);
+    out[(size_t)p * n + i] = acc;
+    // the rollout kernel's key of the aggregated total: NaN first, then the index
+    const uint32_t u = __float_as_uint(acc.x);
+    const uint32_t key = isnan(acc.x) ? 0u : ((u & 0x80000000u) ? ~u : (u | 0x80000000u));
+    k64 = ((unsigned long long)key << 32) | (uint32_t)(index_base + i);
+  }
+  if (keys) {  // (uniform: every lane reaches the shuffles)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const unsigned long long other = __shfl_xor(k64, o);
+      k64 = other < k64 ? other : k64;
+    }
+    if ((threadIdx.x & 63) == 0 && k64 != ~0ull) atomicMin(keys + p, k64);
+  }
+}
+
 }  // namespace mpcr

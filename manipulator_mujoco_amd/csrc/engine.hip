@@ -517,6 +517,8 @@ struct Launch {
   // the call's geom-pose block, addressed likewise (StateArgs)
   const float* geom_pose = nullptr;
   int geom_stride = 0, geom_step_stride = 0;
+  // scenarios per planning problem that share its input rows (0: none; rollout.h, scen_count)
+  int nscen = 0;
 };
 
 // the kernel's arguments for launch l of engine e (the one place they are filled)
@@ -560,8 +562,9 @@ static int rollout_args(const mpcr_engine* e, const Launch& l, RolloutArgs& a) {
   if (l.dpar) {
     set_state_args(a, StateArgs{l.start, l.final_state, l.start_stride, l.ctrl_stride, l.ctrl_step_stride, l.ctrl,
                                 l.geom_pose, l.geom_stride, l.geom_step_stride});
+    set_scen_count(a, l.nscen);
   } else {
-    if (l.start || l.final_state || l.ctrl || l.geom_pose)
+    if (l.start || l.final_state || l.ctrl || l.geom_pose || l.nscen)
       return fail(MPCR_EINVAL, "state, control and geom-pose blocks need a device parameter block");
     std::memcpy(a.par, l.par, sizeof(a.par));
   }
@@ -666,7 +669,7 @@ static int rollout_dp(mpcr_engine* e, const float* input, int layout, int nprob,
                       int flags, void* stream, const float* start = nullptr, int start_stride = 0,
                       float* final_state = nullptr, const float* ctrl = nullptr, int ctrl_stride = 0,
                       int ctrl_step_stride = 0, const float* geom_pose = nullptr, int geom_stride = 0,
-                      int geom_step_stride = 0) {
+                      int geom_step_stride = 0, int nscen = 1) {
   if (layout != MPCR_LAYOUT_XI && layout != MPCR_LAYOUT_THETADOT) return fail(MPCR_EINVAL, "bad layout %d", layout);
   if (n_per == 0) return MPCR_OK;  // an empty batch: the buffers may be null
   if (!input || !params || !cost4) return fail(MPCR_EINVAL, "null argument");
@@ -681,6 +684,7 @@ static int rollout_dp(mpcr_engine* e, const float* input, int layout, int nprob,
   l.start = start; l.start_stride = start_stride; l.final_state = final_state;
   l.ctrl = ctrl; l.ctrl_stride = ctrl_stride; l.ctrl_step_stride = ctrl_step_stride;
   l.geom_pose = geom_pose; l.geom_stride = geom_stride; l.geom_step_stride = geom_step_stride;
+  l.nscen = nscen > 1 ? nscen : 0;  // (nprob counts the rollout problems: nscen per planning problem)
   int rc = launch_rollout(e, l, st);
   if (rc) return rc;
   if (flags & MPCR_F_SYNC) HIPCHK(hipStreamSynchronize(st));
@@ -734,12 +738,15 @@ static int check_geom_pose_model(const DevModel& d) {
   return fail(MPCR_EINVAL, "geom_pose: the model has no static collision geom");
 }
 
-extern "C" int mpcr_rollout_cost_world(mpcr_engine* e, const float* input, int layout, int nprob, int n_per,
-                                       const float* params, const float* start, int start_stride, float* final_state,
-                                       const float* ctrl, int ctrl_stride, int ctrl_step_stride,
-                                       const float* geom_pose, int geom_stride, int geom_step_stride, float* cost4,
-                                       float* theta, float* thetadot, uint64_t* best_keys, int index_base, int* status,
-                                       int flags, void* stream) {
+// mpcr_rollout_cost_world (nscen = 1) and the rollout of
+// mpcr_rollout_cost_scenarios: nprob rollout problems, every nscen of them
+// in a row the scenarios of one planning problem (input, theta and thetadot
+// then hold nprob / nscen n_per rows)
+static int rollout_world(mpcr_engine* e, const float* input, int layout, int nprob, int nscen, int n_per,
+                         const float* params, const float* start, int start_stride, float* final_state,
+                         const float* ctrl, int ctrl_stride, int ctrl_step_stride, const float* geom_pose,
+                         int geom_stride, int geom_step_stride, float* cost4, float* theta, float* thetadot,
+                         uint64_t* best_keys, int index_base, int* status, int flags, void* stream) {
   if (!e) return fail(MPCR_EINVAL, "null argument");
   if (!(flags & MPCR_F_DEVICE_PTRS)) return fail(MPCR_EINVAL, "mpcr_rollout_cost_state takes device pointers");
   if (int rc = check_multi(nprob, n_per, e->max_n)) return rc;
@@ -792,7 +799,88 @@ extern "C" int mpcr_rollout_cost_world(mpcr_engine* e, const float* input, int l
   return rollout_dp(e, input, layout, nprob, n_per, params, cost4, theta, thetadot, best_keys, index_base, status,
                     flags, stream, start, start ? start_stride : 0, final_state, ctrl, ctrl ? ctrl_stride : 0,
                     ctrl ? ctrl_step_stride : 0, geom_pose, geom_pose ? geom_stride : 0,
-                    geom_pose ? geom_step_stride : 0);
+                    geom_pose ? geom_step_stride : 0, nscen);
+}
+
+extern "C" int mpcr_rollout_cost_world(mpcr_engine* e, const float* input, int layout, int nprob, int n_per,
+                                       const float* params, const float* start, int start_stride, float* final_state,
+                                       const float* ctrl, int ctrl_stride, int ctrl_step_stride,
+                                       const float* geom_pose, int geom_stride, int geom_step_stride, float* cost4,
+                                       float* theta, float* thetadot, uint64_t* best_keys, int index_base, int* status,
+                                       int flags, void* stream) {
+  return rollout_world(e, input, layout, nprob, 1, n_per, params, start, start_stride, final_state, ctrl, ctrl_stride,
+                       ctrl_step_stride, geom_pose, geom_stride, geom_step_stride, cost4, theta, thetadot, best_keys,
+                       index_base, status, flags, stream);
+}
+
+// the shape mpcr_scenario_reduce and mpcr_rollout_cost_scenarios accept
+static int check_scenarios(int nprob, int nscen, int n_per, int worst, int max_n) {
+  if (nscen < 1 || nscen > SCEN_MAX) return fail(MPCR_EINVAL, "nscen=%d outside [1, %d]", nscen, SCEN_MAX);
+  if (worst < 1 || worst > nscen) return fail(MPCR_EINVAL, "worst=%d outside [1, nscen=%d]", worst, nscen);
+  if (nprob < 1 || n_per < 1) return fail(MPCR_EINVAL, "nprob=%d, n_per=%d: both must be >= 1", nprob, n_per);
+  if ((long long)nprob * nscen * n_per > max_n)
+    return fail(MPCR_EINVAL, "nprob=%d x nscen=%d x n_per=%d exceeds max_n=%d", nprob, nscen, n_per, max_n);
+  if (nprob > 65535) return fail(MPCR_EINVAL, "nprob=%d exceeds the grid's 65535", nprob);
+  return MPCR_OK;
+}
+
+// cost4_scen and cost4 are read / written when the kernel runs: device memory
+// on the engine's device, rows 16-byte aligned
+static int check_cost_rows(const mpcr_engine* e, const void* p, const char* name) {
+  hipPointerAttribute_t at;
+  if (hipPointerGetAttributes(&at, p) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != e->device) {
+    (void)hipGetLastError();
+    return fail(MPCR_EINVAL, "%s must be device memory on the engine's device %d", name, e->device);
+  }
+  if (reinterpret_cast<uintptr_t>(p) & 15) return fail(MPCR_EINVAL, "%s=%p: rows are 16-byte aligned", name, p);
+  return MPCR_OK;
+}
+
+extern "C" int mpcr_scenario_reduce(mpcr_engine* e, const float* cost4_scen, int nprob, int nscen, int n_per, int worst,
+                                    float* cost4, uint64_t* best_keys, int index_base, int flags, void* stream) {
+  if (!e || !cost4_scen || !cost4) return fail(MPCR_EINVAL, "null argument");
+  if (!(flags & MPCR_F_DEVICE_PTRS)) return fail(MPCR_EINVAL, "mpcr_scenario_reduce takes device pointers");
+  if (int rc = check_scenarios(nprob, nscen, n_per, worst, e->max_n)) return rc;
+  if (int rc = check_cost_rows(e, cost4_scen, "cost4_scen")) return rc;
+  if (int rc = check_cost_rows(e, cost4, "cost4")) return rc;
+  HIPCHK(hipSetDevice(e->device));
+  hipStream_t st = (hipStream_t)stream;
+  auto* keys = reinterpret_cast<unsigned long long*>(best_keys);
+  if (keys && (flags & MPCR_F_RESET_BEST)) hipLaunchKernelGGL(fill_u64, dim3(nprob), dim3(1), 0, st, keys, ~0ull);
+  hipLaunchKernelGGL(scenario_reduce_kernel, dim3((n_per + SCEN_BLOCK - 1) / SCEN_BLOCK, nprob), dim3(SCEN_BLOCK), 0,
+                     st, reinterpret_cast<const float4*>(cost4_scen), nscen, n_per, worst,
+                     reinterpret_cast<float4*>(cost4), keys, index_base);
+  HIPCHK(hipGetLastError());
+  if (flags & MPCR_F_SYNC) HIPCHK(hipStreamSynchronize(st));
+  return MPCR_OK;
+}
+
+extern "C" int mpcr_rollout_cost_scenarios(mpcr_engine* e, const float* input, int layout, int nprob, int nscen,
+                                           int worst, int n_per, const float* params, const float* start,
+                                           int start_stride, float* final_state, const float* ctrl, int ctrl_stride,
+                                           int ctrl_step_stride, const float* geom_pose, int geom_stride,
+                                           int geom_step_stride, float* cost4_scen, float* cost4, float* theta,
+                                           float* thetadot, uint64_t* best_keys, int index_base, int* status,
+                                           int flags, void* stream) {
+  if (!e) return fail(MPCR_EINVAL, "null argument");
+  if (!(flags & MPCR_F_DEVICE_PTRS)) return fail(MPCR_EINVAL, "mpcr_rollout_cost_scenarios takes device pointers");
+  if (int rc = check_scenarios(nprob, nscen, n_per, worst, e->max_n)) return rc;
+  if (!cost4_scen) return fail(MPCR_EINVAL, "null argument");
+  if (best_keys && !cost4) return fail(MPCR_EINVAL, "best_keys come from the reduction: they need cost4");
+  if (int rc = check_cost_rows(e, cost4_scen, "cost4_scen")) return rc;
+  if (cost4)
+    if (int rc = check_cost_rows(e, cost4, "cost4")) return rc;
+  // the rollout: nprob nscen ordinary problems (no keys: the reduction's), then the fold
+  const int rflags = flags & ~(MPCR_F_SYNC | MPCR_F_RESET_BEST);
+  if (int rc = rollout_world(e, input, layout, nprob * nscen, nscen, n_per, params, start, start_stride, final_state,
+                             ctrl, ctrl_stride, ctrl_step_stride, geom_pose, geom_stride, geom_step_stride, cost4_scen,
+                             theta, thetadot, nullptr, index_base, status, rflags, stream))
+    return rc;
+  if (cost4)
+    return mpcr_scenario_reduce(e, cost4_scen, nprob, nscen, n_per, worst, cost4, best_keys, index_base, flags,
+                                stream);
+  if (flags & MPCR_F_SYNC) HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+  return MPCR_OK;
 }
 
 extern "C" int mpcr_rollout_cost_ctrl(mpcr_engine* e, const float* input, int layout, int nprob, int n_per,

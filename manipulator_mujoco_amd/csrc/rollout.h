@@ -146,12 +146,41 @@ __host__ __device__ inline StateArgs state_args(const RolloutArgs& a) {
   return s;
 }
 inline void set_state_args(RolloutArgs& a, const StateArgs& s) { __builtin_memcpy(a.par, &s, sizeof(s)); }
-// whether a launch starts from, or returns, state blocks, or reads a control
-// or geom-pose block
+// Scenarios (mpcr_rollout_cost_scenarios): the count, for the same calls, in
+// par's bytes right behind the StateArgs (whose size and field order stay as
+// they are); 0 or 1: none.  Rollout problem r = p nscen + s is scenario s of
+// planning problem p: an ordinary problem of the launch (its own parameter,
+// start, ctrl and geom-pose block, its own prob_n rows of cost4 / status /
+// final_state), except that every scenario of p reads the same prob_n input
+// rows -- candidate gi = prob_off + b reads row (r / nscen) prob_n + gi %
+// prob_n -- and that theta and thetadot are written by scenario 0 alone, to
+// that row.  The mapping goes through prob_off, so group_args leaves input,
+// theta and thetadot where they are.  Read by the SCEN instantiations (on top
+// of STATE), which the launchers pick when scenarios().
+constexpr size_t kScenOff = 56;
+static_assert(sizeof(StateArgs) <= kScenOff && kScenOff + sizeof(int) <= sizeof(float) * PAR_N,
+              "the scenario count behind StateArgs, inside par");
+__host__ __device__ inline int scen_count(const RolloutArgs& a) {
+  int n;
+  __builtin_memcpy(&n, reinterpret_cast<const char*>(a.par) + kScenOff, sizeof(n));
+  return n;
+}
+inline void set_scen_count(RolloutArgs& a, int n) {
+  __builtin_memcpy(reinterpret_cast<char*>(a.par) + kScenOff, &n, sizeof(n));
+}
+// whether a launch starts from, or returns, state blocks, reads a control or
+// geom-pose block, or shares its input rows among scenarios (whose kernels
+// are STATE ones, block pointers or not)
 inline bool has_state(const RolloutArgs& a) {
   if (!a.dpar) return false;
   const StateArgs s = state_args(a);
-  return s.start || s.final_state || s.ctrl || s.geom_pose;
+  return s.start || s.final_state || s.ctrl || s.geom_pose || scen_count(a) > 1;
+}
+// the scenarios of a launch (0: none)
+inline int scenarios(const RolloutArgs& a) {
+  if (!a.dpar) return 0;
+  const int n = scen_count(a);
+  return n > 1 ? n : 0;
 }
 
 // Per-block LDS image, sized by the kernel variant: NVW = dense-solve width

@@ -2466,6 +2466,7 @@ enum { AF_TRACE_SLOTS = 1, AF_TRACE_EEF = 2, AF_THETA = 4, AF_TDOUT = 8 };  // A
 #ifdef MPCR_ARGS_BY_VALUE
 #define KA (&args)
 #define KSA (&sa)
+#define KSCEN scen_count(args)
 #define ARGS_HAS(f, expr) (expr)
 #define ARGS_LAST_STEP_FIRST(t, H) true
 #else
@@ -2497,6 +2498,14 @@ __device__ __forceinline__ KernargState ksarg() {
   return (KernargState)(p + offsetof(RolloutArgs, par));
 }
 #define KSA ksarg()
+// the scenario count behind it (rollout.h, kScenOff)
+__device__ __forceinline__ int kscen() {
+  const __attribute__((address_space(4))) char* p =
+      (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(p));
+  return *(const __attribute__((address_space(4))) int*)(p + offsetof(RolloutArgs, par) + kScenOff);
+}
+#define KSCEN kscen()
 #endif
 
 template <class S>
@@ -2953,11 +2962,22 @@ __device__ __forceinline__ mfx16 mfma_rows32(const S& s, const float* gx, int ne
 // same resource usage, C3 measured +0.85 % per step (kernel time 1.528 ->
 // 1.542 ms).  In the other instantiations the STATE terms below fold away at
 // compile time.  Never the plant (plant = 0).
-template <int NVW, int NBW, int NGW, bool WIDE, int WPC = 1, bool MULTI = false, bool STATE = false>
-__global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrowWavesPerSimd)
+// SCEN: a STATE batch whose problems come in groups of scenarios that share
+// their input rows (rollout.h, scen_count > 1; mpcr_rollout_cost_scenarios).
+// Its own instantiation once more, on top of the STATE one, so the twelve
+// others compile to the code they had, spill counts included -- and under
+// the names they had: the flag rides on the waves-per-candidate argument
+// (WPCS = WPC + WPCS_SCEN) instead of lengthening the argument list, which
+// would rename every instantiation.
+constexpr int WPCS_SCEN = 4;
+template <int NVW, int NBW, int NGW, bool WIDE, int WPCS = 1, bool MULTI = false, bool STATE = false>
+__global__ void __launch_bounds__(WAVE * (WPCS & 3), WIDE ? kWideWavesPerSimd : kNarrowWavesPerSimd)
     rollout_kernel(RolloutArgs args, const DevModel* __restrict__ mptr) {
+  constexpr int WPC = WPCS & 3;
+  constexpr bool SCEN = (WPCS & WPCS_SCEN) != 0;
   static_assert(WPC == 1 || WPC == 2, "waves per candidate");
   static_assert(MULTI || !STATE, "the STATE instantiations look the problem's start block up");
+  static_assert(STATE || !SCEN, "scenarios are problems of a STATE launch");
 #ifdef MPCR_ARGS_BY_VALUE
   StateArgs sa = {nullptr, nullptr, 0, 0, 0, nullptr, nullptr, 0, 0};
   if constexpr (STATE) sa = state_args(args);
@@ -3171,13 +3191,25 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
   // by all lanes (theta_dot = A_thetadot xi, SBP/mjx_planner.py:348) into the
   // thetadot output (or a scratch row); each step then reads its value with a
   // load issued one step ahead, so no per-step basis latency is exposed
+  // SCEN: the scenarios of a problem share its input rows -- irow, this
+  // candidate's -- and scenario 0 alone writes theta and thetadot, to that row
+  // (orow; -1: another scenario).  Wave-uniform scalars; b itself otherwise.
+  int irow = b, orow = b;
+  if constexpr (SCEN) {
+    const int ns = KSCEN, pn = KA->prob_n, gi = KA->prob_off + b, pr = gi / pn, pp = pr / ns;
+    irow = pp * pn + (gi - pr * pn);
+    orow = pr == pp * ns ? irow : -1;
+  }
   const float* tdp;
   if (KA->layout == 0) {
-    float* tdw = (KA->thetadot ? KA->thetadot : KA->tdscratch) + (size_t)b * nc * H;
+    // (SCEN: the other scenarios keep their own copy of the table in the scratch rows)
+    float* tdw = SCEN ? (KA->thetadot && orow >= 0 ? KA->thetadot + (size_t)orow * nc * H
+                                                   : KA->tdscratch + (size_t)b * nc * H)
+                      : (KA->thetadot ? KA->thetadot : KA->tdscratch) + (size_t)b * nc * H;
     for (int idx = lane; run_main && !resume && idx < nc * H; idx += WAVE) {
       const int j = idx / H, tt = idx - j * H;
       const float* pd = KA->pdot + (size_t)tt * KA->nbasis;
-      const float* xj = KA->input + ((size_t)b * nc + j) * KA->nbasis;
+      const float* xj = KA->input + ((size_t)(SCEN ? irow : b) * nc + j) * KA->nbasis;
       float v = 0.f;
 #pragma unroll
       for (int k = 0; k < 12; k++)
@@ -3189,7 +3221,7 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
     if constexpr (WPC == 2) block_sync();
     tdp = tdw;
   } else {
-    tdp = KA->input + (size_t)b * nc * H;
+    tdp = KA->input + (size_t)(SCEN ? irow : b) * nc * H;
   }
   float vnext = lane < nc ? tdp[lane * H + t_begin] : 0.f;
   float cost_g = 0.f, cost_r = 0.f, cost_c = 0.f;
@@ -3352,7 +3384,8 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
       const float v = vnext;
       if (t + 1 < H) vnext = tdp[lane * H + t + 1];  // next step's, in flight during this one
       s.qvel[ctrl_da] = v;
-      if (ARGS_HAS(AF_TDOUT, KA->layout != 0 && KA->thetadot)) KA->thetadot[(size_t)b * nc * H + lane * H + t] = v;
+      if (ARGS_HAS(AF_TDOUT, KA->layout != 0 && KA->thetadot) && (!SCEN || orow >= 0))
+        KA->thetadot[(size_t)(SCEN ? orow : b) * nc * H + lane * H + t] = v;
     }
     sync();
 
@@ -5226,7 +5259,8 @@ __global__ void __launch_bounds__(WAVE * WPC, WIDE ? kWideWavesPerSimd : kNarrow
         }
       }
       sync();
-      if (lane < nc && ARGS_HAS(AF_THETA, KA->theta)) KA->theta[(size_t)b * nc * H + lane * H + t] = s.qpos[ctrl_qa];
+      if (lane < nc && ARGS_HAS(AF_THETA, KA->theta) && (!SCEN || orow >= 0))
+        KA->theta[(size_t)(SCEN ? orow : b) * nc * H + lane * H + t] = s.qpos[ctrl_qa];
     }
   }
 

@@ -58,11 +58,15 @@ static RolloutArgs group_args(const RolloutArgs& a, int off, int n) {
     g.index_base = a.index_base + off;
   }
   const size_t in_row = a.layout == 0 ? (size_t)a.nctrl * a.nbasis : (size_t)a.nctrl * a.H;
-  g.input = a.input + o * in_row;
-  g.cost4 = a.cost4 + 4 * o;
   const size_t th_row = (size_t)a.nctrl * a.H;
-  if (a.theta) g.theta = a.theta + o * th_row;
-  if (a.thetadot) g.thetadot = a.thetadot + o * th_row;
+  // scenarios share their input rows, which the kernel finds through
+  // prob_off: input, theta and thetadot stay the call's
+  if (!scenarios(a)) {
+    g.input = a.input + o * in_row;
+    if (a.theta) g.theta = a.theta + o * th_row;
+    if (a.thetadot) g.thetadot = a.thetadot + o * th_row;
+  }
+  g.cost4 = a.cost4 + 4 * o;
   if (a.status) g.status = a.status + o;
   if (a.trace_eef) g.trace_eef = a.trace_eef + o * a.H * 7;
   if (a.trace_slots) g.trace_slots = a.trace_slots + o * a.H * a.nslot;
@@ -148,10 +152,16 @@ void rollout_launch(bool wide, const RolloutArgs& a0, const DevModel* dm, unsign
       hipLaunchKernelGGL((rollout_kernel<16, 16, 24, false, 1, true>), dim3(grid), dim3(WAVE), 0, st, a, dm);
     else if (!state)
       hipLaunchKernelGGL((rollout_kernel<16, 16, 24, false>), dim3(grid), dim3(WAVE), 0, st, a, dm);
-    else if ((int)grid <= wpc2_max_n())
+    else if (!scenarios(a) && (int)grid <= wpc2_max_n())
       hipLaunchKernelGGL((rollout_kernel<16, 16, 24, false, 2, true, true>), dim3(grid), dim3(2 * WAVE), 0, st, a, dm);
-    else
+    else if (!scenarios(a))
       hipLaunchKernelGGL((rollout_kernel<16, 16, 24, false, 1, true, true>), dim3(grid), dim3(WAVE), 0, st, a, dm);
+    // (scenarios: the SCEN instantiations, after every other for the same reason)
+    else if ((int)grid <= wpc2_max_n())
+      hipLaunchKernelGGL((rollout_kernel<16, 16, 24, false, 2 + WPCS_SCEN, true, true>), dim3(grid), dim3(2 * WAVE), 0, st, a,
+                         dm);
+    else
+      hipLaunchKernelGGL((rollout_kernel<16, 16, 24, false, 1 + WPCS_SCEN, true, true>), dim3(grid), dim3(WAVE), 0, st, a, dm);
   }
 }
 

@@ -23,10 +23,16 @@ void rollout_wide_launch(int wpc, unsigned grid, hipStream_t st, const RolloutAr
     hipLaunchKernelGGL((rollout_kernel<32, 32, 72, true, 1, true>), dim3(grid), dim3(WAVE), 0, st, a, dm);
   else if (!state)
     hipLaunchKernelGGL((rollout_kernel<32, 32, 72, true>), dim3(grid), dim3(WAVE), 0, st, a, dm);
-  else if (wpc == 2)
+  else if (!scenarios(a) && wpc == 2)
     hipLaunchKernelGGL((rollout_kernel<32, 32, 72, true, 2, true, true>), dim3(grid), dim3(2 * WAVE), 0, st, a, dm);
-  else
+  else if (!scenarios(a))
     hipLaunchKernelGGL((rollout_kernel<32, 32, 72, true, 1, true, true>), dim3(grid), dim3(WAVE), 0, st, a, dm);
+  // scenarios (scen_count > 1): the SCEN instantiations, named after every other
+  else if (wpc == 2)
+    hipLaunchKernelGGL((rollout_kernel<32, 32, 72, true, 2 + WPCS_SCEN, true, true>), dim3(grid), dim3(2 * WAVE), 0, st, a,
+                       dm);
+  else
+    hipLaunchKernelGGL((rollout_kernel<32, 32, 72, true, 1 + WPCS_SCEN, true, true>), dim3(grid), dim3(WAVE), 0, st, a, dm);
 }
 hipError_t rollout_wide_occupancy(int* info) {
   const void* k = reinterpret_cast<const void*>(&rollout_kernel<32, 32, 72, true>);

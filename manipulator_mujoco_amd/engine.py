@@ -420,6 +420,109 @@ class Engine:
                                 ctrl_per_step=ctrl_per_step, geom_pose=geom_pose,
                                 geom_pose_per_step=geom_pose_per_step)
 
+    @staticmethod
+    def _cost_rows(name, t, rows, device=None):
+        import torch
+        if (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous()
+                or (device is not None and t.device != device)):
+            raise ValueError(f"{name} must be a contiguous float32 CUDA tensor")
+        if t.numel() != rows * 4 or t.shape[-1] != 4:
+            raise ValueError(f"{name} must hold {rows} rows of 4; got {tuple(t.shape)}")
+
+    def scenario_reduce(self, cost4_scen, nprob: int, nscen: int, worst: int, cost4=None, best_keys=None,
+                        index_base: int = 0, reset_best: bool = True, stream=None):
+        """Fold per-scenario costs into one row per candidate
+        (``mpcr_scenario_reduce``).  ``cost4_scen``: a device tensor of
+        nprob * nscen * n_per rows of 4, candidate i of problem p in scenario s
+        at row (p nscen + s) n_per + i.  Per candidate the ``worst`` rows with
+        the largest total are averaged, column by column: ``worst`` = nscen is
+        the mean, 1 the worst scenario's row, between them a CVaR.  Returns
+        ``cost4`` (nprob * n_per, 4); ``best_keys`` (int64, nprob elements)
+        receives the packed argmin key of the aggregated total per problem.
+        Graph-capturable."""
+        import torch
+        nprob, nscen, worst = int(nprob), int(nscen), int(worst)
+        if nprob < 1 or nscen < 1:
+            raise ValueError(f"nprob={nprob}, nscen={nscen}: both must be >= 1")
+        if not isinstance(cost4_scen, torch.Tensor):
+            raise ValueError("cost4_scen must be a contiguous float32 CUDA tensor")
+        rows = cost4_scen.numel() // 4
+        if rows % (nprob * nscen):
+            raise ValueError(f"cost4_scen rows ({rows}) must split evenly over nprob={nprob} x nscen={nscen}")
+        n_per = rows // (nprob * nscen)
+        self._cost_rows("cost4_scen", cost4_scen, rows)
+        if cost4 is None:
+            cost4 = torch.empty((nprob * n_per, 4), dtype=torch.float32, device=cost4_scen.device)
+        self._cost_rows("cost4", cost4, nprob * n_per, cost4_scen.device)
+        if best_keys is not None and best_keys.numel() < nprob:
+            raise ValueError("best_keys needs nprob elements")
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        st = stream if stream is not None else torch.cuda.current_stream(cost4_scen.device).cuda_stream
+        flags = MPCR_F_DEVICE_PTRS | (MPCR_F_RESET_BEST if reset_best else 0)
+        check(_lib.load().mpcr_scenario_reduce(self.handle, ptr(cost4_scen), nprob, nscen, n_per, worst, ptr(cost4),
+                                               ptr(best_keys), int(index_base), flags, ctypes.c_void_p(st)))
+        return cost4
+
+    def rollout_cost_scenarios(self, inp, layout: int, params, nprob: int, nscen: int, cost4_scen, worst=None,
+                               cost4=None, start=None, final_state=None, theta=None, thetadot=None, best_keys=None,
+                               index_base: int = 0, status=None, reset_best: bool = True, stream=None, ctrl=None,
+                               ctrl_per_step: bool = False, geom_pose=None, geom_pose_per_step: bool = False):
+        """One set of candidates priced in ``nscen`` scenarios per problem
+        (``mpcr_rollout_cost_scenarios``).  ``inp`` holds nprob * n_per rows;
+        rollout problem r = p nscen + s is scenario s of problem p and is
+        addressed like a problem of ``rollout_cost_state``: ``params`` is
+        (nprob * nscen, 20), and ``start`` / ``ctrl`` / ``geom_pose`` hold one
+        block for all or one per rollout problem (leading size nprob * nscen).
+        ``cost4_scen``, ``status`` and ``final_state`` have nprob * nscen *
+        n_per rows; ``theta`` and ``thetadot`` nprob * n_per, written by
+        scenario 0.  ``cost4`` (nprob * n_per, 4; None skips the fold) receives
+        ``scenario_reduce`` with ``worst`` (default nscen: the mean), and
+        ``best_keys`` (needs ``cost4``) its keys.  Each scenario's slice is
+        bitwise the ``rollout_cost_state`` call on that scenario's blocks.
+        Returns ``cost4`` (or ``cost4_scen`` without one).  Graph-capturable."""
+        import torch
+        nprob, nscen = int(nprob), int(nscen)
+        worst = nscen if worst is None else int(worst)
+        for name, t in (("input", inp), ("params", params)):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous float32 CUDA tensor")
+        n = int(inp.shape[0])
+        if nprob < 1 or nscen < 1 or n % nprob:
+            raise ValueError(f"input rows ({n}) must split evenly over nprob={nprob} problems (nscen={nscen} >= 1)")
+        n_per, R = n // nprob, nprob * nscen
+        if params.numel() < 20 * R:
+            raise ValueError("params needs 20 floats per problem and scenario")
+        self._cost_rows("cost4_scen", cost4_scen, R * n_per, inp.device)
+        if cost4 is not None:
+            self._cost_rows("cost4", cost4, n, inp.device)
+        if best_keys is not None and (cost4 is None or best_keys.numel() < nprob):
+            raise ValueError("best_keys needs nprob elements and cost4 (the keys come from the fold)")
+        blk = self.state_layout()["size"]
+        for name, t in (("start", start), ("final_state", final_state)):
+            if t is not None and (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32
+                                  or not t.is_contiguous() or t.device != inp.device):
+                raise ValueError(f"{name} must be a contiguous float32 CUDA tensor on the input's device")
+        stride = 0
+        if start is not None:
+            if start.numel() not in (blk, R * blk) or start.shape[-1] != blk:
+                raise ValueError(f"start must hold one block of {blk} floats, or one per problem and scenario")
+            stride = blk if R > 1 and start.numel() == R * blk else 0
+        if final_state is not None and (final_state.numel() != R * n_per * blk or final_state.shape[-1] != blk):
+            raise ValueError(f"final_state must be ({R * n_per}, {blk})")
+        if status is not None and status.numel() < R * n_per:
+            raise ValueError(f"status needs {R * n_per} elements")
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        cargs = self._ctrl_args(ctrl, ctrl_per_step, R, inp.device) if ctrl is not None else (None, 0, 0)
+        gargs = (self._geom_pose_args(geom_pose, geom_pose_per_step, R, inp.device) if geom_pose is not None
+                 else (None, 0, 0))
+        st = stream if stream is not None else torch.cuda.current_stream(inp.device).cuda_stream
+        flags = MPCR_F_DEVICE_PTRS | (MPCR_F_RESET_BEST if reset_best else 0)
+        check(_lib.load().mpcr_rollout_cost_scenarios(
+            self.handle, ptr(inp), layout, nprob, nscen, worst, n_per, ptr(params), ptr(start), stride,
+            ptr(final_state), *cargs, *gargs, ptr(cost4_scen), ptr(cost4), ptr(theta), ptr(thetadot), ptr(best_keys),
+            int(index_base), ptr(status), flags, ctypes.c_void_p(st)))
+        return cost4 if cost4 is not None else cost4_scen
+
     def trace(self, inp, layout: int, q0, w, ptgt, qtgt):
         """Debug/parity run (host arrays): cost4, theta, per-step eef pose, masked slot distances."""
         lib = _lib.load()

@@ -109,7 +109,8 @@ def run_cem_planner(num_dof=None, num_batch=None, num_steps=None, maxiter_cem=No
                     target_names=None, show_viewer=None, cam_distance=None, show_contact_points=None,
                     position_threshold=None, rotation_threshold=None, save_data=None, data_dir=None,
                     stop_at_final_target=None, *, max_ticks=100, model_path=None, device=None, graph=True,
-                    verbose=True, planner_kwargs=None, plan_from_state=False, ctrl=None, geom_poses=None):
+                    verbose=True, planner_kwargs=None, plan_from_state=False, ctrl=None, geom_poses=None,
+                    hypotheses=None, scenario_worst=None):
     """Run the CEM planner in closed loop for ``max_ticks`` ticks (headless).
     plan_from_state: every tick's rollouts start from the plant's full state
     (a device copy of its block) instead of the template state with the arm
@@ -123,7 +124,14 @@ def run_cem_planner(num_dof=None, num_batch=None, num_steps=None, maxiter_cem=No
     plant) -> block`` (``moving_obstacle``), given every tick to the plant and
     to the planner's rollouts; the callable may return ``(block, schedule)``
     with a per-step schedule (num_steps, ng, 8) for the planner's horizon.
-    None keeps the model's poses in both."""
+    None keeps the model's poses in both.
+    hypotheses: ``[(geom name, (dx, dy, dz)), ...]``, world hypotheses the
+    planner prices every candidate in besides the plant's own world (scenario
+    0): each adds a scenario in which that static geom is displaced by the
+    offset (m, world) from wherever the tick's poses put it
+    (``cem_planner(num_scenarios=)``).  scenario_worst: a candidate's cost is
+    the mean of its that many largest scenario costs (default: of all)."""
+    hypotheses = list(hypotheses or [])
     if initial_qpos is None:
         initial_qpos = [1.5, -1.8, 1.75, -1.25, -1.6, 0]
     if target_names is None:
@@ -145,7 +153,10 @@ def run_cem_planner(num_dof=None, num_batch=None, num_steps=None, maxiter_cem=No
                       verbose=verbose, **({"return_rollouts": False} | (planner_kwargs or {})
                                           | ({"plan_from_state": True} if plan_from_state else {})
                                           | ({"actuator_ctrl": True} if ctrl is not None else {})
-                                          | ({"geom_poses": "per_step"} if geom_poses is not None else {})))
+                                          | ({"geom_poses": "per_step"} if geom_poses is not None or hypotheses
+                                             else {})
+                                          | ({"num_scenarios": 1 + len(hypotheses), "scenario_worst": scenario_worst}
+                                             if hypotheses else {})))
     log(f"Initialized CEM Planner: {round(time.time() - start_time, 2)}s")
 
     model = cem.model
@@ -179,14 +190,33 @@ def run_cem_planner(num_dof=None, num_batch=None, num_steps=None, maxiter_cem=No
         data.set_ctrl(c)
         return {"ctrl": c}
 
+    hyp_rows = []  # (row of the geom-pose block, world offset) per hypothesis
+    if hypotheses:
+        own_block, _, fixed = data.model.geom_poses()
+        for name, d in hypotheses:
+            row = data.model.geom_row(name)
+            if not fixed[row]:
+                raise ValueError(f"hypothesis: geom {name!r} is not static")
+            hyp_rows.append((row, np.asarray(d, dtype=np.float32).reshape(3)))
+
     def apply_geom_poses(tick):
-        """The tick's geom poses to the plant; the planner's argument for them."""
-        if geom_poses is None:
+        """The tick's geom poses to the plant; the planner's argument for them
+        (with hypotheses: one schedule per scenario, the plant's world first)."""
+        if geom_poses is None and not hyp_rows:
             return {}
-        g = geom_poses(tick, data) if callable(geom_poses) else geom_poses
-        block, sched = g if isinstance(g, tuple) else (g, g)
-        data.set_geom_poses(block)
-        return {"geom_pose": sched}
+        sched = None
+        if geom_poses is not None:
+            g = geom_poses(tick, data) if callable(geom_poses) else geom_poses
+            block, sched = g if isinstance(g, tuple) else (g, g)
+            data.set_geom_poses(block)
+        if not hyp_rows:
+            return {"geom_pose": sched}
+        base = np.asarray(own_block if sched is None else sched, dtype=np.float32)
+        base = np.broadcast_to(base, (num_steps,) + base.shape[-2:])
+        scen = np.stack([base] * (1 + len(hyp_rows)))
+        for s, (row, d) in enumerate(hyp_rows, start=1):
+            scen[s, :, row, :3] += d
+        return {"geom_pose": scen}
 
     _ = cem.compute_cem(xi_mean, data.qpos[ctrl_q], data.qvel[ctrl_v], data.qacc[ctrl_v], target_pos, target_rot,
                         **from_plant, **apply_ctrl(0), **apply_geom_poses(0))
@@ -301,6 +331,11 @@ def main(argv=None):  # SBP/mpc_planner.py:256-314
     parser.add_argument("--obstacle", nargs=4, default=None, metavar=("NAME", "VX", "VY", "VZ"),
                         help="a named static geom moves at this constant world velocity (m/s): the plant gets its "
                              "pose at each tick's time, the planner the predicted poses of its horizon")
+    parser.add_argument("--hypothesis", nargs=4, action="append", default=None, metavar=("NAME", "DX", "DY", "DZ"),
+                        help="repeatable: one more world the planner prices every candidate in, with this static geom "
+                             "displaced by the offset (m); scenario 0 is the plant's own world")
+    parser.add_argument("--scenario_worst", type=int, default=None, metavar="K",
+                        help="a candidate's cost is the mean of its K largest scenario costs (default: of all)")
     a = parser.parse_args(argv)
     geom_poses = None
     if a.obstacle is not None:
@@ -320,7 +355,9 @@ def main(argv=None):  # SBP/mpc_planner.py:256-314
                            save_data=a.save_data, data_dir=a.data_dir,
                            stop_at_final_target=not a.continue_after_final, max_ticks=a.max_ticks,
                            model_path=a.model, graph=not a.no_graph, plan_from_state=a.plan_from_state,
-                           ctrl=ctrl, geom_poses=geom_poses)
+                           ctrl=ctrl, geom_poses=geom_poses,
+                           hypotheses=[(h[0], [float(x) for x in h[1:]]) for h in a.hypothesis or []],
+                           scenario_worst=a.scenario_worst)
 
 
 if __name__ == "__main__":

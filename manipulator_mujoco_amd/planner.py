@@ -30,6 +30,13 @@ planner calls the ``*_multi`` entry points over its B problems, and the
 default B = 1 is their ``nprob = 1`` case (the one-problem kernels), which
 ``compute_cem`` and ``compute_cem_batch`` share, captured graph included.
 
+With ``num_scenarios=S`` each problem makes one plan against S world
+hypotheses (scenarios): the samples are drawn and projected once, rolled out
+in every scenario's world (its own start state, controls and geom poses) by
+one launch, and folded per candidate -- mean, worst case or the mean of the
+``scenario_worst`` worst (``Engine.scenario_reduce``) -- into the costs the
+elites, the update and the best key see.  The default S = 1 is the path above.
+
 Reference behaviours kept on purpose, each behind a flag:
   * elites are gathered from the *unprojected* samples (``elite_from_filtered=False``)
   * the sampling key is not advanced across calls (fixed ``seed`` per call)
@@ -113,16 +120,35 @@ class cem_planner:  # noqa: N801 (reference name)
                         (ng, 8) per problem; "per_step", one block per step of
                         the horizon (H, ng, 8), an obstacle that moves during
                         it.  Independent of the two above
+    num_scenarios       world hypotheses per problem (default 1: none).  With
+                        S > 1 the state, control and geom-pose buffers hold
+                        one block per problem and scenario -- ``compute_cem``'s
+                        ``state`` / ``ctrl`` / ``geom_pose`` take a leading (S,
+                        ...) axis (``state``: a list of S), an input without
+                        it goes to every scenario -- every candidate is rolled
+                        out in each, and the CEM step runs once per problem on
+                        the folded costs.  ``scenario_costs`` keeps the
+                        per-scenario ones; the 9-tuple's trajectories are
+                        scenario 0's, the nominal one.  One rank only
+    scenario_worst      k: a candidate's cost is the mean of its k largest
+                        scenario costs (default S, the mean; 1, the worst case)
     """
 
     def __init__(self, num_dof=None, num_batch=None, num_steps=None, timestep=None, maxiter_cem=None,
                  num_elite=None, w_pos=None, w_rot=None, w_col=None, maxiter_projection=None, *,
                  model_path=None, device=None, seed=0, elite_from_filtered=False, graph=False, group=None,
                  gather_rollouts=False, return_rollouts=True, capture_exchange=True, verbose=True,
-                 num_problems=1, seed_step=0, plan_from_state=False, actuator_ctrl=False, geom_poses=False):
+                 num_problems=1, seed_step=0, plan_from_state=False, actuator_ctrl=False, geom_poses=False,
+                 num_scenarios=1, scenario_worst=None):
         import torch
         import torch.distributed as tdist
 
+        self.num_scenarios = int(num_scenarios)
+        if not 1 <= self.num_scenarios <= 64:
+            raise ValueError(f"num_scenarios={self.num_scenarios} outside [1, 64]")
+        self.scenario_worst = self.num_scenarios if scenario_worst is None else int(scenario_worst)
+        if not 1 <= self.scenario_worst <= self.num_scenarios:
+            raise ValueError(f"scenario_worst={self.scenario_worst} outside [1, num_scenarios={self.num_scenarios}]")
         if not torch.cuda.is_available():
             raise _lib.MpcrError("cem_planner needs a gfx950 GPU (no CPU fallback)")
         self.num_dof = int(num_dof)
@@ -160,6 +186,9 @@ class cem_planner:  # noqa: N801 (reference name)
         if self.num_problems > 1 and self.world > 1:
             raise ValueError(f"num_problems={self.num_problems} with {self.world} ranks: sharded multi-problem "
                              "planning is not supported")
+        if self.num_scenarios > 1 and self.world > 1:
+            raise ValueError(f"num_scenarios={self.num_scenarios} with {self.world} ranks: sharded scenario planning "
+                             "is not supported")
         self.exchange = self.world > 1  # elites through gather_elites (forced on one rank in tests)
         self.index_base = self.rank * self.n_local
 
@@ -179,11 +208,13 @@ class cem_planner:  # noqa: N801 (reference name)
         self.tcp_id = self.model.tcp_site
         n = self.n_local
         B = self.num_problems
-        self.engine = Engine(self.model, self.num, B * n, self.Pdot, device=dev)
+        S = self.num_scenarios
+        self.engine = Engine(self.model, self.num, B * S * n, self.Pdot, device=dev)
         self.cem = CemContext(self.P, self.Pdot, self.Pddot, self.num_dof, B * n, device=dev, num_problems=B)
         f32 = dict(dtype=torch.float32, device=self.device)
         H, it_n = self.num, self.maxiter_cem
         pb = (B,) if B > 1 else ()  # the leading problem axis of every device buffer (none for one problem)
+        sb = (S,) if S > 1 else ()  # the scenario axis of the per-world buffers, after the problem's
         self._key = torch.empty(B, dtype=torch.int64, device=self.device)
         self._eye10 = 10.0 * torch.eye(self.nvar, **f32)  # xi_cov (:386)
         self._mean = torch.empty(pb + (self.nvar,), **f32)
@@ -192,16 +223,19 @@ class cem_planner:  # noqa: N801 (reference name)
         self._xf = torch.empty(pb + (n, self.nvar), **f32)  # xi_filtered
         self._idx = torch.empty(pb + (max(self.ellite_num, 1),), dtype=torch.int32, device=self.device)
         self._beq = torch.empty(pb + (5 * self.num_dof,), **f32)
-        self._par = torch.zeros(pb + (20,), **f32)  # init_pos | weights | target (Engine.params)
+        self._par = torch.zeros(pb + sb + (20,), **f32)  # init_pos | weights | target (Engine.params)
         self._thetadot = torch.empty((it_n,) + pb + (n, self.num_dof * H), **f32)
         self._theta = torch.empty((it_n,) + pb + (n, self.num_dof * H), **f32)
         self._costs = torch.empty((it_n,) + pb + (n, 4), **f32)
         self._mean_in = torch.empty(pb + (self.nvar,), **f32)
+        # every candidate's cost in every scenario; _costs then holds the fold
+        self._scen_costs = torch.empty((it_n, B, S, n, 4), **f32) if S > 1 else None
         # one start state block per problem (Engine.pack_state), the template until a tick stages another
         self.plan_from_state = bool(plan_from_state)
         self._state = None
         if self.plan_from_state:
-            self._state = torch.as_tensor(self.engine.pack_state()).to(self.device).repeat(B, 1).contiguous()
+            self._state = torch.as_tensor(self.engine.pack_state()).to(self.device).repeat(B * S, 1).contiguous()
+            self._state = self._state.view((B,) + sb + (-1,))
         # one control block per problem (actuator order), the model's own until a tick stages another
         self.actuator_ctrl = bool(actuator_ctrl)
         self._ctrl = None
@@ -209,7 +243,7 @@ class cem_planner:  # noqa: N801 (reference name)
             own = self.engine.model.own_ctrl().astype(np.float32)
             if own.size == 0:
                 raise ValueError("actuator_ctrl: the model has no actuators")
-            self._ctrl = torch.as_tensor(own).to(self.device).repeat(B, 1).contiguous()
+            self._ctrl = torch.as_tensor(own).to(self.device).repeat(B * S, 1).contiguous().view((B,) + sb + (-1,))
         # one geom-pose block per problem, or per problem and step: the model's own until a tick stages another
         if geom_poses not in (False, True, "per_step"):
             raise ValueError(f"geom_poses={geom_poses!r}: False, True or 'per_step'")
@@ -219,11 +253,19 @@ class cem_planner:  # noqa: N801 (reference name)
             own, _, fixed = self.engine.model.geom_poses()
             if not fixed.any():
                 raise ValueError("geom_poses: the model has no static collision geom")
-            rep = (B, H, 1, 1) if geom_poses == "per_step" else (B, 1, 1)
+            rep = (B * S, H, 1, 1) if geom_poses == "per_step" else (B * S, 1, 1)
             self._gpose = torch.as_tensor(own).to(self.device).repeat(*rep).contiguous()
+            self._gpose = self._gpose.view((B,) + sb + tuple(self._gpose.shape[1:]))
         self._graphs = None
         if verbose and self.rank == 0:
             self.print_info()
+
+    @property
+    def scenario_costs(self):
+        """(maxiter_cem, num_problems, num_scenarios, n, 4) device tensor:
+        every candidate's cost row in every scenario, as the last tick left
+        it (the 9-tuple's costs are their fold); None without scenarios."""
+        return self._scen_costs
 
     def print_info(self):
         _lib.load()
@@ -252,7 +294,17 @@ class cem_planner:  # noqa: N801 (reference name)
                                       index_base=self.index_base)
         out = dict(theta=self._theta[it], thetadot=self._thetadot[it], best_keys=self._key if last else None,
                    index_base=self.index_base)
-        if self.plan_from_state or self.actuator_ctrl or self.geom_poses:
+        S = self.num_scenarios
+        if S > 1:
+            # every scenario of a problem rolls out the problem's samples in its
+            # own world; the fold leaves one cost row per candidate (and the keys)
+            flat = lambda t: None if t is None else t.view((B * S,) + tuple(t.shape[2:]))  # noqa: E731
+            self.engine.rollout_cost_scenarios(self._xf.view(B * n, self.nvar), MPCR_LAYOUT_XI, self._par, B, S,
+                                               self._scen_costs[it], worst=self.scenario_worst, cost4=self._costs[it],
+                                               start=flat(self._state), ctrl=flat(self._ctrl),
+                                               geom_pose=flat(self._gpose),
+                                               geom_pose_per_step=self.geom_poses == "per_step", **out)
+        elif self.plan_from_state or self.actuator_ctrl or self.geom_poses:
             # the same launch, reading each problem's start / control / geom-pose block
             self.engine.rollout_cost_state(self._xf.view(B * n, self.nvar), MPCR_LAYOUT_XI, self._par, B,
                                            self._costs[it], start=self._state, ctrl=self._ctrl,
@@ -353,6 +405,8 @@ class cem_planner:  # noqa: N801 (reference name)
         # compute_boundary_vec (:174-178)
         self._beq.copy_(torch.as_tensor(st.reshape(B, 5 * d).astype(np.float32)).view(self._beq.shape))
         par = np.stack([Engine.params(init_pos[p], weights[p], target_pos[p], target_rot[p]) for p in range(B)])
+        if self.num_scenarios > 1:  # every scenario of a problem has the problem's parameters
+            par = np.repeat(par[:, None], self.num_scenarios, axis=1)
         self._par.copy_(torch.as_tensor(par).view(self._par.shape))
 
     def _stage_states(self, states):
@@ -366,15 +420,24 @@ class cem_planner:  # noqa: N801 (reference name)
             raise ValueError("a start state needs a planner built with plan_from_state=True")
         if len(states) != self.num_problems:
             raise ValueError(f"{len(states)} start states for {self.num_problems} problem(s)")
+        S = self.num_scenarios
         for p, st in enumerate(states):
             if st is None:
                 continue
-            if hasattr(st, "copy_state"):
-                st.copy_state(self._state[p])
-            else:
-                if not 2 <= len(st) <= 3:
-                    raise ValueError("a start state is a Plant or (qpos, qvel[, qacc_warmstart])")
-                self._state[p].copy_(torch.as_tensor(self.engine.pack_state(*st)))
+            # scenarios: a list holds one start state per scenario, anything else goes to each
+            per = st if S > 1 and isinstance(st, list) else [st] * S
+            if len(per) != S:
+                raise ValueError(f"{len(per)} start states for {S} scenarios")
+            for sc, e in enumerate(per):
+                if e is None:
+                    continue
+                dst = self._state[p, sc] if S > 1 else self._state[p]
+                if hasattr(e, "copy_state"):
+                    e.copy_state(dst)
+                else:
+                    if not 2 <= len(e) <= 3:
+                        raise ValueError("a start state is a Plant or (qpos, qvel[, qacc_warmstart])")
+                    dst.copy_(torch.as_tensor(self.engine.pack_state(*e)))
 
     def _stage_ctrls(self, ctrls):
         """Each problem's actuator controls (nu values, actuator order) into
@@ -387,14 +450,17 @@ class cem_planner:  # noqa: N801 (reference name)
             raise ValueError("actuator controls need a planner built with actuator_ctrl=True")
         if len(ctrls) != self.num_problems:
             raise ValueError(f"{len(ctrls)} control blocks for {self.num_problems} problem(s)")
-        nu = self._ctrl.shape[1]
+        nu = self._ctrl.shape[-1]
+        full = tuple(self._ctrl.shape[1:])  # (nu,), or (S, nu) with scenarios
         for p, c in enumerate(ctrls):
             if c is None:
                 continue
             c = np.asarray(c, dtype=np.float32)
-            if c.shape != (nu,):
-                raise ValueError(f"a control block holds nu={nu} values, got shape {c.shape}")
-            self._ctrl[p].copy_(torch.as_tensor(np.ascontiguousarray(c)))
+            if c.shape != (nu,) and c.shape != full:
+                raise ValueError(f"a control block holds nu={nu} values" + (f" (or {full}, one row per scenario)"
+                                                                             if len(full) == 2 else "")
+                                 + f", got shape {c.shape}")
+            self._ctrl[p].copy_(torch.as_tensor(np.broadcast_to(c, full).copy()))
 
     def _stage_geom_poses(self, blocks):
         """Each problem's geom-pose block into the static buffer: (ng, 8) or,
@@ -409,15 +475,19 @@ class cem_planner:  # noqa: N801 (reference name)
             raise ValueError("geom poses need a planner built with geom_poses=True or 'per_step'")
         if len(blocks) != self.num_problems:
             raise ValueError(f"{len(blocks)} geom-pose blocks for {self.num_problems} problem(s)")
-        full = tuple(self._gpose.shape[1:])
+        # what one problem holds, and one scenario of it: with scenarios a
+        # leading (S, ...) axis, one block (or schedule) per scenario
+        whole = tuple(self._gpose.shape[1:])
+        full = whole[1:] if self.num_scenarios > 1 else whole
         for p, g in enumerate(blocks):
             if g is None:
                 continue
             g = np.asarray(g.cpu() if hasattr(g, "cpu") else g, dtype=np.float32)
-            if g.shape != full and g.shape != full[-2:]:
+            if g.shape != full and g.shape != full[-2:] and g.shape != whole:
                 raise ValueError(f"a geom-pose block is {full[-2:]}"
-                                 + (f" or {full}" if len(full) == 3 else "") + f", got {g.shape}")
-            self._gpose[p].copy_(torch.as_tensor(np.broadcast_to(g, full).copy()))
+                                 + (f" or {full}" if len(full) == 3 else "")
+                                 + (f" or {whole}, one per scenario" if whole != full else "") + f", got {g.shape}")
+            self._gpose[p].copy_(torch.as_tensor(np.broadcast_to(g, whole).copy()))
 
     def compute_cem(self, xi_mean, init_pos=(1.5, -1.8, 1.75, -1.25, -1.6, 0.0), init_vel=None, init_acc=None,
                     target_pos=None, target_rot=None, state=None, ctrl=None, geom_pose=None):

@@ -37,7 +37,8 @@ import sys
 import tempfile
 from collections import Counter
 
-KERNEL = re.compile(r"^(_ZN4mpcr14rollout_kernelILi(\d+)ELi(\d+)ELi(\d+)ELb([01])ELi(\d)ELb([01])ELb([01])E\w+):")
+# (waves per candidate 1 or 2: the scenario instantiations, which add WPCS_SCEN to it, are not part of the census)
+KERNEL = re.compile(r"^(_ZN4mpcr14rollout_kernelILi(\d+)ELi(\d+)ELi(\d+)ELb([01])ELi([12])ELb([01])ELb([01])E\w+):")
 _BLOCK = re.compile(r"^(?:\.L(BB\d+_\d+):|; %bb\.(\d+):)(.*)$")
 _INSN = re.compile(r"^\t([a-z][a-z0-9_]+)(?:\s+(.*))?$")
 _VREG = re.compile(r"\bv(\d+)\b|\bv\[(\d+):(\d+)\]")
