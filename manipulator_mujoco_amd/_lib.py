@@ -20,38 +20,89 @@ MPCR_F_DEVICE_PTRS = 1
 MPCR_F_RESET_BEST = 2
 MPCR_F_SYNC = 4
 
+_vp, _i, _d, _f, _u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_float, ctypes.c_uint64
+_P = ctypes.POINTER
+# the argument types of every entry bound here, in include/mpcr.h's order
+_ARGTYPES = {
+    "mpcr_last_error": [],
+    "mpcr_abi_version": [],
+    "mpcr_device_arch": [_i, ctypes.c_char_p, _i],
+    "mpcr_model_from_blob": [_vp, ctypes.c_size_t, _P(_vp)],
+    "mpcr_model_load": [ctypes.c_char_p, _d, _P(_vp)],
+    "mpcr_model_set_timestep": [_vp, _d],
+    "mpcr_model_info": [_vp, _P(_i), _P(_i), _P(_i), _P(_i), _P(_i)],
+    "mpcr_model_free": [_vp],
+    "mpcr_engine_create": [_vp, _i, _i, _i, _vp, _i, _P(_vp)],
+    "mpcr_engine_free": [_vp],
+    "mpcr_rollout_cost": [_vp, _vp, _i, _i, _P(_d), _P(_f), _P(_f), _P(_f), _vp, _vp, _vp, _vp, _i, _vp, _i, _vp],
+    "mpcr_argmin": [_vp, _vp, _i, _i, _i, _vp, _P(_i), _P(_f), _i, _vp],
+    "mpcr_best_key_decode": [_u64, _P(_i), _P(_f)],
+    "mpcr_topk": [_vp, _vp, _i, _i, _i, _vp, _i, _vp],
+    "mpcr_cem_create": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _P(_vp)],
+    "mpcr_cem_free": [_vp],
+    "mpcr_cem_factor": [_vp, _vp, _f, _i, _vp],
+    "mpcr_cem_sample_project": [_vp, _i, _vp, _u64, _u64, _i, _vp, _vp, _vp, _i, _i, _P(_f), _f, _vp, _i, _vp],
+    "mpcr_project": [_vp, _vp, _vp, _i, _i, _i, _P(_f), _f, _vp, _i, _vp],
+    "mpcr_cem_update": [_vp, _vp, _i, _vp, _i, _vp, _i, _f, _f, _f, _f, _vp, _vp, _i, _vp],
+    "mpcr_rollout_cost_dp": [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp],
+    "mpcr_plant_create": [_vp, _i, _P(_vp)],
+    "mpcr_plant_free": [_vp],
+    "mpcr_plant_set_state": [_vp, _P(_d), _P(_d), _P(_d)],
+    "mpcr_plant_get_state": [_vp, _P(_d), _P(_d), _P(_d), _P(_d)],
+    "mpcr_plant_step": [_vp, _P(_d), _i, _vp],
+    "mpcr_rollout_occupancy": [_i, _P(_i)],
+    "mpcr_set_two_wave_max_n": [_i],
+    "mpcr_engine_dispatches": [_vp, _i, _P(_i)],
+    "mpcr_comm_unique_id": [ctypes.c_char_p],
+    "mpcr_comm_init": [_i, _i, ctypes.c_char_p, _i, _P(_vp)],
+    "mpcr_comm_free": [_vp],
+    "mpcr_comm_allreduce_key": [_vp, _vp, _i, _vp],
+    "mpcr_comm_allgather": [_vp, _vp, _vp, ctypes.c_size_t, _vp],
+    "mpcr_comm_gather_elites": [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp],
+    "mpcr_model_hull_starts": [_vp, _i, _P(ctypes.c_int32), _P(ctypes.c_int32), _P(ctypes.c_uint8), ctypes.c_int64],
+    "mpcr_set_hull_start_scramble": [_u64],
+    # several problems in one call
+    "mpcr_rollout_cost_multi": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp],
+    "mpcr_topk_multi": [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp],
+    "mpcr_cem_set_problems": [_vp, _i],
+    "mpcr_cem_factor_multi": [_vp, _vp, _i, _f, _i, _vp],
+    "mpcr_cem_sample_project_multi": [_vp, _i, _i, _vp, _u64, _u64, _u64, _i, _vp, _vp, _vp, _i, _P(_f), _f, _vp, _i,
+                                      _vp],
+    "mpcr_cem_update_multi": [_vp, _vp, _i, _i, _vp, _i, _vp, _i, _f, _f, _f, _f, _vp, _vp, _i, _vp],
+    # planning from a state
+    "mpcr_state_layout": [_P(_i), _P(_i), _P(_i), _P(_i), _P(_i)],
+    "mpcr_rollout_cost_state": [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp],
+    "mpcr_plant_copy_state": [_vp, _vp, _vp],
+    # actuator controls as a call input
+    "mpcr_rollout_cost_ctrl": [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i,
+                               _vp],
+    "mpcr_plant_set_ctrl": [_vp, _P(_d)],
+    "mpcr_model_actuators": [_vp, _P(_i), _P(_d), _P(_i)],
+    # static geom poses as a call input
+    "mpcr_rollout_cost_world": [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp,
+                                _i, _vp, _i, _vp],
+    "mpcr_plant_set_geom_poses": [_vp, _P(_f)],
+    "mpcr_model_geom_poses": [_vp, _P(_i), _P(_f), _P(_i), _P(_i)],
+    # the wave-reduction self-test
+    "mpcr_selftest_reduce": [_i, _vp, _i, _vp],
+    # scenarios (one set of candidates, several worlds)
+    "mpcr_rollout_cost_scenarios": [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp,
+                                    _vp, _vp, _vp, _vp, _i, _vp, _i, _vp],
+    "mpcr_scenario_reduce": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp],
+}
 # every symbol include/mpcr.h declares (tests check the exports)
-EXPORTS = (
-    "mpcr_last_error", "mpcr_abi_version", "mpcr_device_arch", "mpcr_model_from_blob", "mpcr_model_load",
-    "mpcr_model_set_timestep", "mpcr_model_info", "mpcr_model_free", "mpcr_engine_create", "mpcr_engine_free",
-    "mpcr_rollout_cost", "mpcr_argmin", "mpcr_best_key_decode", "mpcr_topk", "mpcr_cem_create", "mpcr_cem_free",
-    "mpcr_cem_factor", "mpcr_cem_sample_project", "mpcr_project", "mpcr_cem_update", "mpcr_rollout_cost_dp",
-    "mpcr_plant_create", "mpcr_plant_free", "mpcr_plant_set_state", "mpcr_plant_get_state", "mpcr_plant_step",
-    "mpcr_rollout_occupancy", "mpcr_set_two_wave_max_n", "mpcr_engine_dispatches", "mpcr_comm_unique_id", "mpcr_comm_init", "mpcr_comm_free", "mpcr_comm_allreduce_key",
-    "mpcr_comm_allgather", "mpcr_comm_gather_elites", "mpcr_model_hull_starts", "mpcr_set_hull_start_scramble",
-)
-# the multi-problem additions: a library built before them (MPCR_LIB, A/B runs
-# against an older build) still loads; calling one there raises AttributeError
-_MULTI = ("mpcr_rollout_cost_multi", "mpcr_topk_multi", "mpcr_cem_set_problems", "mpcr_cem_factor_multi",
-          "mpcr_cem_sample_project_multi", "mpcr_cem_update_multi")
-EXPORTS += _MULTI
-# planning from a state, likewise: absent from an older build
-_STATE = ("mpcr_state_layout", "mpcr_rollout_cost_state", "mpcr_plant_copy_state")
-EXPORTS += _STATE
-# actuator controls as a call input, likewise
-_CTRL = ("mpcr_rollout_cost_ctrl", "mpcr_plant_set_ctrl", "mpcr_model_actuators")
-EXPORTS += _CTRL
-# static geom poses as a call input, likewise
-_WORLD = ("mpcr_rollout_cost_world", "mpcr_plant_set_geom_poses", "mpcr_model_geom_poses")
-EXPORTS += _WORLD
-# the wave-reduction self-test, likewise
-_SELFTEST = ("mpcr_selftest_reduce",)
-EXPORTS += _SELFTEST
-# scenarios (one set of candidates, several worlds), likewise
-_SCEN = ("mpcr_rollout_cost_scenarios", "mpcr_scenario_reduce")
-EXPORTS += _SCEN
-_VOID = ("mpcr_last_error", "mpcr_model_free", "mpcr_engine_free", "mpcr_best_key_decode", "mpcr_cem_free",
-         "mpcr_plant_free", "mpcr_comm_free")
+EXPORTS = tuple(_ARGTYPES)
+# debug / parity entries, outside the stable ABI surface
+_ARGTYPES.update({
+    "mpcr_rollout_trace": [_vp, _vp, _i, _i, _P(_d), _P(_f), _P(_f), _P(_f), _vp, _vp, _vp, _vp],
+    "mpcr_plant_step_debug": [_vp, _P(_d), _vp, _i],
+    "mpcr_plant_dbg_size": [],
+})
+# what an entry returns, where it is not the int status
+_VOID = ("mpcr_model_free", "mpcr_engine_free", "mpcr_best_key_decode", "mpcr_cem_free", "mpcr_plant_free",
+         "mpcr_comm_free")
+_RESTYPE = {"mpcr_last_error": ctypes.c_char_p, "mpcr_model_hull_starts": ctypes.c_int64,
+            "mpcr_set_hull_start_scramble": _u64, **dict.fromkeys(_VOID)}
 
 _lib = None
 
@@ -75,104 +126,13 @@ def load():
     except ImportError:
         pass
     lib = ctypes.CDLL(LIB_PATH)
-    vp, i, d, f = ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_float
-    P = ctypes.POINTER
-    lib.mpcr_last_error.restype = ctypes.c_char_p
-    lib.mpcr_abi_version.restype = i
-    lib.mpcr_device_arch.argtypes = [i, ctypes.c_char_p, i]
-    lib.mpcr_model_from_blob.argtypes = [vp, ctypes.c_size_t, P(vp)]
-    lib.mpcr_model_load.argtypes = [ctypes.c_char_p, d, P(vp)]
-    lib.mpcr_model_set_timestep.argtypes = [vp, d]
-    lib.mpcr_model_info.argtypes = [vp, P(i), P(i), P(i), P(i), P(i)]
-    lib.mpcr_model_free.argtypes = [vp]
-    lib.mpcr_model_free.restype = None
-    lib.mpcr_engine_create.argtypes = [vp, i, i, i, vp, i, P(vp)]
-    lib.mpcr_engine_free.argtypes = [vp]
-    lib.mpcr_engine_free.restype = None
-    lib.mpcr_rollout_cost.argtypes = [vp, vp, i, i, P(d), P(f), P(f), P(f), vp, vp, vp, vp, i, vp, i, vp]
-    lib.mpcr_rollout_trace.argtypes = [vp, vp, i, i, P(d), P(f), P(f), P(f), vp, vp, vp, vp]
-    lib.mpcr_argmin.argtypes = [vp, vp, i, i, i, vp, P(i), P(f), i, vp]
-    lib.mpcr_best_key_decode.argtypes = [ctypes.c_uint64, P(i), P(f)]
-    lib.mpcr_best_key_decode.restype = None
-    lib.mpcr_topk.argtypes = [vp, vp, i, i, i, vp, i, vp]
-    u64 = ctypes.c_uint64
-    lib.mpcr_cem_create.argtypes = [i, i, i, i, vp, vp, vp, vp, i, P(vp)]
-    lib.mpcr_cem_free.argtypes = [vp]
-    lib.mpcr_cem_free.restype = None
-    lib.mpcr_cem_factor.argtypes = [vp, vp, f, i, vp]
-    lib.mpcr_cem_sample_project.argtypes = [vp, i, vp, u64, u64, i, vp, vp, vp, i, i, P(f), f, vp, i, vp]
-    lib.mpcr_project.argtypes = [vp, vp, vp, i, i, i, P(f), f, vp, i, vp]
-    lib.mpcr_cem_update.argtypes = [vp, vp, i, vp, i, vp, i, f, f, f, f, vp, vp, i, vp]
-    lib.mpcr_rollout_cost_dp.argtypes = [vp, vp, i, i, vp, vp, vp, vp, vp, i, vp, i, vp]
-    lib.mpcr_plant_create.argtypes = [vp, i, P(vp)]
-    lib.mpcr_plant_free.argtypes = [vp]
-    lib.mpcr_plant_free.restype = None
-    lib.mpcr_plant_set_state.argtypes = [vp, P(d), P(d), P(d)]
-    lib.mpcr_plant_get_state.argtypes = [vp, P(d), P(d), P(d), P(d)]
-    lib.mpcr_plant_step.argtypes = [vp, P(d), i, vp]
-    lib.mpcr_rollout_occupancy.argtypes = [i, P(i)]
-    lib.mpcr_set_two_wave_max_n.argtypes = [i]
-    lib.mpcr_engine_dispatches.argtypes = [vp, i, P(i)]
-    lib.mpcr_plant_step_debug.argtypes = [vp, P(d), vp, i]
-    lib.mpcr_plant_dbg_size.argtypes = []
-    lib.mpcr_comm_unique_id.argtypes = [ctypes.c_char_p]
-    lib.mpcr_comm_init.argtypes = [i, i, ctypes.c_char_p, i, P(vp)]
-    lib.mpcr_comm_free.argtypes = [vp]
-    lib.mpcr_comm_free.restype = None
-    lib.mpcr_comm_allreduce_key.argtypes = [vp, vp, i, vp]
-    lib.mpcr_comm_allgather.argtypes = [vp, vp, vp, ctypes.c_size_t, vp]
-    lib.mpcr_comm_gather_elites.argtypes = [vp, vp, vp, i, i, i, vp, vp, vp]
-    lib.mpcr_model_hull_starts.argtypes = [vp, i, P(ctypes.c_int32), P(ctypes.c_int32), P(ctypes.c_uint8), ctypes.c_int64]
-    lib.mpcr_set_hull_start_scramble.argtypes = [u64]
-    multi = {
-        "mpcr_rollout_cost_multi": [vp, vp, i, i, i, vp, vp, vp, vp, vp, i, vp, i, vp],
-        "mpcr_topk_multi": [vp, vp, i, i, i, i, vp, i, vp],
-        "mpcr_cem_set_problems": [vp, i],
-        "mpcr_cem_factor_multi": [vp, vp, i, f, i, vp],
-        "mpcr_cem_sample_project_multi": [vp, i, i, vp, u64, u64, u64, i, vp, vp, vp, i, P(f), f, vp, i, vp],
-        "mpcr_cem_update_multi": [vp, vp, i, i, vp, i, vp, i, f, f, f, f, vp, vp, i, vp],
-    }
-    have_multi = hasattr(lib, _MULTI[0])
-    for name, at in multi.items():
-        if have_multi:
-            getattr(lib, name).argtypes = at
-    state = {
-        "mpcr_state_layout": [P(i), P(i), P(i), P(i), P(i)],
-        "mpcr_rollout_cost_state": [vp, vp, i, i, i, vp, vp, i, vp, vp, vp, vp, vp, i, vp, i, vp],
-        "mpcr_plant_copy_state": [vp, vp, vp],
-    }
-    have_state = hasattr(lib, _STATE[0])
-    for name, at in state.items():
-        if have_state:
-            getattr(lib, name).argtypes = at
-    have_ctrl = hasattr(lib, _CTRL[0])
-    if have_ctrl:
-        lib.mpcr_rollout_cost_ctrl.argtypes = [vp, vp, i, i, i, vp, vp, i, vp, vp, i, i, vp, vp, vp, vp, i, vp, i, vp]
-        lib.mpcr_plant_set_ctrl.argtypes = [vp, P(d)]
-        lib.mpcr_model_actuators.argtypes = [vp, P(i), P(d), P(i)]
-    have_world = hasattr(lib, _WORLD[0])
-    if have_world:
-        lib.mpcr_rollout_cost_world.argtypes = [vp, vp, i, i, i, vp, vp, i, vp, vp, i, i, vp, i, i, vp, vp, vp, vp, i,
-                                                vp, i, vp]
-        lib.mpcr_plant_set_geom_poses.argtypes = [vp, P(f)]
-        lib.mpcr_model_geom_poses.argtypes = [vp, P(i), P(f), P(i), P(i)]
-    have_selftest = hasattr(lib, _SELFTEST[0])
-    if have_selftest:
-        lib.mpcr_selftest_reduce.argtypes = [i, vp, i, vp]
-    have_scen = hasattr(lib, _SCEN[0])
-    if have_scen:
-        lib.mpcr_rollout_cost_scenarios.argtypes = [vp, vp, i, i, i, i, i, vp, vp, i, vp, vp, i, i, vp, i, i, vp, vp, vp,
-                                                    vp, vp, i, vp, i, vp]
-        lib.mpcr_scenario_reduce.argtypes = [vp, vp, i, i, i, i, vp, vp, i, i, vp]
-    for name in EXPORTS + ("mpcr_rollout_trace", "mpcr_plant_step_debug", "mpcr_plant_dbg_size"):
-        if (name in _MULTI and not have_multi) or (name in _STATE and not have_state) or (
-                name in _CTRL and not have_ctrl) or (name in _WORLD and not have_world) or (
-                name in _SELFTEST and not have_selftest) or (name in _SCEN and not have_scen):
-            continue
-        if name not in _VOID:
-            getattr(lib, name).restype = i
-    lib.mpcr_model_hull_starts.restype = ctypes.c_int64
-    lib.mpcr_set_hull_start_scramble.restype = u64
+    # an entry this library does not export stays unbound: a library built
+    # before it (MPCR_LIB, A/B runs against an older build) still loads, and
+    # calling the entry there raises AttributeError
+    for name, argtypes in _ARGTYPES.items():
+        if hasattr(lib, name):
+            fn = getattr(lib, name)
+            fn.argtypes, fn.restype = argtypes, _RESTYPE.get(name, ctypes.c_int)
     _lib = lib
     return lib
 

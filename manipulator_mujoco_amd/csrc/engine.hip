@@ -507,17 +507,9 @@ struct Launch {
   float* dbg = nullptr;
   bool reset_key = false;
   int nprob = 1, prob_n = 0;  // nprob > 1: problems of prob_n candidates each (0: one problem)
-  // a batch's start block per problem (stride in floats) and final block per candidate (RolloutArgs)
-  const float* start = nullptr;
-  float* final_state = nullptr;
-  int start_stride = 0;
-  // the call's control block per problem and, optionally, per step (strides in floats; StateArgs)
-  const float* ctrl = nullptr;
-  int ctrl_stride = 0, ctrl_step_stride = 0;
-  // the call's geom-pose block, addressed likewise (StateArgs)
-  const float* geom_pose = nullptr;
-  int geom_stride = 0, geom_step_stride = 0;
-  // scenarios per planning problem that share its input rows (0: none; rollout.h, scen_count)
+  // the call's state blocks (rollout.h: start / final_state, ctrl, geom_pose; strides in floats) and
+  // the scenarios per planning problem that share its input rows (0: none; scen_count)
+  StateArgs sa = {};
   int nscen = 0;
 };
 
@@ -560,11 +552,10 @@ static int rollout_args(const mpcr_engine* e, const Launch& l, RolloutArgs& a) {
   // bytes (rollout.h; null pointers when it has no state blocks) and never
   // parameter values, so has_state() cannot read those as pointers
   if (l.dpar) {
-    set_state_args(a, StateArgs{l.start, l.final_state, l.start_stride, l.ctrl_stride, l.ctrl_step_stride, l.ctrl,
-                                l.geom_pose, l.geom_stride, l.geom_step_stride});
+    set_state_args(a, l.sa);
     set_scen_count(a, l.nscen);
   } else {
-    if (l.start || l.final_state || l.ctrl || l.geom_pose || l.nscen)
+    if (l.sa.start || l.sa.final_state || l.sa.ctrl || l.sa.geom_pose || l.nscen)
       return fail(MPCR_EINVAL, "state, control and geom-pose blocks need a device parameter block");
     std::memcpy(a.par, l.par, sizeof(a.par));
   }
@@ -608,20 +599,31 @@ extern "C" int mpcr_selftest_reduce(int device, const float* in, int nvec, float
   return MPCR_OK;
 }
 
+static int check_layout(int layout) {
+  if (layout != MPCR_LAYOUT_XI && layout != MPCR_LAYOUT_THETADOT) return fail(MPCR_EINVAL, "bad layout %d", layout);
+  return MPCR_OK;
+}
+
+// a host-pointer entry's input, n rows of the layout, into the engine's staging buffer
+static int stage_input(mpcr_engine* e, const float* input, int layout, int n, hipStream_t st) {
+  const size_t cols = (size_t)e->host.nctrl * (layout == MPCR_LAYOUT_XI ? e->nbasis : e->H);
+  HIPCHK(hipMemcpyAsync(e->d_in, input, sizeof(float) * n * cols, hipMemcpyHostToDevice, st));
+  return MPCR_OK;
+}
+
 extern "C" int mpcr_rollout_cost(mpcr_engine* e, const float* input, int layout, int n, const double* q0,
                                  const float* w, const float* ptgt, const float* qtgt, float* cost4, float* theta,
                                  float* thetadot, uint64_t* best_key, int index_base, int* status, int flags,
                                  void* stream) {
   if (!e || !q0 || !w || !ptgt || !qtgt) return fail(MPCR_EINVAL, "null argument");
   if (n < 0 || n > e->max_n) return fail(MPCR_EINVAL, "n=%d outside [0, max_n=%d]", n, e->max_n);
-  if (layout != MPCR_LAYOUT_XI && layout != MPCR_LAYOUT_THETADOT) return fail(MPCR_EINVAL, "bad layout %d", layout);
+  if (int rc = check_layout(layout)) return rc;
   if (n == 0) return MPCR_OK;  // an empty batch: input / cost4 may be null (a zero-size tensor's data pointer)
   if (!input || !cost4) return fail(MPCR_EINVAL, "null argument");
   HIPCHK(hipSetDevice(e->device));
   hipStream_t st = (hipStream_t)stream;
   auto* key = reinterpret_cast<unsigned long long*>(best_key);
   const int nc = e->host.nctrl;
-  const size_t cols = layout == MPCR_LAYOUT_XI ? (size_t)nc * e->nbasis : (size_t)nc * e->H;
   Launch l;
   l.layout = layout;
   l.n = n;
@@ -635,7 +637,7 @@ extern "C" int mpcr_rollout_cost(mpcr_engine* e, const float* input, int layout,
     if (flags & MPCR_F_SYNC) HIPCHK(hipStreamSynchronize(st));
     return MPCR_OK;
   }
-  HIPCHK(hipMemcpyAsync(e->d_in, input, sizeof(float) * n * cols, hipMemcpyHostToDevice, st));
+  if (int rc = stage_input(e, input, layout, n, st)) return rc;
   l.in = e->d_in; l.cost4 = e->d_cost; l.theta = theta ? e->d_theta : nullptr;
   l.thetadot = thetadot ? e->d_thetadot : nullptr; l.key = best_key ? e->d_key : nullptr;
   l.status = status ? e->d_status : nullptr; l.reset_key = true;
@@ -658,56 +660,6 @@ static int check_multi(int nprob, int n_per, int max_n) {
   if ((long long)nprob * n_per > max_n)
     return fail(MPCR_EINVAL, "nprob=%d x n_per=%d exceeds max_n=%d", nprob, n_per, max_n);
   return MPCR_OK;
-}
-
-// mpcr_rollout_cost_dp (nprob = 1), mpcr_rollout_cost_multi and
-// mpcr_rollout_cost_state (start / final_state, else null).  One problem
-// runs the one-problem kernels through either entry (prob_n = 0): the MULTI
-// instantiations' problem lookup is paid only where there is one to make.
-static int rollout_dp(mpcr_engine* e, const float* input, int layout, int nprob, int n_per, const float* params,
-                      float* cost4, float* theta, float* thetadot, uint64_t* best_keys, int index_base, int* status,
-                      int flags, void* stream, const float* start = nullptr, int start_stride = 0,
-                      float* final_state = nullptr, const float* ctrl = nullptr, int ctrl_stride = 0,
-                      int ctrl_step_stride = 0, const float* geom_pose = nullptr, int geom_stride = 0,
-                      int geom_step_stride = 0, int nscen = 1) {
-  if (layout != MPCR_LAYOUT_XI && layout != MPCR_LAYOUT_THETADOT) return fail(MPCR_EINVAL, "bad layout %d", layout);
-  if (n_per == 0) return MPCR_OK;  // an empty batch: the buffers may be null
-  if (!input || !params || !cost4) return fail(MPCR_EINVAL, "null argument");
-  HIPCHK(hipSetDevice(e->device));
-  hipStream_t st = (hipStream_t)stream;
-  Launch l;
-  l.layout = layout; l.n = nprob * n_per; l.index_base = index_base; l.dpar = params;
-  l.nprob = nprob; l.prob_n = nprob > 1 ? n_per : 0;
-  l.in = input; l.cost4 = cost4; l.theta = theta; l.thetadot = thetadot;
-  l.key = reinterpret_cast<unsigned long long*>(best_keys); l.status = status;
-  l.reset_key = (flags & MPCR_F_RESET_BEST) != 0;
-  l.start = start; l.start_stride = start_stride; l.final_state = final_state;
-  l.ctrl = ctrl; l.ctrl_stride = ctrl_stride; l.ctrl_step_stride = ctrl_step_stride;
-  l.geom_pose = geom_pose; l.geom_stride = geom_stride; l.geom_step_stride = geom_step_stride;
-  l.nscen = nscen > 1 ? nscen : 0;  // (nprob counts the rollout problems: nscen per planning problem)
-  int rc = launch_rollout(e, l, st);
-  if (rc) return rc;
-  if (flags & MPCR_F_SYNC) HIPCHK(hipStreamSynchronize(st));
-  return MPCR_OK;
-}
-
-extern "C" int mpcr_rollout_cost_dp(mpcr_engine* e, const float* input, int layout, int n, const float* params,
-                                    float* cost4, float* theta, float* thetadot, uint64_t* best_key, int index_base,
-                                    int* status, int flags, void* stream) {
-  if (!e) return fail(MPCR_EINVAL, "null argument");
-  if (n < 0 || n > e->max_n) return fail(MPCR_EINVAL, "n=%d outside [0, max_n=%d]", n, e->max_n);
-  return rollout_dp(e, input, layout, 1, n, params, cost4, theta, thetadot, best_key, index_base, status, flags,
-                    stream);
-}
-
-extern "C" int mpcr_rollout_cost_multi(mpcr_engine* e, const float* input, int layout, int nprob, int n_per,
-                                       const float* params, float* cost4, float* theta, float* thetadot,
-                                       uint64_t* best_keys, int index_base, int* status, int flags, void* stream) {
-  if (!e) return fail(MPCR_EINVAL, "null argument");
-  if (!(flags & MPCR_F_DEVICE_PTRS)) return fail(MPCR_EINVAL, "mpcr_rollout_cost_multi takes device pointers");
-  if (int rc = check_multi(nprob, n_per, e->max_n)) return rc;
-  return rollout_dp(e, input, layout, nprob, n_per, params, cost4, theta, thetadot, best_keys, index_base, status,
-                    flags, stream);
 }
 
 extern "C" int mpcr_state_layout(int* qpos, int* qvel, int* qacc_warmstart, int* qacc, int* eef) {
@@ -738,68 +690,100 @@ static int check_geom_pose_model(const DevModel& d) {
   return fail(MPCR_EINVAL, "geom_pose: the model has no static collision geom");
 }
 
-// mpcr_rollout_cost_world (nscen = 1) and the rollout of
-// mpcr_rollout_cost_scenarios: nprob rollout problems, every nscen of them
-// in a row the scenarios of one planning problem (input, theta and thetadot
-// then hold nprob / nscen n_per rows)
-static int rollout_world(mpcr_engine* e, const float* input, int layout, int nprob, int nscen, int n_per,
-                         const float* params, const float* start, int start_stride, float* final_state,
-                         const float* ctrl, int ctrl_stride, int ctrl_step_stride, const float* geom_pose,
-                         int geom_stride, int geom_step_stride, float* cost4, float* theta, float* thetadot,
-                         uint64_t* best_keys, int index_base, int* status, int flags, void* stream) {
-  if (!e) return fail(MPCR_EINVAL, "null argument");
-  if (!(flags & MPCR_F_DEVICE_PTRS)) return fail(MPCR_EINVAL, "mpcr_rollout_cost_state takes device pointers");
-  if (int rc = check_multi(nprob, n_per, e->max_n)) return rc;
-  if (start && start_stride != 0 && start_stride < ST_N)
+// whether p is device memory on device d: what a kernel that runs there reads or writes
+static bool device_memory(const void* p, int d) {
+  hipPointerAttribute_t at;
+  if (hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeDevice && at.device == d) return true;
+  (void)hipGetLastError();
+  return false;
+}
+
+// A call's block per problem and, optionally, per step (StateArgs): `name` at
+// p, addressed by `stem`_stride and `stem`_step_stride in floats, one unit of
+// `unit` floats (named `unit_name`) per step.  align: bytes its rows are
+// aligned to (0: no demand).  ctrl: nu floats; geom_pose: 8 ngeom, 16 bytes.
+static int check_block(const mpcr_engine* e, const char* name, const char* stem, const float* p, int stride,
+                       int step_stride, const char* unit_name, int unit, int align) {
+  if (align && ((reinterpret_cast<uintptr_t>(p) & (align - 1)) || (stride & (align / 4 - 1)) ||
+                (step_stride & (align / 4 - 1))))
+    return fail(MPCR_EINVAL, "%s=%p, %s_stride=%d, %s_step_stride=%d: rows are %d-byte aligned (strides are "
+                             "multiples of %d floats)",
+                name, (const void*)p, stem, stride, stem, step_stride, align, align / 4);
+  if (step_stride != 0 && step_stride < unit)
+    return fail(MPCR_EINVAL, "%s_step_stride=%d: 0 (constant over the horizon) or at least %s=%d floats", stem,
+                step_stride, unit_name, unit);
+  const long long rows = step_stride ? (long long)step_stride * (e->H - 1) + unit : unit;  // floats one problem reads
+  if (stride != 0 && stride < rows)
+    return fail(MPCR_EINVAL, "%s_stride=%d: 0 (one block for every problem) or at least the %lld floats a problem "
+                             "reads (%s=%d, %s_step_stride=%d, H=%d)",
+                stem, stride, rows, unit_name, unit, stem, step_stride, e->H);
+  // read by the kernel when it runs
+  if (!device_memory(p, e->device))
+    return fail(MPCR_EINVAL, "%s must be device memory on the engine's device %d", name, e->device);
+  return MPCR_OK;
+}
+
+// Where every device-pointer rollout entry ends, its own checks made and the
+// call described in l: l.nprob rollout problems of l.n candidates in all.
+// The state blocks that are set are validated (a model that cannot take the
+// block refuses first), then the launch and the sync.  One problem runs the
+// one-problem kernels through any entry (prob_n = 0): the MULTI
+// instantiations' problem lookup is paid only where there is one to make.
+static int rollout_call(mpcr_engine* e, Launch& l, int flags, void* stream) {
+  StateArgs& s = l.sa;
+  if (s.start && s.start_stride != 0 && s.start_stride < ST_N)
     return fail(MPCR_EINVAL, "start_stride=%d: 0 (one block for every problem) or at least the block's %d floats",
-                start_stride, (int)ST_N);
-  if (ctrl) {
-    const int nu = e->host.nu;
+                s.start_stride, (int)ST_N);
+  if (s.ctrl) {
     if (int rc = check_ctrl_model(e->host)) return rc;
-    if (ctrl_step_stride != 0 && ctrl_step_stride < nu)
-      return fail(MPCR_EINVAL, "ctrl_step_stride=%d: 0 (constant over the horizon) or at least nu=%d floats",
-                  ctrl_step_stride, nu);
-    const long long rows = ctrl_step_stride ? (long long)ctrl_step_stride * (e->H - 1) + nu : nu;  // floats one problem reads
-    if (ctrl_stride != 0 && ctrl_stride < rows)
-      return fail(MPCR_EINVAL, "ctrl_stride=%d: 0 (one block for every problem) or at least the %lld floats a problem "
-                               "reads (nu=%d, ctrl_step_stride=%d, H=%d)",
-                  ctrl_stride, rows, nu, ctrl_step_stride, e->H);
-    // read by the kernel when it runs: it must be device memory on the engine's device
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, ctrl) != hipSuccess || at.type != hipMemoryTypeDevice ||
-        at.device != e->device) {
-      (void)hipGetLastError();
-      return fail(MPCR_EINVAL, "ctrl must be device memory on the engine's device %d", e->device);
-    }
+    if (int rc = check_block(e, "ctrl", "ctrl", s.ctrl, s.ctrl_stride, s.ctrl_step_stride, "nu", e->host.nu, 0))
+      return rc;
   }
-  if (geom_pose) {
-    const int blk = 8 * e->dev.ngeom;  // floats of one block
+  if (s.geom_pose) {
     if (int rc = check_geom_pose_model(e->dev)) return rc;
-    if ((reinterpret_cast<uintptr_t>(geom_pose) & 15) || (geom_stride & 3) || (geom_step_stride & 3))
-      return fail(MPCR_EINVAL, "geom_pose=%p, geom_stride=%d, geom_step_stride=%d: rows are 16-byte aligned "
-                               "(strides are multiples of 4 floats)",
-                  (const void*)geom_pose, geom_stride, geom_step_stride);
-    if (geom_step_stride != 0 && geom_step_stride < blk)
-      return fail(MPCR_EINVAL, "geom_step_stride=%d: 0 (constant over the horizon) or at least a block's 8 ngeom=%d "
-                               "floats",
-                  geom_step_stride, blk);
-    const long long rows = geom_step_stride ? (long long)geom_step_stride * (e->H - 1) + blk : blk;  // floats one problem reads
-    if (geom_stride != 0 && geom_stride < rows)
-      return fail(MPCR_EINVAL, "geom_stride=%d: 0 (one block for every problem) or at least the %lld floats a "
-                               "problem reads (ngeom=%d, geom_step_stride=%d, H=%d)",
-                  geom_stride, rows, e->dev.ngeom, geom_step_stride, e->H);
-    // read by the kernel when it runs: it must be device memory on the engine's device
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, geom_pose) != hipSuccess || at.type != hipMemoryTypeDevice ||
-        at.device != e->device) {
-      (void)hipGetLastError();
-      return fail(MPCR_EINVAL, "geom_pose must be device memory on the engine's device %d", e->device);
-    }
+    if (int rc = check_block(e, "geom_pose", "geom", s.geom_pose, s.geom_stride, s.geom_step_stride, "8 ngeom",
+                             8 * e->dev.ngeom, 16))
+      return rc;
   }
-  return rollout_dp(e, input, layout, nprob, n_per, params, cost4, theta, thetadot, best_keys, index_base, status,
-                    flags, stream, start, start ? start_stride : 0, final_state, ctrl, ctrl ? ctrl_stride : 0,
-                    ctrl ? ctrl_step_stride : 0, geom_pose, geom_pose ? geom_stride : 0,
-                    geom_pose ? geom_step_stride : 0, nscen);
+  // a block that is not set has no strides
+  if (!s.start) s.start_stride = 0;
+  if (!s.ctrl) s.ctrl_stride = s.ctrl_step_stride = 0;
+  if (!s.geom_pose) s.geom_stride = s.geom_step_stride = 0;
+  if (int rc = check_layout(l.layout)) return rc;
+  if (!l.in || !l.dpar || !l.cost4) return fail(MPCR_EINVAL, "null argument");
+  HIPCHK(hipSetDevice(e->device));
+  hipStream_t st = (hipStream_t)stream;
+  l.prob_n = l.nprob > 1 ? l.n / l.nprob : 0;
+  l.reset_key = (flags & MPCR_F_RESET_BEST) != 0;
+  if (int rc = launch_rollout(e, l, st)) return rc;
+  if (flags & MPCR_F_SYNC) HIPCHK(hipStreamSynchronize(st));
+  return MPCR_OK;
+}
+
+extern "C" int mpcr_rollout_cost_dp(mpcr_engine* e, const float* input, int layout, int n, const float* params,
+                                    float* cost4, float* theta, float* thetadot, uint64_t* best_key, int index_base,
+                                    int* status, int flags, void* stream) {
+  if (!e) return fail(MPCR_EINVAL, "null argument");
+  if (n < 0 || n > e->max_n) return fail(MPCR_EINVAL, "n=%d outside [0, max_n=%d]", n, e->max_n);
+  if (n == 0) return check_layout(layout);  // an empty batch: the buffers may be null
+  Launch l;
+  l.in = input; l.layout = layout; l.n = n; l.dpar = params; l.index_base = index_base;
+  l.cost4 = cost4; l.theta = theta; l.thetadot = thetadot; l.status = status;
+  l.key = reinterpret_cast<unsigned long long*>(best_key);
+  return rollout_call(e, l, flags, stream);
+}
+
+extern "C" int mpcr_rollout_cost_multi(mpcr_engine* e, const float* input, int layout, int nprob, int n_per,
+                                       const float* params, float* cost4, float* theta, float* thetadot,
+                                       uint64_t* best_keys, int index_base, int* status, int flags, void* stream) {
+  if (!e) return fail(MPCR_EINVAL, "null argument");
+  if (!(flags & MPCR_F_DEVICE_PTRS)) return fail(MPCR_EINVAL, "mpcr_rollout_cost_multi takes device pointers");
+  if (int rc = check_multi(nprob, n_per, e->max_n)) return rc;
+  Launch l;
+  l.in = input; l.layout = layout; l.nprob = nprob; l.n = nprob * n_per; l.dpar = params; l.index_base = index_base;
+  l.cost4 = cost4; l.theta = theta; l.thetadot = thetadot; l.status = status;
+  l.key = reinterpret_cast<unsigned long long*>(best_keys);
+  return rollout_call(e, l, flags, stream);
 }
 
 extern "C" int mpcr_rollout_cost_world(mpcr_engine* e, const float* input, int layout, int nprob, int n_per,
@@ -808,9 +792,17 @@ extern "C" int mpcr_rollout_cost_world(mpcr_engine* e, const float* input, int l
                                        const float* geom_pose, int geom_stride, int geom_step_stride, float* cost4,
                                        float* theta, float* thetadot, uint64_t* best_keys, int index_base, int* status,
                                        int flags, void* stream) {
-  return rollout_world(e, input, layout, nprob, 1, n_per, params, start, start_stride, final_state, ctrl, ctrl_stride,
-                       ctrl_step_stride, geom_pose, geom_stride, geom_step_stride, cost4, theta, thetadot, best_keys,
-                       index_base, status, flags, stream);
+  if (!e) return fail(MPCR_EINVAL, "null argument");
+  if (!(flags & MPCR_F_DEVICE_PTRS)) return fail(MPCR_EINVAL, "mpcr_rollout_cost_state takes device pointers");
+  if (int rc = check_multi(nprob, n_per, e->max_n)) return rc;
+  Launch l;
+  l.in = input; l.layout = layout; l.nprob = nprob; l.n = nprob * n_per; l.dpar = params; l.index_base = index_base;
+  l.cost4 = cost4; l.theta = theta; l.thetadot = thetadot; l.status = status;
+  l.key = reinterpret_cast<unsigned long long*>(best_keys);
+  l.sa.start = start; l.sa.start_stride = start_stride; l.sa.final_state = final_state;
+  l.sa.ctrl = ctrl; l.sa.ctrl_stride = ctrl_stride; l.sa.ctrl_step_stride = ctrl_step_stride;
+  l.sa.geom_pose = geom_pose; l.sa.geom_stride = geom_stride; l.sa.geom_step_stride = geom_step_stride;
+  return rollout_call(e, l, flags, stream);
 }
 
 // the shape mpcr_scenario_reduce and mpcr_rollout_cost_scenarios accept
@@ -827,11 +819,8 @@ static int check_scenarios(int nprob, int nscen, int n_per, int worst, int max_n
 // cost4_scen and cost4 are read / written when the kernel runs: device memory
 // on the engine's device, rows 16-byte aligned
 static int check_cost_rows(const mpcr_engine* e, const void* p, const char* name) {
-  hipPointerAttribute_t at;
-  if (hipPointerGetAttributes(&at, p) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != e->device) {
-    (void)hipGetLastError();
+  if (!device_memory(p, e->device))
     return fail(MPCR_EINVAL, "%s must be device memory on the engine's device %d", name, e->device);
-  }
   if (reinterpret_cast<uintptr_t>(p) & 15) return fail(MPCR_EINVAL, "%s=%p: rows are 16-byte aligned", name, p);
   return MPCR_OK;
 }
@@ -870,12 +859,16 @@ extern "C" int mpcr_rollout_cost_scenarios(mpcr_engine* e, const float* input, i
   if (int rc = check_cost_rows(e, cost4_scen, "cost4_scen")) return rc;
   if (cost4)
     if (int rc = check_cost_rows(e, cost4, "cost4")) return rc;
-  // the rollout: nprob nscen ordinary problems (no keys: the reduction's), then the fold
-  const int rflags = flags & ~(MPCR_F_SYNC | MPCR_F_RESET_BEST);
-  if (int rc = rollout_world(e, input, layout, nprob * nscen, nscen, n_per, params, start, start_stride, final_state,
-                             ctrl, ctrl_stride, ctrl_step_stride, geom_pose, geom_stride, geom_step_stride, cost4_scen,
-                             theta, thetadot, nullptr, index_base, status, rflags, stream))
-    return rc;
+  // the rollout: nprob nscen ordinary problems, every nscen of them in a row the scenarios of one planning
+  // problem (input, theta and thetadot hold nprob n_per rows; no keys: the reduction's), then the fold
+  Launch l;
+  l.in = input; l.layout = layout; l.nprob = nprob * nscen; l.n = l.nprob * n_per; l.dpar = params;
+  l.index_base = index_base; l.nscen = nscen > 1 ? nscen : 0;
+  l.cost4 = cost4_scen; l.theta = theta; l.thetadot = thetadot; l.status = status;
+  l.sa.start = start; l.sa.start_stride = start_stride; l.sa.final_state = final_state;
+  l.sa.ctrl = ctrl; l.sa.ctrl_stride = ctrl_stride; l.sa.ctrl_step_stride = ctrl_step_stride;
+  l.sa.geom_pose = geom_pose; l.sa.geom_stride = geom_stride; l.sa.geom_step_stride = geom_step_stride;
+  if (int rc = rollout_call(e, l, flags & ~(MPCR_F_SYNC | MPCR_F_RESET_BEST), stream)) return rc;
   if (cost4)
     return mpcr_scenario_reduce(e, cost4_scen, nprob, nscen, n_per, worst, cost4, best_keys, index_base, flags,
                                 stream);
@@ -982,12 +975,8 @@ extern "C" int mpcr_plant_copy_state(mpcr_plant* p, float* d_dst, void* stream) 
   if (!p || !d_dst) return fail(MPCR_EINVAL, "null argument");
   HIPCHK(hipSetDevice(p->e->device));
   // the copy runs on the plant's device: the destination must live there
-  hipPointerAttribute_t at;
-  if (hipPointerGetAttributes(&at, d_dst) != hipSuccess || at.type != hipMemoryTypeDevice ||
-      at.device != p->e->device) {
-    (void)hipGetLastError();
+  if (!device_memory(d_dst, p->e->device))
     return fail(MPCR_EINVAL, "d_dst must be device memory on the plant's device %d", p->e->device);
-  }
   HIPCHK(hipMemcpyAsync(d_dst, p->d_state, sizeof(float) * ST_N, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return MPCR_OK;
 }
@@ -1034,6 +1023,23 @@ extern "C" int mpcr_plant_set_geom_poses(mpcr_plant* p, const float* block) {
   return MPCR_OK;
 }
 
+// The plant's one-candidate launch on st: the joint velocities v (host, nctrl;
+// the caller syncs before v goes) staged as the input, the state block
+// stepped in place -- plant = 1: forward only, 3: a committed step
+// (RolloutArgs::plant) -- with a zero parameter block, dbg as given.
+static int plant_launch(mpcr_plant* p, const float* v, int plant, float* dbg, hipStream_t st) {
+  mpcr_engine* e = p->e;
+  const int nc = e->host.nctrl;
+  HIPCHK(hipMemcpyAsync(p->d_in, v, sizeof(float) * nc, hipMemcpyHostToDevice, st));
+  Launch l;
+  l.layout = MPCR_LAYOUT_THETADOT; l.n = 1; l.in = p->d_in; l.cost4 = p->d_cost;
+  l.state = p->d_state; l.plant = plant; l.dbg = dbg;
+  const double q0[DX_NCTRL] = {};
+  const float w[3] = {0.f, 0.f, 0.f}, pt[3] = {0.f, 0.f, 0.f}, qt[4] = {1.f, 0.f, 0.f, 0.f};
+  fill_par(l.par, nc, q0, w, pt, qt);
+  return launch_rollout(e, l, st);
+}
+
 // commit = 0: mj_forward (qacc and the eef pose of the current state, nothing
 // advanced; qvel_ctrl ignored); commit = 1: mj_step with qvel[:nctrl] =
 // qvel_ctrl (NULL keeps the current joint velocities)
@@ -1051,15 +1057,7 @@ extern "C" int mpcr_plant_step(mpcr_plant* p, const double* qvel_ctrl, int commi
   } else {
     for (int k = 0; k < nc; k++) v[k] = (float)qvel_ctrl[k];
   }
-  HIPCHK(hipMemcpyAsync(p->d_in, v, sizeof(float) * nc, hipMemcpyHostToDevice, st));
-  Launch l;
-  l.layout = MPCR_LAYOUT_THETADOT; l.n = 1; l.in = p->d_in; l.cost4 = p->d_cost;
-  l.state = p->d_state; l.plant = commit ? 3 : 1;
-  const double q0[DX_NCTRL] = {};
-  const float w[3] = {0.f, 0.f, 0.f}, pt[3] = {0.f, 0.f, 0.f}, qt[4] = {1.f, 0.f, 0.f, 0.f};
-  fill_par(l.par, nc, q0, w, pt, qt);
-  int rc = launch_rollout(e, l, st);
-  if (rc) return rc;
+  if (int rc = plant_launch(p, v, commit ? 3 : 1, nullptr, st)) return rc;
   HIPCHK(hipStreamSynchronize(st));
   return MPCR_OK;
 }
@@ -1083,15 +1081,7 @@ extern "C" int mpcr_plant_step_debug(mpcr_plant* p, const double* qvel_ctrl, flo
   HIPCHK(hipMemset(d_dbg, 0, sizeof(float) * DBG_N));
   const float pf = (float)mpr_pair;  // the pair whose MPR the kernel traces (DBG_MPR), -1: none
   HIPCHK(hipMemcpy(d_dbg + DBG_MPR, &pf, sizeof(float), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(p->d_in, v, sizeof(float) * nc, hipMemcpyHostToDevice));
-  Launch l;
-  l.layout = MPCR_LAYOUT_THETADOT; l.n = 1; l.in = p->d_in; l.cost4 = p->d_cost;
-  l.state = p->d_state; l.plant = 3; l.dbg = d_dbg;
-  const double q0[DX_NCTRL] = {};
-  const float w[3] = {0.f, 0.f, 0.f}, pt[3] = {0.f, 0.f, 0.f}, qt[4] = {1.f, 0.f, 0.f, 0.f};
-  fill_par(l.par, nc, q0, w, pt, qt);
-  int rc = launch_rollout(e, l, 0);
-  if (rc) return rc;
+  if (int rc = plant_launch(p, v, 3, d_dbg, nullptr)) return rc;
   HIPCHK(hipDeviceSynchronize());
   HIPCHK(hipMemcpy(dbg_host, d_dbg, sizeof(float) * DBG_N, hipMemcpyDeviceToHost));
   return MPCR_OK;
@@ -1106,13 +1096,12 @@ extern "C" int mpcr_rollout_trace(mpcr_engine* e, const float* input, int layout
   if (!e || !input || !cost4 || n <= 0 || n > e->max_n) return fail(MPCR_EINVAL, "bad trace arguments");
   HIPCHK(hipSetDevice(e->device));
   const int nc = e->host.nctrl;
-  const size_t cols = layout == MPCR_LAYOUT_XI ? (size_t)nc * e->nbasis : (size_t)nc * e->H;
   const int nslot = e->host.nslot > 0 ? e->host.nslot : 1;
   DevBufs tmp;  // freed on every return
   float* d_eef = tmp.alloc<float>((size_t)n * e->H * 7);
   float* d_slots = tmp.alloc<float>((size_t)n * e->H * nslot);
   if (tmp.rc) return fail(tmp.rc, "device allocation failed");
-  HIPCHK(hipMemcpy(e->d_in, input, sizeof(float) * n * cols, hipMemcpyHostToDevice));
+  if (int rc = stage_input(e, input, layout, n, nullptr)) return rc;
   Launch l;
   l.layout = layout; l.n = n; l.in = e->d_in; l.cost4 = e->d_cost; l.theta = e->d_theta; l.status = e->d_status;
   l.trace_eef = d_eef; l.trace_slots = d_slots;
@@ -1148,15 +1137,13 @@ extern "C" int mpcr_rollout_profile(mpcr_engine* e, const float* input, int layo
                                     const float* w, const float* ptgt, const float* qtgt,
                                     unsigned long long* phases16 /* 64 slots: wave 0, wave 1 (WPC = 2) */) {
   HIPCHK(hipSetDevice(e->device));
-  const int nc = e->host.nctrl;
-  const size_t cols = layout == MPCR_LAYOUT_XI ? (size_t)nc * e->nbasis : (size_t)nc * e->H;
   DevBufs tmp;  // freed on every return
   unsigned long long* d_prof = tmp.alloc<unsigned long long>(64);
   if (tmp.rc) return fail(tmp.rc, "device allocation failed");
   HIPCHK(hipMemset(d_prof, 0, 64 * sizeof(unsigned long long)));
   e->dev.prof = d_prof;  // wave-level counters for this launch only
   HIPCHK(hipMemcpy(e->d_model, &e->dev, sizeof(DevModel), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(e->d_in, input, sizeof(float) * n * cols, hipMemcpyHostToDevice));
+  if (int rc = stage_input(e, input, layout, n, nullptr)) return rc;
   RolloutArgs a;
   if (int rc = prof_args(e, layout, n, q0, w, ptgt, qtgt, d_prof, a)) return rc;
   rollout_launch(e->wide, a, (const DevModel*)e->d_model, n, nullptr);
@@ -1175,13 +1162,11 @@ extern "C" int mpcr_rollout_profile(mpcr_engine* e, const float* input, int layo
 extern "C" int mpcr_rollout_wavetime(mpcr_engine* e, const float* input, int layout, int n, const double* q0,
                                      const float* w, const float* ptgt, const float* qtgt, unsigned long long* out) {
   HIPCHK(hipSetDevice(e->device));
-  const int nc = e->host.nctrl;
-  const size_t cols = layout == MPCR_LAYOUT_XI ? (size_t)nc * e->nbasis : (size_t)nc * e->H;
   DevBufs tmp;  // freed on every return
   unsigned long long* d_prof = tmp.alloc<unsigned long long>(6 * (size_t)n);
   if (tmp.rc) return fail(tmp.rc, "device allocation failed");
   HIPCHK(hipMemset(d_prof, 0, 6 * (size_t)n * sizeof(unsigned long long)));
-  HIPCHK(hipMemcpy(e->d_in, input, sizeof(float) * n * cols, hipMemcpyHostToDevice));
+  if (int rc = stage_input(e, input, layout, n, nullptr)) return rc;
   RolloutArgs a;
   if (int rc = prof_args(e, layout, n, q0, w, ptgt, qtgt, d_prof, a)) return rc;
   rollout_launch(e->wide, a, (const DevModel*)e->d_model, n, nullptr);

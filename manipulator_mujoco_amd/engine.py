@@ -9,6 +9,7 @@ torch stream) or host numpy arrays (staged through the engine's buffers).
 from __future__ import annotations
 
 import ctypes
+import math
 
 import numpy as np
 
@@ -18,6 +19,31 @@ from ._lib import MPCR_F_DEVICE_PTRS, MPCR_F_RESET_BEST, MPCR_LAYOUT_THETADOT, M
 
 def _f32p(a):
     return a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+
+
+def _ptr(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _check_tensor(name, t, device=None):
+    """What every device-pointer call asks of a tensor it hands to the library."""
+    import torch
+    if (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous()
+            or (device is not None and t.device != device)):
+        raise ValueError(f"{name} must be a contiguous float32 CUDA tensor"
+                         + (" on the input's device" if device is not None else ""))
+
+
+def _stream_arg(t, stream):
+    """The stream a call runs on: the current torch stream of ``t``'s device
+    unless one is given."""
+    import torch
+    return ctypes.c_void_p(stream if stream is not None else torch.cuda.current_stream(t.device).cuda_stream)
+
+
+def _call_tail(t, reset_best, stream):
+    """The (flags, stream) that end a device-pointer call."""
+    return MPCR_F_DEVICE_PTRS | (MPCR_F_RESET_BEST if reset_best else 0), _stream_arg(t, stream)
 
 
 class Model:
@@ -226,17 +252,13 @@ class Engine:
             is_torch = False
         n = int(inp.shape[0])
         if is_torch:
-            import torch
-            if not inp.is_cuda or inp.dtype != torch.float32 or not inp.is_contiguous():
-                raise ValueError("input must be a contiguous float32 CUDA tensor")
+            _check_tensor("input", inp)
             if cost4 is None:
                 cost4 = torch.empty((n, 4), dtype=torch.float32, device=inp.device)
-            ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
-            st = stream if stream is not None else torch.cuda.current_stream(inp.device).cuda_stream
-            flags = MPCR_F_DEVICE_PTRS | (MPCR_F_RESET_BEST if reset_best else 0)
-            check(lib.mpcr_rollout_cost(self.handle, ptr(inp), layout, n, q0.ctypes.data_as(dp), _f32p(w),
-                                        _f32p(pt), _f32p(qt), ptr(cost4), ptr(theta), ptr(thetadot),
-                                        ptr(best_key), int(index_base), ptr(status), flags, ctypes.c_void_p(st)))
+            check(lib.mpcr_rollout_cost(self.handle, _ptr(inp), layout, n, q0.ctypes.data_as(dp), _f32p(w),
+                                        _f32p(pt), _f32p(qt), _ptr(cost4), _ptr(theta), _ptr(thetadot),
+                                        _ptr(best_key), int(index_base), _ptr(status),
+                                        *_call_tail(inp, reset_best, stream)))
             return cost4
         inp = np.ascontiguousarray(inp, dtype=np.float32)
         if cost4 is None:
@@ -279,11 +301,10 @@ class Engine:
                     geom_pose_per_step=False):
         """nprob None: ``rollout_cost_dp`` (its own C entry, which takes an
         empty batch); else ``rollout_cost_multi`` or, with state = (start,
-        final_state), ``rollout_cost_state``."""
-        import torch
-        for name, t in (("input", inp), ("params", params), ("cost4", cost4)):
-            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
-                raise ValueError(f"{name} must be a contiguous float32 CUDA tensor")
+        final_state), ``rollout_cost_state`` (``mpcr_rollout_cost_world``,
+        whichever of its blocks are set)."""
+        _check_tensor("input", inp)
+        _check_tensor("cost4", cost4)
         n, lib = int(inp.shape[0]), _lib.load()
         fn, shape = lib.mpcr_rollout_cost_dp, (n,)
         if nprob is not None:
@@ -292,59 +313,58 @@ class Engine:
             if best_keys is not None and best_keys.numel() < nprob:
                 raise ValueError("best_keys needs nprob elements")
             fn, shape = lib.mpcr_rollout_cost_multi, (nprob, n // nprob)
-        if params.numel() < 20 * (nprob or 1):
-            raise ValueError("params needs 20 floats per problem")
-        ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
-        extra = ()
+        args = (self._params_arg(params, nprob or 1),)
         if state is not None:
-            start, final_state = state
-            blk = self.state_layout()["size"]
-            for name, t in (("start", start), ("final_state", final_state)):
-                if t is not None and (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32
-                                      or not t.is_contiguous() or t.device != inp.device):
-                    raise ValueError(f"{name} must be a contiguous float32 CUDA tensor on the input's device")
-            stride = 0
-            if start is not None:
-                if start.numel() not in (blk, nprob * blk) or start.shape[-1] != blk:
-                    raise ValueError(f"start must hold one block of {blk} floats, or one per problem")
-                stride = blk if nprob > 1 and start.numel() == nprob * blk else 0
-            if final_state is not None and (final_state.numel() != n * blk or final_state.shape[-1] != blk):
-                raise ValueError(f"final_state must be ({n}, {blk})")
-            fn, extra = lib.mpcr_rollout_cost_state, (ptr(start), stride, ptr(final_state))
-            if ctrl is not None:
-                extra += self._ctrl_args(ctrl, ctrl_per_step, nprob, inp.device)
-                fn = lib.mpcr_rollout_cost_ctrl
-            if geom_pose is not None:
-                if ctrl is None:
-                    extra += (None, 0, 0)
-                extra += self._geom_pose_args(geom_pose, geom_pose_per_step, nprob, inp.device)
-                fn = lib.mpcr_rollout_cost_world
-        st = stream if stream is not None else torch.cuda.current_stream(inp.device).cuda_stream
-        flags = MPCR_F_DEVICE_PTRS | (MPCR_F_RESET_BEST if reset_best else 0)
-        check(fn(self.handle, ptr(inp), layout, *shape, ptr(params), *extra, ptr(cost4), ptr(theta), ptr(thetadot),
-                 ptr(best_keys), int(index_base), ptr(status), flags, ctypes.c_void_p(st)))
+            fn = lib.mpcr_rollout_cost_world
+            args += self._state_args(nprob, n, inp, *state, ctrl, ctrl_per_step, geom_pose, geom_pose_per_step)
+        check(fn(self.handle, _ptr(inp), layout, *shape, *args, _ptr(cost4), _ptr(theta), _ptr(thetadot),
+                 _ptr(best_keys), int(index_base), _ptr(status), *_call_tail(inp, reset_best, stream)))
         return cost4
 
-    def _ctrl_args(self, ctrl, per_step, nprob, device):
-        """(pointer, problem stride, step stride) of a control tensor: (nu,),
-        (nprob, nu) or, per_step, (nprob, H, nu)."""
-        import torch
-        nu = self.nu
-        if (not isinstance(ctrl, torch.Tensor) or not ctrl.is_cuda or ctrl.dtype != torch.float32
-                or not ctrl.is_contiguous() or ctrl.device != device):
-            raise ValueError("ctrl must be a contiguous float32 CUDA tensor on the input's device")
-        if nu == 0:
-            shape_ok = True  # the library refuses it: the model has no actuators
-        elif per_step:
-            shape_ok = tuple(ctrl.shape) == (nprob, self.H, nu)
+    @staticmethod
+    def _params_arg(params, nprob):
+        _check_tensor("params", params)
+        if params.numel() < 20 * nprob:
+            raise ValueError("params needs 20 floats per rollout problem")
+        return _ptr(params)
+
+    def _state_args(self, nprob, n, inp, start, final_state, ctrl, ctrl_per_step, geom_pose, geom_pose_per_step):
+        """What ``mpcr_rollout_cost_world`` and ``mpcr_rollout_cost_scenarios``
+        take from ``start`` to the geom-pose strides, validated for ``nprob``
+        rollout problems of ``n`` candidates in all."""
+        dev = inp.device
+        # (a call without state blocks, a plain planner's, does not ask the library for their size)
+        blk = self.state_layout()["size"] if start is not None or final_state is not None else 0
+        if final_state is not None:
+            _check_tensor("final_state", final_state, dev)
+            if final_state.numel() != n * blk or final_state.shape[-1] != blk:
+                raise ValueError(f"final_state must be ({n}, {blk})")
+        start_args = self._block_args("start", start, (blk,), nprob, dev, by_numel=True)[:2]
+        return (*start_args, _ptr(final_state),
+                *self._block_args("ctrl", ctrl, (self.nu,), nprob, dev, ctrl_per_step),
+                *self._block_args("geom_pose", geom_pose, (self.ngeom, 8), nprob, dev, geom_pose_per_step))
+
+    def _block_args(self, name, t, unit, nprob, device, per_step=False, by_numel=False):
+        """(pointer, problem stride, step stride) of a block tensor: one unit
+        for every problem, ``(nprob,) + unit`` with one per problem or, with
+        per_step, ``(nprob, H) + unit`` with one per problem and step.
+        by_numel: any shape of that many elements whose last dimension is the
+        unit's.  None: no block."""
+        if t is None:
+            return None, 0, 0
+        _check_tensor(name, t, device)
+        size = math.prod(unit)
+        shapes = [(nprob, self.H) + unit] if per_step else [unit, (nprob,) + unit]
+        if by_numel:
+            shape_ok = t.numel() in (size, nprob * size) and t.shape[-1] == unit[-1]
         else:
-            shape_ok = tuple(ctrl.shape) in ((nu,), (nprob, nu))
+            shape_ok = tuple(t.shape) in shapes or unit == (0,)  # no actuators: the library refuses the call
         if not shape_ok:
-            raise ValueError(f"ctrl must be ({nu},) or ({nprob}, {nu}), or with ctrl_per_step ({nprob}, {self.H}, {nu}); "
-                             f"got {tuple(ctrl.shape)}")
+            raise ValueError(f"{name} must be " + " or ".join(map(str, shapes))
+                             + (f" (with {name}_per_step)" if per_step else "") + f"; got {tuple(t.shape)}")
         if per_step:
-            return ctypes.c_void_p(ctrl.data_ptr()), self.H * nu, nu
-        return ctypes.c_void_p(ctrl.data_ptr()), nu if ctrl.dim() == 2 and nprob > 1 else 0, 0
+            return _ptr(t), self.H * size, size
+        return _ptr(t), size if nprob > 1 and t.numel() == nprob * size else 0, 0
 
     @property
     def ngeom(self):
@@ -352,25 +372,6 @@ class Engine:
         if self._ngeom is None:
             self._ngeom = int(self.model.geom_poses()[0].shape[0])
         return self._ngeom
-
-    def _geom_pose_args(self, gp, per_step, nprob, device):
-        """(pointer, problem stride, step stride) of a geom-pose tensor: (ng, 8),
-        (nprob, ng, 8) or, per_step, (nprob, H, ng, 8)."""
-        import torch
-        if (not isinstance(gp, torch.Tensor) or not gp.is_cuda or gp.dtype != torch.float32
-                or not gp.is_contiguous() or gp.device != device):
-            raise ValueError("geom_pose must be a contiguous float32 CUDA tensor on the input's device")
-        ng = self.ngeom
-        if per_step:
-            shape_ok = tuple(gp.shape) == (nprob, self.H, ng, 8)
-        else:
-            shape_ok = tuple(gp.shape) in ((ng, 8), (nprob, ng, 8))
-        if not shape_ok:
-            raise ValueError(f"geom_pose must be ({ng}, 8) or ({nprob}, {ng}, 8), or with geom_pose_per_step "
-                             f"({nprob}, {self.H}, {ng}, 8); got {tuple(gp.shape)}")
-        if per_step:
-            return ctypes.c_void_p(gp.data_ptr()), self.H * ng * 8, ng * 8
-        return ctypes.c_void_p(gp.data_ptr()), ng * 8 if gp.dim() == 3 and nprob > 1 else 0, 0
 
     def rollout_cost_dp(self, inp, layout: int, params, cost4, theta=None, thetadot=None, best_key=None,
                         index_base: int = 0, status=None, reset_best: bool = True, stream=None):
@@ -422,10 +423,7 @@ class Engine:
 
     @staticmethod
     def _cost_rows(name, t, rows, device=None):
-        import torch
-        if (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous()
-                or (device is not None and t.device != device)):
-            raise ValueError(f"{name} must be a contiguous float32 CUDA tensor")
+        _check_tensor(name, t, device)
         if t.numel() != rows * 4 or t.shape[-1] != 4:
             raise ValueError(f"{name} must hold {rows} rows of 4; got {tuple(t.shape)}")
 
@@ -444,8 +442,7 @@ class Engine:
         nprob, nscen, worst = int(nprob), int(nscen), int(worst)
         if nprob < 1 or nscen < 1:
             raise ValueError(f"nprob={nprob}, nscen={nscen}: both must be >= 1")
-        if not isinstance(cost4_scen, torch.Tensor):
-            raise ValueError("cost4_scen must be a contiguous float32 CUDA tensor")
+        _check_tensor("cost4_scen", cost4_scen)
         rows = cost4_scen.numel() // 4
         if rows % (nprob * nscen):
             raise ValueError(f"cost4_scen rows ({rows}) must split evenly over nprob={nprob} x nscen={nscen}")
@@ -456,11 +453,9 @@ class Engine:
         self._cost_rows("cost4", cost4, nprob * n_per, cost4_scen.device)
         if best_keys is not None and best_keys.numel() < nprob:
             raise ValueError("best_keys needs nprob elements")
-        ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
-        st = stream if stream is not None else torch.cuda.current_stream(cost4_scen.device).cuda_stream
-        flags = MPCR_F_DEVICE_PTRS | (MPCR_F_RESET_BEST if reset_best else 0)
-        check(_lib.load().mpcr_scenario_reduce(self.handle, ptr(cost4_scen), nprob, nscen, n_per, worst, ptr(cost4),
-                                               ptr(best_keys), int(index_base), flags, ctypes.c_void_p(st)))
+        check(_lib.load().mpcr_scenario_reduce(self.handle, _ptr(cost4_scen), nprob, nscen, n_per, worst, _ptr(cost4),
+                                               _ptr(best_keys), int(index_base),
+                                               *_call_tail(cost4_scen, reset_best, stream)))
         return cost4
 
     def rollout_cost_scenarios(self, inp, layout: int, params, nprob: int, nscen: int, cost4_scen, worst=None,
@@ -480,47 +475,27 @@ class Engine:
         ``best_keys`` (needs ``cost4``) its keys.  Each scenario's slice is
         bitwise the ``rollout_cost_state`` call on that scenario's blocks.
         Returns ``cost4`` (or ``cost4_scen`` without one).  Graph-capturable."""
-        import torch
         nprob, nscen = int(nprob), int(nscen)
         worst = nscen if worst is None else int(worst)
-        for name, t in (("input", inp), ("params", params)):
-            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
-                raise ValueError(f"{name} must be a contiguous float32 CUDA tensor")
+        _check_tensor("input", inp)
         n = int(inp.shape[0])
         if nprob < 1 or nscen < 1 or n % nprob:
             raise ValueError(f"input rows ({n}) must split evenly over nprob={nprob} problems (nscen={nscen} >= 1)")
         n_per, R = n // nprob, nprob * nscen
-        if params.numel() < 20 * R:
-            raise ValueError("params needs 20 floats per problem and scenario")
         self._cost_rows("cost4_scen", cost4_scen, R * n_per, inp.device)
         if cost4 is not None:
             self._cost_rows("cost4", cost4, n, inp.device)
         if best_keys is not None and (cost4 is None or best_keys.numel() < nprob):
             raise ValueError("best_keys needs nprob elements and cost4 (the keys come from the fold)")
-        blk = self.state_layout()["size"]
-        for name, t in (("start", start), ("final_state", final_state)):
-            if t is not None and (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32
-                                  or not t.is_contiguous() or t.device != inp.device):
-                raise ValueError(f"{name} must be a contiguous float32 CUDA tensor on the input's device")
-        stride = 0
-        if start is not None:
-            if start.numel() not in (blk, R * blk) or start.shape[-1] != blk:
-                raise ValueError(f"start must hold one block of {blk} floats, or one per problem and scenario")
-            stride = blk if R > 1 and start.numel() == R * blk else 0
-        if final_state is not None and (final_state.numel() != R * n_per * blk or final_state.shape[-1] != blk):
-            raise ValueError(f"final_state must be ({R * n_per}, {blk})")
         if status is not None and status.numel() < R * n_per:
             raise ValueError(f"status needs {R * n_per} elements")
-        ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
-        cargs = self._ctrl_args(ctrl, ctrl_per_step, R, inp.device) if ctrl is not None else (None, 0, 0)
-        gargs = (self._geom_pose_args(geom_pose, geom_pose_per_step, R, inp.device) if geom_pose is not None
-                 else (None, 0, 0))
-        st = stream if stream is not None else torch.cuda.current_stream(inp.device).cuda_stream
-        flags = MPCR_F_DEVICE_PTRS | (MPCR_F_RESET_BEST if reset_best else 0)
+        # the R rollout problems' blocks, as rollout_cost_state takes its nprob problems'
+        args = self._state_args(R, R * n_per, inp, start, final_state, ctrl, ctrl_per_step, geom_pose,
+                                geom_pose_per_step)
         check(_lib.load().mpcr_rollout_cost_scenarios(
-            self.handle, ptr(inp), layout, nprob, nscen, worst, n_per, ptr(params), ptr(start), stride,
-            ptr(final_state), *cargs, *gargs, ptr(cost4_scen), ptr(cost4), ptr(theta), ptr(thetadot), ptr(best_keys),
-            int(index_base), ptr(status), flags, ctypes.c_void_p(st)))
+            self.handle, _ptr(inp), layout, nprob, nscen, worst, n_per, self._params_arg(params, R), *args,
+            _ptr(cost4_scen), _ptr(cost4), _ptr(theta), _ptr(thetadot), _ptr(best_keys), int(index_base),
+            _ptr(status), *_call_tail(inp, reset_best, stream)))
         return cost4 if cost4 is not None else cost4_scen
 
     def trace(self, inp, layout: int, q0, w, ptgt, qtgt):
@@ -632,14 +607,11 @@ class Plant:
         """The plant's state block into ``tensor`` (float32, CUDA, contiguous,
         at least one block), device to device on the current torch stream
         (``mpcr_plant_copy_state``): a planner's start state."""
-        import torch
         size = Engine.state_layout()["size"]
-        if (not isinstance(tensor, torch.Tensor) or not tensor.is_cuda or tensor.dtype != torch.float32
-                or not tensor.is_contiguous() or tensor.numel() < size or tensor.device.index != self.device):
-            raise ValueError(f"tensor must be a contiguous float32 CUDA tensor of at least {size} elements on the "
-                             f"plant's device (cuda:{self.device})")
-        st = stream if stream is not None else torch.cuda.current_stream(tensor.device).cuda_stream
-        check(_lib.load().mpcr_plant_copy_state(self.handle, ctypes.c_void_p(tensor.data_ptr()), ctypes.c_void_p(st)))
+        _check_tensor("tensor", tensor)
+        if tensor.numel() < size or tensor.device.index != self.device:
+            raise ValueError(f"tensor must hold at least {size} elements on the plant's device (cuda:{self.device})")
+        check(_lib.load().mpcr_plant_copy_state(self.handle, _ptr(tensor), _stream_arg(tensor, stream)))
         return tensor
 
     def forward(self):

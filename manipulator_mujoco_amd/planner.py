@@ -304,15 +304,13 @@ class cem_planner:  # noqa: N801 (reference name)
                                                start=flat(self._state), ctrl=flat(self._ctrl),
                                                geom_pose=flat(self._gpose),
                                                geom_pose_per_step=self.geom_poses == "per_step", **out)
-        elif self.plan_from_state or self.actuator_ctrl or self.geom_poses:
-            # the same launch, reading each problem's start / control / geom-pose block
+        else:
+            # one launch over the problems, reading each one's start / control /
+            # geom-pose block where the planner stages one (None: the model's own)
             self.engine.rollout_cost_state(self._xf.view(B * n, self.nvar), MPCR_LAYOUT_XI, self._par, B,
                                            self._costs[it], start=self._state, ctrl=self._ctrl,
                                            geom_pose=self._gpose, geom_pose_per_step=self.geom_poses == "per_step",
                                            **out)
-        else:
-            self.engine.rollout_cost_multi(self._xf.view(B * n, self.nvar), MPCR_LAYOUT_XI, self._par, B,
-                                           self._costs[it], **out)
 
     def _seg_local_update(self, it):
         """compute_ellite_samples + compute_mean_cov on one rank (:355-360)."""

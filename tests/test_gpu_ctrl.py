@@ -435,6 +435,16 @@ def test_ctrl_calls_validate_their_arguments(torch_cuda):
 
     EINVAL, EMODEL = -1, -2
     assert call(0, 0) == 0 and call(NU, 0) == 0 and call(H * NU, NU) == 0 and call(0, NU) == 0
+    # the raw entry is the Engine's call: a schedule inside the ranges that
+    # differs by problem and step, bit for bit on the costs
+    xi[:] = _xi(torch, n)
+    ctrl[:] = dev(torch, c1()) + 0.01 * torch.arange(2 * H, device="cuda").view(2, H, 1)
+    assert call(H * NU, NU) == 0
+    torch.cuda.synchronize()
+    c_ref = z(n, 4)
+    e.rollout_cost_state(xi, MPCR_LAYOUT_XI, par, 2, c_ref, ctrl=ctrl, ctrl_per_step=True)
+    torch.cuda.synchronize()
+    assert torch.isfinite(c).all() and torch.equal(c.view(torch.int32), c_ref.view(torch.int32))
     for bad in (1, NU - 1, -NU):
         assert call(bad, 0) == EINVAL and b"ctrl_stride" in lib.mpcr_last_error()
     for bad in (1, NU - 1, -NU):

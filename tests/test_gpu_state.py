@@ -460,6 +460,17 @@ def test_state_calls_validate_their_arguments(torch_cuda):
                                            ptr(fin), ptr(c), None, None, None, 0, None, flags, None)
 
     assert call(blk) == 0 and call(0) == 0
+    # the raw entry is the Engine's call: per-problem start blocks (problem 1's
+    # free dofs moving), bit for bit on the costs and the final states
+    xi[:], par[:] = _xi(torch, n), _par_blocks(torch, 2)
+    start[1, e.state_layout()["qvel"] + 6:e.state_layout()["qvel"] + m.nv] = 0.05
+    assert call(blk) == 0
+    torch.cuda.synchronize()
+    c_ref, fin_ref = z(n, 4), z(n, blk)
+    e.rollout_cost_state(xi, MPCR_LAYOUT_XI, par, 2, c_ref, start=start, final_state=fin_ref)
+    torch.cuda.synchronize()
+    assert torch.equal(c.view(torch.int32), c_ref.view(torch.int32))
+    assert torch.equal(fin.view(torch.int32), fin_ref.view(torch.int32))
     for bad in (1, blk - 1, -blk):
         assert call(bad) == -1 and b"start_stride" in lib.mpcr_last_error()
     assert call(blk, flags=0) == -1 and b"device pointers" in lib.mpcr_last_error()  # host-pointer mode: none
