@@ -31,6 +31,7 @@ namespace mpcr {
 struct DevOptions {
   int newton_reuse = 1;             // MPCR_NEWTON_REUSE (0: the kernel's first Newton iteration recomputes)
   int narrow_eager = 0;             // MPCR_NARROW_EAGER (1: contact geometry on every lane, not only the emitting ones)
+  int lane_work = 1;                // MPCR_LANE_WORK (0: the single-arm step's former one-lane / repeated work)
   int m_slab = 0;                   // MPCR_M_SLAB (tests: the HBM-slab path on a model that fits)
   int w2_lead_max = W2_LEAD_MAX;    // MPCR_W2_LEAD_MAX
   uint64_t start_scramble = 0;      // mpcr_set_hull_start_scramble's seed (0: the extreme vertices)
@@ -320,7 +321,7 @@ inline int build_dev_model(const mpcr_model_t& m, const int32_t* lutadr, const D
   d.iterations = m.iterations;
   d.ls_iterations = m.ls_iterations;
   d.disableflags = m.disableflags | (opt.newton_reuse ? 0 : DEV_NO_NEWTON_REUSE) |
-                   (opt.narrow_eager ? DEV_NARROW_EAGER : 0);
+                   (opt.narrow_eager ? DEV_NARROW_EAGER : 0) | (opt.lane_work ? 0 : DEV_NO_LANE_WORK);
   d.timestep = (float)m.timestep;
   d.tolerance = (float)m.tolerance;
   d.ls_tolerance = (float)m.ls_tolerance;

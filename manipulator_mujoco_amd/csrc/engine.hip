@@ -382,6 +382,7 @@ extern "C" int mpcr_engine_create(const mpcr_model* m, int device, int max_n, in
   DevOptions opt;
   opt.newton_reuse = env_int_or("MPCR_NEWTON_REUSE", 1);
   opt.narrow_eager = env_int_or("MPCR_NARROW_EAGER", 0);
+  opt.lane_work = env_int_or("MPCR_LANE_WORK", 1);
   opt.m_slab = env_int_or("MPCR_M_SLAB", 0);
   opt.w2_lead_max = env_int_or("MPCR_W2_LEAD_MAX", W2_LEAD_MAX);
   opt.start_scramble = g_start_scramble.load();

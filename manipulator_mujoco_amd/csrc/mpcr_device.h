@@ -59,6 +59,11 @@ constexpr int DEV_NO_NEWTON_REUSE = 1 << 30;
 // points and normals, not only the lanes that emit a contact (rollout.hip,
 // narrow_lane, single-arm kernels; MPCR_NARROW_EAGER=1, tests)
 constexpr int DEV_NARROW_EAGER = 1 << 29;
+// ... and this one: the single-arm step keeps its former one-lane and repeated
+// work (rollout.hip, "lane work": the pose cost's tail every step, one tree's
+// centre of mass at a time, Newton's first rows recomputed, the line search's
+// own q0 at alpha = 0; MPCR_LANE_WORK=0 in the environment, tests)
+constexpr int DEV_NO_LANE_WORK = 1 << 28;
 
 struct DevModel {
   int nbody, njnt, nq, nv, ngeom, npair, neq, nslot;

@@ -145,6 +145,23 @@ template <class S> constexpr bool kStepKin = !S::WIDE && (MPCR_STEP_TABLE & 1) !
 template <class S> constexpr bool kStepDof = !S::WIDE && (MPCR_STEP_TABLE & 2) != 0;
 template <class S> constexpr bool kStepRow = !S::WIDE && (MPCR_STEP_TABLE & 4) != 0;
 template <class S> constexpr bool kStepLoad = !S::WIDE && (MPCR_STEP_TABLE & 8) != 0;
+// MPCR_LANE_WORK: which one-lane or repeated work of the single-arm step is
+// built in its cheaper form (bit 0 the pose cost's transcendental tail deferred
+// and spread over lanes, 1 the trees' centres of mass in one reduction, 2
+// Newton's first rows from the warm-start choice, 3 the line search's q0 at
+// alpha = 0 from Newton's cost).  Every built form sits behind
+// DEV_NO_LANE_WORK in the device model's flags (the environment's
+// MPCR_LANE_WORK=0 at engine creation, tests -- an on / off switch for all
+// items, not this mask): the former path stays reachable in the same build.
+// 15 is the shipped build; the others attribute a change in results or time
+// (tools/build_variant.py).
+#ifndef MPCR_LANE_WORK
+#define MPCR_LANE_WORK 15
+#endif
+template <class S> constexpr bool kLanePose = !S::WIDE && (MPCR_LANE_WORK & 1) != 0;
+template <class S> constexpr bool kLaneCom = !S::WIDE && (MPCR_LANE_WORK & 2) != 0;
+template <class S> constexpr bool kLaneJar = !S::WIDE && (MPCR_LANE_WORK & 4) != 0;
+template <class S> constexpr bool kLaneQ0 = !S::WIDE && (MPCR_LANE_WORK & 8) != 0;
 // The step table (step_table.h) behind the device model, and quad q (16
 // bytes: one dwordx4 load) of one of its records.  Single-arm kernels only.
 __device__ __forceinline__ const StepTable* step_table(const DevModel* m) {
@@ -3000,6 +3017,16 @@ __global__ void __launch_bounds__(WAVE * (WPCS & 3), WIDE ? kWideWavesPerSimd : 
   const int H = KA->H;
   // horizon segment of this launch (dual-arm one-wave variant only)
   constexpr bool SEG = WIDE && WPC == 1;
+  // lane work by kernel: the one-wave kernels only -- the two-wave kernels
+  // have none of the items (with the pose cost, the centres of mass
+  // and q0 built in them, C2's 1024 x 50 measured +0.5 %, past the parent's
+  // pass range).  Of the one-wave kernels the STATE one takes the centres of
+  // mass and q0 alone: the pose cost's three parked registers cost it two
+  // scalar spills, the warm start's rows twenty spill reloads in the step loop
+  // (tests/test_spill_census.py); the others fit 128 VGPRs with none new.
+  constexpr bool LW_ONE = WPC == 1;
+  constexpr bool LW_POSE = kLanePose<S> && LW_ONE && !STATE, LW_COM = kLaneCom<S> && LW_ONE, LW_Q0 = kLaneQ0<S> && LW_ONE;
+  constexpr bool LW_JAR = kLaneJar<S> && LW_ONE && !STATE;
   const int t_begin = SEG ? KA->t0 : 0, t_end = SEG ? KA->t1 : H;
   const bool resume = SEG && t_begin > 0, suspend = SEG && t_end < H;
   float* const segs = SEG ? KA->seg_state + (size_t)b * SEG_STRIDE : nullptr;
@@ -3225,6 +3252,10 @@ __global__ void __launch_bounds__(WAVE * (WPCS & 3), WIDE ? kWideWavesPerSimd : 
   }
   float vnext = lane < nc ? tdp[lane * H + t_begin] : 0.f;
   float cost_g = 0.f, cost_r = 0.f, cost_c = 0.f;
+  // Lane work, the pose cost: the three scalars of step t wait in lane t & 63
+  // of these until the flush evaluates up to 64 steps' square roots, division
+  // and arc cosine side by side
+  float pk_d2 = 0.f, pk_qq = 0.f, pk_qd = 0.f;
   SlotHist<S> shist;
 #pragma unroll
   for (int j = 0; j < SlotHist<S>::NC; j++)
@@ -3603,7 +3634,35 @@ __global__ void __launch_bounds__(WAVE * (WPCS & 3), WIDE ? kWideWavesPerSimd : 
         s.tenp[t][side][0] = pw[0]; s.tenp[t][side][1] = pw[1]; s.tenp[t][side][2] = pw[2];
       }
     }
+    // Lane work: row tr of the wave (lanes 16 tr + i) sums tree tr, lane i of
+    // the row holding what lane i holds in the loop below -- the in-row steps
+    // see the same operands in the same positions, so lane 15 of the row ends
+    // with wsum_lo<16>'s sum (its -0 restoration done here on the lane), and
+    // the rows' last lanes divide together.
+    bool com_rows = false;
+    if constexpr (LW_COM && NBW == 16)
+      com_rows = !(m->disableflags & DEV_NO_LANE_WORK) && m->ntree <= WAVE / 16;
+    if (com_rows) {
+      const int tr = lane >> 4, i = lane & 15;
+      const bool row = tr < m->ntree;
+      const float mm = (row && i < nb && m->body_tree[i] == tr) ? m->body_mass[i] : 0.f;
+      const bool in = row && i < nb;
+      const float tm = row ? m->tree_mass[tr] : 1.f;  // (ahead of the sums: its wait hides behind them)
+      float c[3];
+#pragma unroll
+      for (int k = 0; k < 3; k++) {
+        c[k] = wsum_row(mm * (in ? s.xipos[i][k] : 0.f));
+        if (__float_as_uint(c[k]) == 0x80000000u) c[k] = 0.f;
+      }
+      if (row && i == 15) {
+        s.com[tr][0] = c[0] / tm; s.com[tr][1] = c[1] / tm; s.com[tr][2] = c[2] / tm;
+      }
+    }
     for (int tr = 0; tr < m->ntree; tr++) {
+      // (the rows above did every tree; a branch in the loop and not an else
+      // around it, so that the kernels without the rows keep the loop's code)
+      if constexpr (LW_COM && NBW == 16)
+        if (com_rows) break;
       float mm = (lane < nb && m->body_tree[lane] == tr) ? m->body_mass[lane] : 0.f;
       float cx = wsum_lo<NBW>(mm * (lane < nb ? s.xipos[lane][0] : 0.f));
       float cy = wsum_lo<NBW>(mm * (lane < nb ? s.xipos[lane][1] : 0.f));
@@ -3616,6 +3675,74 @@ __global__ void __launch_bounds__(WAVE * (WPCS & 3), WIDE ? kWideWavesPerSimd : 
     sync();
 
     // ---- eef outputs (pre-integration) + pose cost -------------------------
+    if constexpr (LW_POSE) {
+      // Lane work: the step keeps what needs its LDS image -- the eef point,
+      // |ep - pt|^2, eq.eq and eq.qt -- and parks the three scalars in the
+      // step's lane; the square roots, the division and the arc cosine run at
+      // the flush for up to 64 steps side by side.  Every lane computes lane 0's
+      // scalars (the reads are broadcasts, the instructions the same), so the
+      // parking needs no trip through the scalar unit.  The model scalars are
+      // read together ahead of the block: one wait instead of three in a row.
+      const int dfl = m->disableflags, tcpb = m->tcp_body, hndb = m->hande_body;
+      const float tp[3] = {m->tcp_pos[0], m->tcp_pos[1], m->tcp_pos[2]};
+      const bool pose_defer = !(dfl & DEV_NO_LANE_WORK);
+      if (lane == 0 || pose_defer) {
+        float ep[3] = {0.f, 0.f, 0.f}, eq[4] = {1.f, 0.f, 0.f, 0.f};
+        if (tcpb >= 0) {
+          float w[3], R[9];
+#pragma unroll
+          for (int k = 0; k < 9; k++) R[k] = s.xmat[tcpb][k];
+          mv(w, R, tp);
+          ep[0] = s.xpos[tcpb][0] + w[0]; ep[1] = s.xpos[tcpb][1] + w[1]; ep[2] = s.xpos[tcpb][2] + w[2];
+        }
+        if (hndb >= 0) {
+          eq[0] = s.xquat[hndb][0]; eq[1] = s.xquat[hndb][1]; eq[2] = s.xquat[hndb][2]; eq[3] = s.xquat[hndb][3];
+        }
+        const float* pt = &s.par[PAR_PT];
+        const float* qt = &s.par[PAR_QT];
+        float dx = ep[0] - pt[0], dy = ep[1] - pt[1], dz = ep[2] - pt[2];
+        if (pose_defer) {
+          // (single-arm kernels: the horizon starts at 0; one opaque use of the
+          // step counter, so the slot grows no induction variable of its own,
+          // which cost a scalar spill)
+          int slot = t;
+          asm volatile("" : "+s"(slot));
+          slot &= WAVE - 1;
+          const float d2 = dx * dx + dy * dy + dz * dz;
+          const float qq = eq[0] * eq[0] + eq[1] * eq[1] + eq[2] * eq[2] + eq[3] * eq[3];
+          const float qd = eq[0] * qt[0] + eq[1] * qt[1] + eq[2] * qt[2] + eq[3] * qt[3];
+          if (lane == slot) { pk_d2 = d2; pk_qq = qq; pk_qd = qd; }
+          // at the last step, and every 64 steps, lanes 0 .. slot run the
+          // parent's expressions on their step's scalars and the costs take the
+          // results in step order: the parent's sums, operand for operand
+          if (slot == WAVE - 1 || t == H - 1) {
+            const float pg = sqrtf(pk_d2);
+            const float qn = sqrtf(pk_qq);
+            const float dq = fabsf(pk_qd / qn);
+            const float pr = 2.f * acosf(clampf(dq, -1.f, 1.f));
+            for (int i = 0; i <= slot; i++) {
+              cost_g += rdlane(pg, i);
+              cost_r += rdlane(pr, i);
+            }
+          }
+        } else {
+          cost_g += sqrtf(dx * dx + dy * dy + dz * dz);
+          float qn = sqrtf(eq[0] * eq[0] + eq[1] * eq[1] + eq[2] * eq[2] + eq[3] * eq[3]);
+          float dq = fabsf((eq[0] * qt[0] + eq[1] * qt[1] + eq[2] * qt[2] + eq[3] * qt[3]) / qn);
+          cost_r += 2.f * acosf(clampf(dq, -1.f, 1.f));
+        }
+        if (lane == 0 && ARGS_HAS(AF_TRACE_EEF, KA->trace_eef)) {
+          float* e = KA->trace_eef + ((size_t)b * H + t) * 7;
+          e[0] = ep[0]; e[1] = ep[1]; e[2] = ep[2]; e[3] = eq[0]; e[4] = eq[1]; e[5] = eq[2]; e[6] = eq[3];
+        }
+        // the last step's pre-integration pose (the step first, the argument read behind it)
+        // (LW_POSE: no STATE kernel here)
+        if (lane == 0 && ARGS_LAST_STEP_FIRST(t, H) && KA->plant != 0 && t == H - 1) {
+          float* e = KA->state + ST_EEF;
+          e[0] = ep[0]; e[1] = ep[1]; e[2] = ep[2]; e[3] = eq[0]; e[4] = eq[1]; e[5] = eq[2]; e[6] = eq[3];
+        }
+      }
+    } else
     if (lane == 0) {
       float ep[3] = {0.f, 0.f, 0.f}, eq[4] = {1.f, 0.f, 0.f, 0.f};
       if (m->tcp_body >= 0) {
@@ -4857,22 +4984,47 @@ __global__ void __launch_bounds__(WAVE * (WPCS & 3), WIDE ? kWideWavesPerSimd : 
       // iteration starts at the one it picks -- the same expressions on the
       // same data.  So the choice keeps M a_w and the chosen side's reduced
       // sums, and iteration 0 takes them instead of an m_dot and two wave sums
-      // (-24 VALU per C3 candidate-step).  The rows' J a - aref are recomputed:
-      // keeping both sides' in efc_jar / efc_jv saved 21 more but any LDS store
-      // in the choice's row loop took the one-wave kernels from 118 to 124
-      // VGPRs ("Measured and not kept").  DEV_NO_NEWTON_REUSE in the
+      // (-24 VALU per C3 candidate-step).  The first 64 rows' J a - aref come
+      // from the choice too where LW_JAR holds (lane work, below; -23 more);
+      // elsewhere they are recomputed.  DEV_NO_NEWTON_REUSE in the
       // device model's flags (MPCR_NEWTON_REUSE=0, tests) recomputes all.
       bool ws_keep = false, ws_won = false;
       float ws_maw = 0.f, ws_gw = 0.f, ws_cost = 0.f;
+      // Lane work (MPCR_LANE_WORK, single-arm kernels; all wave-uniform):
+      // lw, the device model's flags allow it; ws_jar, the first rows' J a - aref
+      // at the warm-start candidate the choice picks, kept in two registers
+      // through the choice (no LDS store in its loop; the one-wave kernels end
+      // at 128 VGPRs) for Newton's first iteration, whose rows 64 and up are
+      // recomputed.
+      bool lw = false;
+      float ws_jar = 0.f;
       if (nefc > 0) {
         // warm start: the better of qacc_warmstart and qacc_smooth
         const int dflags = m->disableflags;
+        if constexpr (!S::WIDE) {
+          lw = !(dflags & DEV_NO_LANE_WORK);
+        }
         if (!(dflags & 4)) {
           if constexpr (!S::WIDE) ws_keep = !(dflags & DEV_NO_NEWTON_REUSE);
           // (the Gauss term of qacc_smooth itself is (M a_s - f_s)'(a_s - a_s) = 0)
           const float maw = lane < nv ? m_dot(lane, s.qws) : 0.f;
           const float gw = lane < nv ? (maw - s.qfs[lane]) * (s.qws[lane] - s.qas[lane]) : 0.f;
           float cw = 0.f, cs = 0.f;
+          float jw0 = 0.f, js0 = 0.f;
+          if constexpr (LW_JAR) {  // the same rows in the same order, the first trip's values kept
+            auto ws_row = [&](int r, float& jw, float& js) {
+              jw = jdot(s, gx, r, s.qws) - s.efc_aref[r];
+              js = jdot(s, gx, r, s.qas) - s.efc_aref[r];
+              const bool eq = (s.efc_src[r] >> 24) == 1;
+              if (eq || jw < 0.f) cw += s.efc_D[r] * jw * jw;
+              if (eq || js < 0.f) cs += s.efc_D[r] * js * js;
+            };
+            if (lane < nefc) ws_row(lane, jw0, js0);
+            for (int r = lane + WAVE; r < nefc; r += WAVE) {
+              float jw, js;
+              ws_row(r, jw, js);
+            }
+          } else
           for (int r = lane; r < nefc; r += WAVE) {
             const float jw = jdot(s, gx, r, s.qws) - s.efc_aref[r];
             const float js = jdot(s, gx, r, s.qas) - s.efc_aref[r];
@@ -4902,6 +5054,7 @@ __global__ void __launch_bounds__(WAVE * (WPCS & 3), WIDE ? kWideWavesPerSimd : 
           const float costw = 0.5f * gws + 0.5f * cw;
           const float costs = 0.5f * cs;
           if (costw < costs && lane < NVW) qacc_l = s.qws[lane];
+          if constexpr (LW_JAR) ws_jar = costw < costs ? jw0 : js0;
           if constexpr (!S::WIDE) {
             ws_won = costw < costs;
             ws_maw = maw;
@@ -4936,6 +5089,22 @@ __global__ void __launch_bounds__(WAVE * (WPCS & 3), WIDE ? kWideWavesPerSimd : 
           if (reuse && ws_won) ma = ws_maw;
           else ma = lane < nv ? m_dot(lane, s.qacc) : 0.f;
           float cc = 0.f;
+          if constexpr (LW_JAR) {
+            auto it_row = [&](int r, float jar) {
+              const bool act = ((s.efc_src[r] >> 24) == 1) || jar < 0.f;
+              const float D = s.efc_D[r];
+              s.efc_jar[r] = jar;
+              s.efc_f[r] = act ? -D * jar : 0.f;
+              s.efc_Da[r] = act ? D : 0.f;
+              cc += act ? D * jar * jar : 0.f;
+            };
+            int r = lane;
+            if (reuse && lw) {  // the first iteration: rows 0-63 from the warm-start choice
+              if (r < nefc) it_row(r, ws_jar);
+              r += WAVE;
+            }
+            for (; r < nefc; r += WAVE) it_row(r, jdot(s, gx, r, s.qacc) - s.efc_aref[r]);
+          } else
           for (int r = lane; r < nefc; r += WAVE) {
             const float jar = jdot(s, gx, r, s.qacc) - s.efc_aref[r];
             bool act = ((s.efc_src[r] >> 24) == 1) || jar < 0.f;
@@ -5086,7 +5255,20 @@ __global__ void __launch_bounds__(WAVE * (WPCS & 3), WIDE ? kWideWavesPerSimd : 
           sync();
           using LT = LsReal<S>;
           using LsPt = LsPtT<LT>;
-          LsPt p0 = ls_eval(s, lane, qg, (LT)0);
+          // alpha = 0: the rows' active set is the iteration's (jar < 0) and
+          // 0.5 sum D jar^2 + 0.5 gauss is the cost above: halving is exact unless
+          // a row term D jar^2 is subnormal (fp32 denormals are on), where the
+          // two may round apart in the last subnormal bit -- not met in any batch
+          // run, and the on / off tests compare bit for bit.  So with lane work
+          // p0 takes it and sums q1, q2 alone
+          LsPt p0;
+          if (LW_Q0 && lw) {
+            p0 = ls_eval<S, false>(s, lane, qg, (LT)0);
+            p0.cost = cost;
+            p0.full = true;
+          } else {
+            p0 = ls_eval(s, lane, qg, (LT)0);
+          }
           const bool ell_ls = S::WIDE && m->cone == 1;
           if (ell_ls) {
             const LT al[3] = {0, 0, 0};
