@@ -313,6 +313,34 @@ int mpcr_rollout_cost_world(mpcr_engine* e, const float* input, int layout, int 
                             int geom_stride, int geom_step_stride, float* cost4, float* theta, float* thetadot,
                             uint64_t* best_keys, int index_base, int* status, int flags, void* stream);
 
+/* mpcr_rollout_cost_world with the pose the end effector is priced against
+   as an input of the call (a backward-compatible addition;
+   mpcr_rollout_cost_world is this call with target = NULL).  target
+   (nullable): device memory, 16-byte aligned, rows of 8 floats, x y z 0 |
+   qw qx qy qz: floats 12..19 of a parameter block (ptgt | qtgt).  Float 3 is
+   reserved and never read; the quaternion may have any norm and is
+   normalised by the kernel exactly as the parameter block's is.  Step t of
+   problem p reads the row at target + p target_stride + t target_step_stride
+   (strides in floats, multiples of 4): target_stride = 0 is one schedule for
+   every problem, target_step_stride = 0 one row for the whole horizon; a
+   non-zero step stride is at least 8, and a non-zero target_stride holds what
+   a problem reads (target_step_stride (H - 1) + 8).  With a schedule the
+   parameter block's own ptgt / qtgt are not used; its init_pos and weights
+   are.  Only the cost's goal and rotation terms, the total and the best key
+   depend on it: cost4's collision column, theta, thetadot, final_state and
+   status are bitwise the call without one.  Read when the kernel runs
+   (graph-capturable; a replay sees new contents), never written.  Per
+   problem, not per candidate.  A schedule repeating the parameter block's
+   target is bitwise the call without one.  target = NULL keeps the parameter
+   block's target.  MPCR_EINVAL: host memory, a misaligned pointer or stride,
+   a stride out of range. */
+int mpcr_rollout_cost_target(mpcr_engine* e, const float* input, int layout, int nprob, int n_per,
+                             const float* params, const float* start, int start_stride, float* final_state,
+                             const float* ctrl, int ctrl_stride, int ctrl_step_stride, const float* geom_pose,
+                             int geom_stride, int geom_step_stride, const float* target, int target_stride,
+                             int target_step_stride, float* cost4, float* theta, float* thetadot,
+                             uint64_t* best_keys, int index_base, int* status, int flags, void* stream);
+
 /* Fold the costs of candidates that were rolled out in several scenarios
    (world hypotheses) into one row each.  cost4_scen holds nprob nscen n_per
    rows of 4 (a rollout's cost4: total | goal | rotation | collision):
@@ -359,6 +387,22 @@ int mpcr_rollout_cost_scenarios(mpcr_engine* e, const float* input, int layout, 
                                 const float* geom_pose, int geom_stride, int geom_step_stride, float* cost4_scen,
                                 float* cost4, float* theta, float* thetadot, uint64_t* best_keys, int index_base,
                                 int* status, int flags, void* stream);
+
+/* mpcr_rollout_cost_scenarios with a target schedule (a backward-compatible
+   addition; mpcr_rollout_cost_scenarios is this call with target = NULL):
+   target, target_stride and target_step_stride as in
+   mpcr_rollout_cost_target, the strides per rollout problem r = p nscen + s,
+   so each scenario may carry its own hypothesis of where the target goes.
+   Each scenario's slice is bitwise what mpcr_rollout_cost_target computes
+   for that scenario's blocks alone. */
+int mpcr_rollout_cost_scenarios_target(mpcr_engine* e, const float* input, int layout, int nprob, int nscen,
+                                       int worst, int n_per, const float* params, const float* start,
+                                       int start_stride, float* final_state, const float* ctrl, int ctrl_stride,
+                                       int ctrl_step_stride, const float* geom_pose, int geom_stride,
+                                       int geom_step_stride, const float* target, int target_stride,
+                                       int target_step_stride, float* cost4_scen, float* cost4, float* theta,
+                                       float* thetadot, uint64_t* best_keys, int index_base, int* status, int flags,
+                                       void* stream);
 
 /* Closed-loop plant: one environment of the model, stepped by the rollout
    kernel (fp32 state resident on the device).  Created at the template

@@ -89,6 +89,11 @@ _ARGTYPES = {
     "mpcr_rollout_cost_scenarios": [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp,
                                     _vp, _vp, _vp, _vp, _i, _vp, _i, _vp],
     "mpcr_scenario_reduce": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp],
+    # target poses as a call input
+    "mpcr_rollout_cost_target": [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _i, _i, _vp,
+                                 _vp, _vp, _vp, _i, _vp, _i, _vp],
+    "mpcr_rollout_cost_scenarios_target": [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _i,
+                                           _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp],
 }
 # every symbol include/mpcr.h declares (tests check the exports)
 EXPORTS = tuple(_ARGTYPES)

@@ -512,6 +512,7 @@ struct Launch {
   // the scenarios per planning problem that share its input rows (0: none; scen_count)
   StateArgs sa = {};
   int nscen = 0;
+  TargetArgs ta = {};  // the call's target schedule (rollout.h; null: the parameter block's target)
 };
 
 // the kernel's arguments for launch l of engine e (the one place they are filled)
@@ -555,8 +556,9 @@ static int rollout_args(const mpcr_engine* e, const Launch& l, RolloutArgs& a) {
   if (l.dpar) {
     set_state_args(a, l.sa);
     set_scen_count(a, l.nscen);
+    set_target_args(a, l.ta);
   } else {
-    if (l.sa.start || l.sa.final_state || l.sa.ctrl || l.sa.geom_pose || l.nscen)
+    if (l.sa.start || l.sa.final_state || l.sa.ctrl || l.sa.geom_pose || l.nscen || l.ta.target)
       return fail(MPCR_EINVAL, "state, control and geom-pose blocks need a device parameter block");
     std::memcpy(a.par, l.par, sizeof(a.par));
   }
@@ -702,7 +704,8 @@ static bool device_memory(const void* p, int d) {
 // A call's block per problem and, optionally, per step (StateArgs): `name` at
 // p, addressed by `stem`_stride and `stem`_step_stride in floats, one unit of
 // `unit` floats (named `unit_name`) per step.  align: bytes its rows are
-// aligned to (0: no demand).  ctrl: nu floats; geom_pose: 8 ngeom, 16 bytes.
+// aligned to (0: no demand).  ctrl: nu floats; geom_pose: 8 ngeom, 16 bytes;
+// target: a row of 8, 16 bytes.
 static int check_block(const mpcr_engine* e, const char* name, const char* stem, const float* p, int stride,
                        int step_stride, const char* unit_name, int unit, int align) {
   if (align && ((reinterpret_cast<uintptr_t>(p) & (align - 1)) || (stride & (align / 4 - 1)) ||
@@ -750,6 +753,17 @@ static int rollout_call(mpcr_engine* e, Launch& l, int flags, void* stream) {
   if (!s.start) s.start_stride = 0;
   if (!s.ctrl) s.ctrl_stride = s.ctrl_step_stride = 0;
   if (!s.geom_pose) s.geom_stride = s.geom_step_stride = 0;
+  TargetArgs& tg = l.ta;
+  if (tg.target) {
+    if (int rc = check_block(e, "target", "target", tg.target, tg.stride, tg.step_stride, "a target row", 8, 16))
+      return rc;
+    // the kernel parks a problem's offset as a count of 4-float quads in 32 bits
+    if ((((long long)(l.nprob - 1) * tg.stride) >> 2) > 0xffffffffll)
+      return fail(MPCR_EINVAL, "target_stride=%d x nprob=%d: a problem's offset exceeds 2^34 floats", tg.stride,
+                  l.nprob);
+  } else {
+    tg.stride = tg.step_stride = 0;
+  }
   if (int rc = check_layout(l.layout)) return rc;
   if (!l.in || !l.dpar || !l.cost4) return fail(MPCR_EINVAL, "null argument");
   HIPCHK(hipSetDevice(e->device));
@@ -787,12 +801,13 @@ extern "C" int mpcr_rollout_cost_multi(mpcr_engine* e, const float* input, int l
   return rollout_call(e, l, flags, stream);
 }
 
-extern "C" int mpcr_rollout_cost_world(mpcr_engine* e, const float* input, int layout, int nprob, int n_per,
-                                       const float* params, const float* start, int start_stride, float* final_state,
-                                       const float* ctrl, int ctrl_stride, int ctrl_step_stride,
-                                       const float* geom_pose, int geom_stride, int geom_step_stride, float* cost4,
-                                       float* theta, float* thetadot, uint64_t* best_keys, int index_base, int* status,
-                                       int flags, void* stream) {
+extern "C" int mpcr_rollout_cost_target(mpcr_engine* e, const float* input, int layout, int nprob, int n_per,
+                                        const float* params, const float* start, int start_stride, float* final_state,
+                                        const float* ctrl, int ctrl_stride, int ctrl_step_stride,
+                                        const float* geom_pose, int geom_stride, int geom_step_stride,
+                                        const float* target, int target_stride, int target_step_stride, float* cost4,
+                                        float* theta, float* thetadot, uint64_t* best_keys, int index_base,
+                                        int* status, int flags, void* stream) {
   if (!e) return fail(MPCR_EINVAL, "null argument");
   if (!(flags & MPCR_F_DEVICE_PTRS)) return fail(MPCR_EINVAL, "mpcr_rollout_cost_state takes device pointers");
   if (int rc = check_multi(nprob, n_per, e->max_n)) return rc;
@@ -803,7 +818,19 @@ extern "C" int mpcr_rollout_cost_world(mpcr_engine* e, const float* input, int l
   l.sa.start = start; l.sa.start_stride = start_stride; l.sa.final_state = final_state;
   l.sa.ctrl = ctrl; l.sa.ctrl_stride = ctrl_stride; l.sa.ctrl_step_stride = ctrl_step_stride;
   l.sa.geom_pose = geom_pose; l.sa.geom_stride = geom_stride; l.sa.geom_step_stride = geom_step_stride;
+  l.ta.target = target; l.ta.stride = target_stride; l.ta.step_stride = target_step_stride;
   return rollout_call(e, l, flags, stream);
+}
+
+extern "C" int mpcr_rollout_cost_world(mpcr_engine* e, const float* input, int layout, int nprob, int n_per,
+                                       const float* params, const float* start, int start_stride, float* final_state,
+                                       const float* ctrl, int ctrl_stride, int ctrl_step_stride,
+                                       const float* geom_pose, int geom_stride, int geom_step_stride, float* cost4,
+                                       float* theta, float* thetadot, uint64_t* best_keys, int index_base, int* status,
+                                       int flags, void* stream) {
+  return mpcr_rollout_cost_target(e, input, layout, nprob, n_per, params, start, start_stride, final_state, ctrl,
+                                  ctrl_stride, ctrl_step_stride, geom_pose, geom_stride, geom_step_stride, nullptr, 0,
+                                  0, cost4, theta, thetadot, best_keys, index_base, status, flags, stream);
 }
 
 // the shape mpcr_scenario_reduce and mpcr_rollout_cost_scenarios accept
@@ -845,13 +872,14 @@ extern "C" int mpcr_scenario_reduce(mpcr_engine* e, const float* cost4_scen, int
   return MPCR_OK;
 }
 
-extern "C" int mpcr_rollout_cost_scenarios(mpcr_engine* e, const float* input, int layout, int nprob, int nscen,
-                                           int worst, int n_per, const float* params, const float* start,
-                                           int start_stride, float* final_state, const float* ctrl, int ctrl_stride,
-                                           int ctrl_step_stride, const float* geom_pose, int geom_stride,
-                                           int geom_step_stride, float* cost4_scen, float* cost4, float* theta,
-                                           float* thetadot, uint64_t* best_keys, int index_base, int* status,
-                                           int flags, void* stream) {
+extern "C" int mpcr_rollout_cost_scenarios_target(mpcr_engine* e, const float* input, int layout, int nprob, int nscen,
+                                                  int worst, int n_per, const float* params, const float* start,
+                                                  int start_stride, float* final_state, const float* ctrl,
+                                                  int ctrl_stride, int ctrl_step_stride, const float* geom_pose,
+                                                  int geom_stride, int geom_step_stride, const float* target,
+                                                  int target_stride, int target_step_stride, float* cost4_scen,
+                                                  float* cost4, float* theta, float* thetadot, uint64_t* best_keys,
+                                                  int index_base, int* status, int flags, void* stream) {
   if (!e) return fail(MPCR_EINVAL, "null argument");
   if (!(flags & MPCR_F_DEVICE_PTRS)) return fail(MPCR_EINVAL, "mpcr_rollout_cost_scenarios takes device pointers");
   if (int rc = check_scenarios(nprob, nscen, n_per, worst, e->max_n)) return rc;
@@ -869,12 +897,26 @@ extern "C" int mpcr_rollout_cost_scenarios(mpcr_engine* e, const float* input, i
   l.sa.start = start; l.sa.start_stride = start_stride; l.sa.final_state = final_state;
   l.sa.ctrl = ctrl; l.sa.ctrl_stride = ctrl_stride; l.sa.ctrl_step_stride = ctrl_step_stride;
   l.sa.geom_pose = geom_pose; l.sa.geom_stride = geom_stride; l.sa.geom_step_stride = geom_step_stride;
+  l.ta.target = target; l.ta.stride = target_stride; l.ta.step_stride = target_step_stride;
   if (int rc = rollout_call(e, l, flags & ~(MPCR_F_SYNC | MPCR_F_RESET_BEST), stream)) return rc;
   if (cost4)
     return mpcr_scenario_reduce(e, cost4_scen, nprob, nscen, n_per, worst, cost4, best_keys, index_base, flags,
                                 stream);
   if (flags & MPCR_F_SYNC) HIPCHK(hipStreamSynchronize((hipStream_t)stream));
   return MPCR_OK;
+}
+
+extern "C" int mpcr_rollout_cost_scenarios(mpcr_engine* e, const float* input, int layout, int nprob, int nscen,
+                                           int worst, int n_per, const float* params, const float* start,
+                                           int start_stride, float* final_state, const float* ctrl, int ctrl_stride,
+                                           int ctrl_step_stride, const float* geom_pose, int geom_stride,
+                                           int geom_step_stride, float* cost4_scen, float* cost4, float* theta,
+                                           float* thetadot, uint64_t* best_keys, int index_base, int* status,
+                                           int flags, void* stream) {
+  return mpcr_rollout_cost_scenarios_target(e, input, layout, nprob, nscen, worst, n_per, params, start, start_stride,
+                                            final_state, ctrl, ctrl_stride, ctrl_step_stride, geom_pose, geom_stride,
+                                            geom_step_stride, nullptr, 0, 0, cost4_scen, cost4, theta, thetadot,
+                                            best_keys, index_base, status, flags, stream);
 }
 
 extern "C" int mpcr_rollout_cost_ctrl(mpcr_engine* e, const float* input, int layout, int nprob, int n_per,

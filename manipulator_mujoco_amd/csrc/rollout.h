@@ -168,13 +168,47 @@ __host__ __device__ inline int scen_count(const RolloutArgs& a) {
 inline void set_scen_count(RolloutArgs& a, int n) {
   __builtin_memcpy(reinterpret_cast<char*>(a.par) + kScenOff, &n, sizeof(n));
 }
-// whether a launch starts from, or returns, state blocks, reads a control or
-// geom-pose block, or shares its input rows among scenarios (whose kernels
-// are STATE ones, block pointers or not)
+// Target schedule (mpcr_rollout_cost_target): the pose the cost's two terms
+// read as an input of the call, for the same calls, in par's bytes behind the
+// scenario count (64..80; StateArgs and the count stay where they are).  A
+// target row is 8 floats, x y z 0 | qw qx qy qz -- floats PAR_PT.. of a
+// parameter block -- 16-byte aligned; float 3 is never read, the quaternion
+// may have any norm (normalised by target_quat_unit, like the parameter
+// block's).  Addressed like ctrl: step t (absolute) of problem p reads the row
+// at target + p stride + t step_stride (floats, multiples of 4; 0: one
+// schedule for every problem / one row for the whole horizon).  Null keeps the
+// parameter block's ptgt / qtgt; with a schedule they are not used.  Per
+// problem, so group_args leaves it alone.  Read by the STATE instantiations.
+struct TargetArgs {
+  const float* target;
+  int stride, step_stride;
+};
+constexpr size_t kTargetOff = 64;
+static_assert(sizeof(StateArgs) == 56 && offsetof(StateArgs, geom_step_stride) == 52, "StateArgs keeps its layout");
+static_assert(kScenOff + sizeof(int) <= kTargetOff && kTargetOff % 8 == 0 && sizeof(TargetArgs) == 16 &&
+                  kTargetOff + sizeof(TargetArgs) <= sizeof(float) * PAR_N,
+              "the target schedule behind the scenario count, inside par");
+__host__ __device__ inline TargetArgs target_args(const RolloutArgs& a) {
+  TargetArgs t;
+  __builtin_memcpy(&t, reinterpret_cast<const char*>(a.par) + kTargetOff, sizeof(t));
+  return t;
+}
+inline void set_target_args(RolloutArgs& a, const TargetArgs& t) {
+  __builtin_memcpy(reinterpret_cast<char*>(a.par) + kTargetOff, &t, sizeof(t));
+}
+// the unit quaternion of a target's (parameter block or schedule row): the one
+// expression both go through
+__host__ __device__ inline void target_quat_unit(const float q[4], float out[4]) {
+  const float qn = sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+  out[0] = q[0] / qn; out[1] = q[1] / qn; out[2] = q[2] / qn; out[3] = q[3] / qn;
+}
+// whether a launch starts from, or returns, state blocks, reads a control,
+// geom-pose or target block, or shares its input rows among scenarios (whose
+// kernels are STATE ones, block pointers or not)
 inline bool has_state(const RolloutArgs& a) {
   if (!a.dpar) return false;
   const StateArgs s = state_args(a);
-  return s.start || s.final_state || s.ctrl || s.geom_pose || scen_count(a) > 1;
+  return s.start || s.final_state || s.ctrl || s.geom_pose || scen_count(a) > 1 || target_args(a).target;
 }
 // the scenarios of a launch (0: none)
 inline int scenarios(const RolloutArgs& a) {
@@ -258,7 +292,9 @@ struct __align__(16) SmemT {
   };
   alignas(16) float gxpos[NGW][4];   // gxpos+gxmat (dead during Newton) double as the
   float gxmat[NGW][12];  // Hessian solve's LDS scratch (NGW*16 >= NVW*LD)
-  float cprev_pad_;       // unused (the previous slot distances live in HBM, RolloutArgs::slot_prev); keeps the layout
+  // keeps the layout (the previous slot distances live in HBM, RolloutArgs::slot_prev); the STATE kernels park
+  // the problem's target-schedule offset here, as bits (TargetArgs)
+  float cprev_pad_;
   float par[PAR_N];       // q0 | w | ptgt | qtgt (normalised)
   float eqp[NEQP][2][4];  // connect anchors in world (body1, body2)
   float tenp[WIDE ? DX_NTEN : 1][2][4];  // spatial-tendon sites in world

@@ -2524,6 +2524,20 @@ __device__ __forceinline__ int kscen() {
 }
 #define KSCEN kscen()
 #endif
+// The target schedule behind the scenario count (rollout.h, kTargetOff;
+// KTA->field): both units read it where they use it, once a step, from the
+// kernarg segment through a laundered pointer -- the dual-arm kernels too,
+// whose by-value copy of it held four more scalars across the horizon loop (a
+// fifth spilled VGPR and 32 bytes of scratch in the one-wave kernel)
+static_assert((offsetof(RolloutArgs, par) + kTargetOff) % 8 == 0, "TargetArgs' pointer aligned inside the kernarg segment");
+typedef const __attribute__((address_space(4))) TargetArgs* KernargTarget;
+__device__ __forceinline__ KernargTarget ktarg() {
+  const __attribute__((address_space(4))) char* p =
+      (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(p));
+  return (KernargTarget)(p + offsetof(RolloutArgs, par) + kTargetOff);
+}
+#define KTA ktarg()
 
 template <class S>
 __device__ __forceinline__ void emit_contacts(const DevModel* __restrict__ m, S& s, const RolloutArgs& args,
@@ -3167,8 +3181,13 @@ __global__ void __launch_bounds__(WAVE * (WPCS & 3), WIDE ? kWideWavesPerSimd : 
     const int pr = KA->prob_n ? (KA->prob_off + b) / KA->prob_n : 0;
     const float* dp = KA->dpar + (size_t)pr * PAR_N;
     if (lane < PAR_N) s.par[lane] = dp[lane];
-    if constexpr (STATE)
+    if constexpr (STATE) {
       if (KSA->start) st_in = KSA->start + (size_t)pr * KSA->start_stride;
+      // the problem's target schedule (TargetArgs), its offset in rows' quads
+      // (strides are multiples of 4 floats; the host bounds it, rollout_call),
+      // parked in the image's spare word: no scalar lives across the step for it
+      if (lane == 0) s.cprev_pad_ = __uint_as_float((unsigned)(((size_t)pr * (unsigned)KTA->stride) >> 2));
+    }
   } else {
     if (lane < PAR_N) s.par[lane] = KA->dpar ? KA->dpar[lane] : KA->par[lane];
   }
@@ -3203,12 +3222,7 @@ __global__ void __launch_bounds__(WAVE * (WPCS & 3), WIDE ? kWideWavesPerSimd : 
   }
   }
   sync();
-  if (lane == 0) {  // normalise the target quaternion once
-    const float* q = &s.par[PAR_QT];
-    const float qn = sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    s.par[PAR_QT] = q[0] / qn; s.par[PAR_QT + 1] = q[1] / qn; s.par[PAR_QT + 2] = q[2] / qn;
-    s.par[PAR_QT + 3] = q[3] / qn;
-  }
+  if (lane == 0) target_quat_unit(&s.par[PAR_QT], &s.par[PAR_QT]);  // normalise the target quaternion once
   if (lane < nc && !from_state && !resume) s.qpos[m->ctrl_qposadr[lane]] = s.par[PAR_Q0 + lane];
   sync();
   }
@@ -3437,6 +3451,24 @@ __global__ void __launch_bounds__(WAVE * (WPCS & 3), WIDE ? kWideWavesPerSimd : 
         gp_row = true;
       }
     }
+    // the call's target row of this step (STATE, TargetArgs): lane 0 loads
+    // the row at the problem's parked offset (init) and refreshes the image's
+    // ptgt | qtgt ahead of the pose cost, which stays as it is.  Both units
+    // issue the load here, ahead of the kinematics: eight registers on one
+    // lane's behalf, which the dual-arm kernels carry too (measured: loading
+    // at the refresh cost their two-wave kernel 0.5 - 0.7 % at 1024 x 50)
+    [[maybe_unused]] auto target_load = [&](float4& p, float4& q) -> bool {
+      const float* tg = KTA->target;
+      if (!tg || lane != 0) return false;
+      const float4* row = reinterpret_cast<const float4*>(tg) + __float_as_uint(s.cprev_pad_) +
+                          (((size_t)t * (unsigned)KTA->step_stride) >> 2);
+      p = row[0];
+      q = row[1];
+      return true;
+    };
+    [[maybe_unused]] float4 tgp = {0.f, 0.f, 0.f, 0.f}, tgq = {1.f, 0.f, 0.f, 0.f};
+    [[maybe_unused]] bool tg_row = false;
+    if constexpr (STATE) tg_row = target_load(tgp, tgq);
     // ---- kinematics: local pose per body, then pointer jumping ----------------
     {
       float q[4] = {1.f, 0.f, 0.f, 0.f}, p[3] = {0.f, 0.f, 0.f};
@@ -3670,6 +3702,14 @@ __global__ void __launch_bounds__(WAVE * (WPCS & 3), WIDE ? kWideWavesPerSimd : 
       if (lane == 0) {
         float tm = m->tree_mass[tr];
         s.com[tr][0] = cx / tm; s.com[tr][1] = cy / tm; s.com[tr][2] = cz / tm;
+      }
+    }
+    if constexpr (STATE) {
+      // this step's target into the image (the sync below orders it ahead of the pose cost)
+      if (tg_row) {
+        s.par[PAR_PT] = tgp.x; s.par[PAR_PT + 1] = tgp.y; s.par[PAR_PT + 2] = tgp.z;
+        const float q[4] = {tgq.x, tgq.y, tgq.z, tgq.w};
+        target_quat_unit(q, &s.par[PAR_QT]);
       }
     }
     sync();

@@ -285,6 +285,21 @@ class Engine:
         return p
 
     @staticmethod
+    def target_rows(pos, rot):
+        """Target rows (``mpcr_rollout_cost_target``), float32 ``(..., 8)``: x y
+        z 0 | qw qx qy qz from ``pos`` ``(..., 3)`` and ``rot`` ``(..., 4)``,
+        broadcast against each other.  Only the layout: the kernel normalises
+        the quaternion."""
+        pos, rot = np.asarray(pos, dtype=np.float32), np.asarray(rot, dtype=np.float32)
+        if pos.shape[-1:] != (3,) or rot.shape[-1:] != (4,):
+            raise ValueError(f"target_rows takes (..., 3) and (..., 4); got {pos.shape} and {rot.shape}")
+        lead = np.broadcast_shapes(pos.shape[:-1], rot.shape[:-1])
+        rows = np.zeros(lead + (8,), dtype=np.float32)
+        rows[..., :3] = pos
+        rows[..., 4:] = rot
+        return rows
+
+    @staticmethod
     def state_layout():
         """``mpcr_state_layout``: the offsets of a state block's parts and its
         size in floats (no GPU needed)."""
@@ -298,11 +313,12 @@ class Engine:
 
     def _rollout_dp(self, nprob, inp, layout, params, cost4, theta, thetadot, best_keys, index_base, status,
                     reset_best, stream, state=None, ctrl=None, ctrl_per_step=False, geom_pose=None,
-                    geom_pose_per_step=False):
+                    geom_pose_per_step=False, target=None, target_per_step=False):
         """nprob None: ``rollout_cost_dp`` (its own C entry, which takes an
         empty batch); else ``rollout_cost_multi`` or, with state = (start,
         final_state), ``rollout_cost_state`` (``mpcr_rollout_cost_world``,
-        whichever of its blocks are set)."""
+        whichever of its blocks are set; with a target schedule
+        ``mpcr_rollout_cost_target``)."""
         _check_tensor("input", inp)
         _check_tensor("cost4", cost4)
         n, lib = int(inp.shape[0]), _lib.load()
@@ -317,6 +333,9 @@ class Engine:
         if state is not None:
             fn = lib.mpcr_rollout_cost_world
             args += self._state_args(nprob, n, inp, *state, ctrl, ctrl_per_step, geom_pose, geom_pose_per_step)
+            if target is not None:
+                fn = lib.mpcr_rollout_cost_target
+                args += self._block_args("target", target, (8,), nprob, inp.device, target_per_step)
         check(fn(self.handle, _ptr(inp), layout, *shape, *args, _ptr(cost4), _ptr(theta), _ptr(thetadot),
                  _ptr(best_keys), int(index_base), _ptr(status), *_call_tail(inp, reset_best, stream)))
         return cost4
@@ -395,7 +414,8 @@ class Engine:
     def rollout_cost_state(self, inp, layout: int, params, nprob: int, cost4, start=None, final_state=None,
                            theta=None, thetadot=None, best_keys=None, index_base: int = 0, status=None,
                            reset_best: bool = True, stream=None, ctrl=None, ctrl_per_step: bool = False,
-                           geom_pose=None, geom_pose_per_step: bool = False):
+                           geom_pose=None, geom_pose_per_step: bool = False, target=None,
+                           target_per_step: bool = False):
         """``rollout_cost_multi`` from a given full state and / or returning
         the final states (``mpcr_rollout_cost_state``).  ``start``: a device
         tensor of one state block (``pack_state``, ``Plant.copy_state``) shared
@@ -415,11 +435,19 @@ class Engine:
         (``Model.geom_poses``, ``Model.pose_rows``), (ng, 8) for every problem
         or (nprob, ng, 8) with one block per problem, or with
         ``geom_pose_per_step`` (nprob, H, ng, 8), one block per step; used as
-        it is and read when the kernel runs.  None keeps the model's poses."""
+        it is and read when the kernel runs.  None keeps the model's poses.
+        ``target`` (``mpcr_rollout_cost_target``): the pose the cost's goal and
+        rotation terms read, as a device tensor of target rows
+        (``Engine.target_rows``), (8,) for every problem or (nprob, 8) with one
+        per problem, or with ``target_per_step`` (nprob, H, 8), one row per
+        step; the quaternion may have any norm.  It replaces the parameter
+        block's ptgt / qtgt and is read when the kernel runs.  None keeps the
+        parameter block's target."""
         return self._rollout_dp(int(nprob), inp, layout, params, cost4, theta, thetadot, best_keys, index_base,
                                 status, reset_best, stream, state=(start, final_state), ctrl=ctrl,
                                 ctrl_per_step=ctrl_per_step, geom_pose=geom_pose,
-                                geom_pose_per_step=geom_pose_per_step)
+                                geom_pose_per_step=geom_pose_per_step, target=target,
+                                target_per_step=target_per_step)
 
     @staticmethod
     def _cost_rows(name, t, rows, device=None):
@@ -461,7 +489,8 @@ class Engine:
     def rollout_cost_scenarios(self, inp, layout: int, params, nprob: int, nscen: int, cost4_scen, worst=None,
                                cost4=None, start=None, final_state=None, theta=None, thetadot=None, best_keys=None,
                                index_base: int = 0, status=None, reset_best: bool = True, stream=None, ctrl=None,
-                               ctrl_per_step: bool = False, geom_pose=None, geom_pose_per_step: bool = False):
+                               ctrl_per_step: bool = False, geom_pose=None, geom_pose_per_step: bool = False,
+                               target=None, target_per_step: bool = False):
         """One set of candidates priced in ``nscen`` scenarios per problem
         (``mpcr_rollout_cost_scenarios``).  ``inp`` holds nprob * n_per rows;
         rollout problem r = p nscen + s is scenario s of problem p and is
@@ -474,6 +503,8 @@ class Engine:
         ``scenario_reduce`` with ``worst`` (default nscen: the mean), and
         ``best_keys`` (needs ``cost4``) its keys.  Each scenario's slice is
         bitwise the ``rollout_cost_state`` call on that scenario's blocks.
+        ``target`` / ``target_per_step`` as there, per rollout problem
+        (``mpcr_rollout_cost_scenarios_target``).
         Returns ``cost4`` (or ``cost4_scen`` without one).  Graph-capturable."""
         nprob, nscen = int(nprob), int(nscen)
         worst = nscen if worst is None else int(worst)
@@ -492,7 +523,11 @@ class Engine:
         # the R rollout problems' blocks, as rollout_cost_state takes its nprob problems'
         args = self._state_args(R, R * n_per, inp, start, final_state, ctrl, ctrl_per_step, geom_pose,
                                 geom_pose_per_step)
-        check(_lib.load().mpcr_rollout_cost_scenarios(
+        fn = _lib.load().mpcr_rollout_cost_scenarios
+        if target is not None:
+            fn = _lib.load().mpcr_rollout_cost_scenarios_target
+            args += self._block_args("target", target, (8,), R, inp.device, target_per_step)
+        check(fn(
             self.handle, _ptr(inp), layout, nprob, nscen, worst, n_per, self._params_arg(params, R), *args,
             _ptr(cost4_scen), _ptr(cost4), _ptr(theta), _ptr(thetadot), _ptr(best_keys), int(index_base),
             _ptr(status), *_call_tail(inp, reset_best, stream)))

@@ -104,13 +104,33 @@ def moving_obstacle(model, name, velocity, num_steps, timestep):
     return poses
 
 
+def moving_target(velocity, num_steps, timestep):
+    """A target that translates at the constant world ``velocity`` (m/s), its
+    orientation held: a callable ``(tick, pos, rot) -> (pos_now, (pos_traj,
+    rot_traj))`` for the pose ``pos`` / ``rot`` the target had when it became
+    current, ``tick`` ticks ago.  ``pos_now`` is its position at the tick's
+    time, pos + tick timestep velocity; the trajectory holds the ``num_steps``
+    predicted poses of the planner's horizon (``compute_cem(target_traj=)``),
+    step k at pos + (tick + k) timestep velocity: (num_steps, 3) and
+    (num_steps, 4)."""
+    v = np.asarray(velocity, dtype=np.float64).reshape(3)
+
+    def at(tick, pos, rot):
+        pos, rot = np.asarray(pos, dtype=np.float64).reshape(3), np.asarray(rot, dtype=np.float64).reshape(4)
+        k = tick + np.arange(num_steps, dtype=np.float64)
+        traj = pos[None, :] + (k * timestep)[:, None] * v[None, :]
+        return pos + (tick * timestep) * v, (traj, np.tile(rot, (num_steps, 1)))
+
+    return at
+
+
 def run_cem_planner(num_dof=None, num_batch=None, num_steps=None, maxiter_cem=None, maxiter_projection=None,
                     w_pos=None, w_rot=None, w_col=None, num_elite=None, timestep=None, initial_qpos=None,
                     target_names=None, show_viewer=None, cam_distance=None, show_contact_points=None,
                     position_threshold=None, rotation_threshold=None, save_data=None, data_dir=None,
                     stop_at_final_target=None, *, max_ticks=100, model_path=None, device=None, graph=True,
                     verbose=True, planner_kwargs=None, plan_from_state=False, ctrl=None, geom_poses=None,
-                    hypotheses=None, scenario_worst=None):
+                    hypotheses=None, scenario_worst=None, target_velocity=None):
     """Run the CEM planner in closed loop for ``max_ticks`` ticks (headless).
     plan_from_state: every tick's rollouts start from the plant's full state
     (a device copy of its block) instead of the template state with the arm
@@ -130,7 +150,13 @@ def run_cem_planner(num_dof=None, num_batch=None, num_steps=None, maxiter_cem=No
     0): each adds a scenario in which that static geom is displaced by the
     offset (m, world) from wherever the tick's poses put it
     (``cem_planner(num_scenarios=)``).  scenario_worst: a candidate's cost is
-    the mean of its that many largest scenario costs (default: of all)."""
+    the mean of its that many largest scenario costs (default: of all).
+    target_velocity: from the tick a named target body becomes current, its
+    position translates at this constant world velocity (m/s), one timestep
+    per tick (``moving_target``): the planner gets the num_steps predicted
+    poses of its horizon (``cem_planner(target_schedule=)``), the reached-test
+    and the logged cost_g use the pose at the tick's time.  "home" does not
+    move.  None: the targets stand still, and nothing changes."""
     hypotheses = list(hypotheses or [])
     if initial_qpos is None:
         initial_qpos = [1.5, -1.8, 1.75, -1.25, -1.6, 0]
@@ -156,7 +182,8 @@ def run_cem_planner(num_dof=None, num_batch=None, num_steps=None, maxiter_cem=No
                                           | ({"geom_poses": "per_step"} if geom_poses is not None or hypotheses
                                              else {})
                                           | ({"num_scenarios": 1 + len(hypotheses), "scenario_worst": scenario_worst}
-                                             if hypotheses else {})))
+                                             if hypotheses else {})
+                                          | ({"target_schedule": True} if target_velocity is not None else {})))
     log(f"Initialized CEM Planner: {round(time.time() - start_time, 2)}s")
 
     model = cem.model
@@ -227,6 +254,8 @@ def run_cem_planner(num_dof=None, num_batch=None, num_steps=None, maxiter_cem=No
     step_ms, eef_dist = [], []
     target_idx = 0
     current_target = target_names[target_idx]
+    target_motion = None if target_velocity is None else moving_target(target_velocity, num_steps, timestep)
+    target_since = 0  # the tick the current target became current
     if show_viewer:
         log("No viewer on this build: running the closed loop headless")
 
@@ -240,10 +269,14 @@ def run_cem_planner(num_dof=None, num_batch=None, num_steps=None, maxiter_cem=No
             target_rot = init_rotation
         if current_target == "target_1" and "target_0" in target_names:
             bodies.set("target_0", data.site_xpos_tcp, data.xquat_hande)
+        to_target = {}
+        if target_motion is not None and current_target != "home":
+            target_pos, traj = target_motion(_tick - target_since, target_pos, target_rot)
+            to_target = {"target_traj": traj}
 
         cost, best_cost_g, best_cost_r, best_cost_c, best_vels, best_traj, xi_mean, _, _ = cem.compute_cem(
             xi_mean, data.qpos[ctrl_q], data.qvel[ctrl_v], data.qacc[ctrl_v], target_pos, target_rot, **from_plant,
-            **apply_ctrl(_tick), **apply_geom_poses(_tick))
+            **apply_ctrl(_tick), **apply_geom_poses(_tick), **to_target)
 
         thetadot = np.mean(best_vels[1:num_steps - 2], axis=0)
         data.step(thetadot)
@@ -270,10 +303,12 @@ def run_cem_planner(num_dof=None, num_batch=None, num_steps=None, maxiter_cem=No
                 else:
                     target_idx = 0
                     current_target = target_names[target_idx]
+                    target_since = _tick + 1
                     log(f"Reached final target. Looping back to first target: {current_target}")
             else:
                 target_idx = target_idx + 1
                 current_target = target_names[target_idx]
+                target_since = _tick + 1
                 log(f"Moving to next target: {current_target}")
             if current_target == "home" and "target_0" in target_names:
                 bodies.set("target_0", data.site_xpos_tcp, data.xquat_hande)
@@ -336,6 +371,9 @@ def main(argv=None):  # SBP/mpc_planner.py:256-314
                              "displaced by the offset (m); scenario 0 is the plant's own world")
     parser.add_argument("--scenario_worst", type=int, default=None, metavar="K",
                         help="a candidate's cost is the mean of its K largest scenario costs (default: of all)")
+    parser.add_argument("--target_velocity", nargs=3, type=float, default=None, metavar=("VX", "VY", "VZ"),
+                        help="a target body, once current, translates at this constant world velocity (m/s): the "
+                             "planner gets the predicted poses of its horizon")
     a = parser.parse_args(argv)
     geom_poses = None
     if a.obstacle is not None:
@@ -357,7 +395,7 @@ def main(argv=None):  # SBP/mpc_planner.py:256-314
                            model_path=a.model, graph=not a.no_graph, plan_from_state=a.plan_from_state,
                            ctrl=ctrl, geom_poses=geom_poses,
                            hypotheses=[(h[0], [float(x) for x in h[1:]]) for h in a.hypothesis or []],
-                           scenario_worst=a.scenario_worst)
+                           scenario_worst=a.scenario_worst, target_velocity=a.target_velocity)
 
 
 if __name__ == "__main__":

@@ -120,6 +120,14 @@ class cem_planner:  # noqa: N801 (reference name)
                         (ng, 8) per problem; "per_step", one block per step of
                         the horizon (H, ng, 8), an obstacle that moves during
                         it.  Independent of the two above
+    target_schedule     the rollouts price the end effector against a target
+                        pose per step of the horizon, read per problem from a
+                        static device buffer of target rows (H, 8)
+                        (``compute_cem(target_traj=...)``), instead of the one
+                        pose of the parameter block.  Every tick stages it: a
+                        tick without a trajectory holds ``target_pos`` /
+                        ``target_rot`` over the horizon and plans what a
+                        planner without the flag plans, bit for bit
     num_scenarios       world hypotheses per problem (default 1: none).  With
                         S > 1 the state, control and geom-pose buffers hold
                         one block per problem and scenario -- ``compute_cem``'s
@@ -139,7 +147,7 @@ class cem_planner:  # noqa: N801 (reference name)
                  model_path=None, device=None, seed=0, elite_from_filtered=False, graph=False, group=None,
                  gather_rollouts=False, return_rollouts=True, capture_exchange=True, verbose=True,
                  num_problems=1, seed_step=0, plan_from_state=False, actuator_ctrl=False, geom_poses=False,
-                 num_scenarios=1, scenario_worst=None):
+                 num_scenarios=1, scenario_worst=None, target_schedule=False):
         import torch
         import torch.distributed as tdist
 
@@ -256,6 +264,9 @@ class cem_planner:  # noqa: N801 (reference name)
             rep = (B * S, H, 1, 1) if geom_poses == "per_step" else (B * S, 1, 1)
             self._gpose = torch.as_tensor(own).to(self.device).repeat(*rep).contiguous()
             self._gpose = self._gpose.view((B,) + sb + tuple(self._gpose.shape[1:]))
+        # one target row per problem (and scenario) and step: every tick stages it (_stage_targets)
+        self.target_schedule = bool(target_schedule)
+        self._target = torch.zeros((B,) + sb + (H, 8), **f32) if self.target_schedule else None
         self._graphs = None
         if verbose and self.rank == 0:
             self.print_info()
@@ -303,14 +314,16 @@ class cem_planner:  # noqa: N801 (reference name)
                                                self._scen_costs[it], worst=self.scenario_worst, cost4=self._costs[it],
                                                start=flat(self._state), ctrl=flat(self._ctrl),
                                                geom_pose=flat(self._gpose),
-                                               geom_pose_per_step=self.geom_poses == "per_step", **out)
+                                               geom_pose_per_step=self.geom_poses == "per_step",
+                                               target=flat(self._target), target_per_step=self.target_schedule,
+                                               **out)
         else:
             # one launch over the problems, reading each one's start / control /
             # geom-pose block where the planner stages one (None: the model's own)
             self.engine.rollout_cost_state(self._xf.view(B * n, self.nvar), MPCR_LAYOUT_XI, self._par, B,
                                            self._costs[it], start=self._state, ctrl=self._ctrl,
                                            geom_pose=self._gpose, geom_pose_per_step=self.geom_poses == "per_step",
-                                           **out)
+                                           target=self._target, target_per_step=self.target_schedule, **out)
 
     def _seg_local_update(self, it):
         """compute_ellite_samples + compute_mean_cov on one rank (:355-360)."""
@@ -487,8 +500,43 @@ class cem_planner:  # noqa: N801 (reference name)
                                  + (f" or {whole}, one per scenario" if whole != full else "") + f", got {g.shape}")
             self._gpose[p].copy_(torch.as_tensor(np.broadcast_to(g, whole).copy()))
 
+    def _stage_targets(self, trajs, target_pos, target_rot):
+        """Each problem's target schedule into the static buffer: (H, 8) target
+        rows (``Engine.target_rows``) or a (pos (H, 3), rot (H, 4)) pair; with
+        scenarios also a leading (S, ...) axis, one schedule per scenario.
+        Unlike the other blocks, None does not keep what is staged: the tick's
+        target_pos / target_rot, given every tick, are held over the horizon.
+        Every rank of a sharded planner stages the same schedule."""
+        import torch
+        if not self.target_schedule:
+            if trajs is not None and any(t is not None for t in trajs):
+                raise ValueError("a target trajectory needs a planner built with target_schedule=True")
+            return
+        B, S, H = self.num_problems, self.num_scenarios, self.num
+        if trajs is None:
+            trajs = [None] * B
+        if len(trajs) != B:
+            raise ValueError(f"{len(trajs)} target trajectories for {B} problem(s)")
+        whole = tuple(self._target.shape[1:])  # (H, 8), or (S, H, 8) with scenarios
+        out = np.empty((B,) + whole, dtype=np.float32)
+        for p, tr in enumerate(trajs):
+            if tr is None:
+                out[p] = Engine.target_rows(target_pos[p], target_rot[p])
+                continue
+            if isinstance(tr, (tuple, list)) and len(tr) == 2:
+                pos, rot = (np.asarray(x.cpu() if hasattr(x, "cpu") else x, dtype=np.float32) for x in tr)
+                if pos.shape[-1:] != (3,) or rot.shape[-1:] != (4,) or pos.shape[:-1] != rot.shape[:-1]:
+                    raise ValueError(f"a target trajectory pair is (pos (H, 3), rot (H, 4)); got {pos.shape}, {rot.shape}")
+                tr = Engine.target_rows(pos, rot)
+            tr = np.asarray(tr.cpu() if hasattr(tr, "cpu") else tr, dtype=np.float32)
+            if tr.shape != (H, 8) and tr.shape != whole:
+                raise ValueError(f"a target trajectory is ({H}, 8) rows or a (pos ({H}, 3), rot ({H}, 4)) pair"
+                                 + (f", or {whole}, one per scenario" if S > 1 else "") + f"; got {tr.shape}")
+            out[p] = tr
+        self._target.copy_(torch.as_tensor(out))
+
     def compute_cem(self, xi_mean, init_pos=(1.5, -1.8, 1.75, -1.25, -1.6, 0.0), init_vel=None, init_acc=None,
-                    target_pos=None, target_rot=None, state=None, ctrl=None, geom_pose=None):
+                    target_pos=None, target_rot=None, state=None, ctrl=None, geom_pose=None, target_traj=None):
         """One MPC tick of CEM (SBP/mjx_planner.py:364-406). Returns the reference 9-tuple (numpy).
         state (planners built with plan_from_state): the full state the
         rollouts start from, a ``Plant`` or ``(qpos, qvel[, qacc_warmstart])``;
@@ -498,7 +546,11 @@ class cem_planner:  # noqa: N801 (reference name)
         staged last (at first the model's own).  geom_pose (planners built
         with geom_poses): the static geoms' poses of the rollouts, a
         geom-pose block (ng, 8) or, "per_step", (H, ng, 8); None keeps the
-        one staged last (at first the model's own)."""
+        one staged last (at first the model's own).  target_traj (planners
+        built with target_schedule): the target pose of every step of the
+        horizon, (H, 8) target rows or a (pos (H, 3), rot (H, 4)) pair, with
+        scenarios also (S, H, 8); None holds target_pos / target_rot over
+        the horizon."""
         import torch
 
         from . import dist as mdist
@@ -522,6 +574,7 @@ class cem_planner:  # noqa: N801 (reference name)
         self._stage_states(None if state is None else [state])
         self._stage_ctrls(None if ctrl is None else [ctrl])
         self._stage_geom_poses(None if geom_pose is None else [geom_pose])
+        self._stage_targets(None if target_traj is None else [target_traj], target_pos[None], target_rot[None])
         self._run_iterations()
 
         costs, theta, thetadot = self._costs, self._theta, self._thetadot
@@ -548,7 +601,7 @@ class cem_planner:  # noqa: N801 (reference name)
         return tuple(o.cpu().numpy() if isinstance(o, torch.Tensor) else o for o in out)
 
     def compute_cem_batch(self, xi_mean, init_pos, init_vel=None, init_acc=None, target_pos=None, target_rot=None,
-                          weights=None, states=None, ctrls=None, geom_poses=None):
+                          weights=None, states=None, ctrls=None, geom_poses=None, target_trajs=None):
         """One MPC tick of ``num_problems`` independent CEM problems in one
         batched sequence of launches (each kernel of ``compute_cem`` once,
         over every problem): xi_mean (B, nvar), init_pos / init_vel /
@@ -562,7 +615,10 @@ class cem_planner:  # noqa: N801 (reference name)
         ``state`` (a None entry keeps that problem's).  ctrls (planners built
         with actuator_ctrl): one control block per problem, likewise.
         geom_poses (planners built with geom_poses): one geom-pose block per
-        problem, likewise."""
+        problem, likewise.  target_trajs (planners built with
+        target_schedule): one target trajectory per problem as
+        ``compute_cem``'s ``target_traj``; a None entry holds that problem's
+        target_pos / target_rot over the horizon."""
         import torch
 
         B, d, H, n, it_n = self.num_problems, self.num_dof, self.num, self.n_local, self.maxiter_cem
@@ -589,6 +645,7 @@ class cem_planner:  # noqa: N801 (reference name)
         self._stage_states(states)
         self._stage_ctrls(ctrls)
         self._stage_geom_poses(geom_poses)
+        self._stage_targets(target_trajs, target_pos, target_rot)
         self._run_iterations()
 
         # each problem's best candidate of the last iteration: the low word of

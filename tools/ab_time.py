@@ -6,7 +6,9 @@ of rollout_cost, with CTRL=none (no control block: runs on a library from
 before the control input too), const (one block of the model's own controls)
 or sched (one row per step), and GEOM=none, const (one block of the model's
 own static geom poses) or sched (one block per step); START=1 starts from a
-block holding the template state, which alone selects the STATE kernels."""
+block holding the template state, which alone selects the STATE kernels;
+TARGET=none, const (one target row, the parameter block's) or sched (one row
+per step, the target translating and yawing over the horizon)."""
 import os
 import sys
 
@@ -41,7 +43,7 @@ if os.environ.get("THETA", "1") == "0":  # traffic attribution: no theta / theta
 key = torch.empty(1, dtype=torch.int64, device="cuda")
 args = (xi, MPCR_LAYOUT_XI, q0, (20., 3., 80.), (-0.3, -0.3, 0.5), (0., 1., 0., 0.))
 entry, ctrl_mode = os.environ.get("ENTRY", "cost"), os.environ.get("CTRL", "none")
-geom_mode = os.environ.get("GEOM", "none")
+geom_mode, target_mode = os.environ.get("GEOM", "none"), os.environ.get("TARGET", "none")
 if entry == "state":
     par = torch.as_tensor(Engine.params(*args[2:])).cuda()
     ckw = {}
@@ -54,6 +56,13 @@ if entry == "state":
         own = torch.as_tensor(e.model.geom_poses()[0]).cuda()
         ckw |= (dict(geom_pose=own) if geom_mode == "const"
                 else dict(geom_pose=own.repeat(1, H, 1, 1).contiguous(), geom_pose_per_step=True))
+    if target_mode != "none":
+        t = np.arange(H if target_mode == "sched" else 1) * 0.05
+        pos = np.asarray(args[4]) + t[:, None] * np.array([0.2, -0.1, 0.1]) * (12.0 / H)
+        rot = np.stack([np.zeros_like(t), np.cos(0.5 * t * (12.0 / H)), np.sin(0.5 * t * (12.0 / H)), np.zeros_like(t)], 1)
+        rows = torch.as_tensor(Engine.target_rows(pos, 1.7 * rot)).cuda()
+        ckw |= dict(target=rows[0].contiguous()) if target_mode == "const" else dict(target=rows[None].contiguous(),
+                                                                                     target_per_step=True)
 
     def run(theta=None, thetadot=None, best_key=None, status=None):
         e.rollout_cost_state(xi, MPCR_LAYOUT_XI, par, 1, c4, theta=theta, thetadot=thetadot, best_keys=best_key,
@@ -85,7 +94,8 @@ run(theta=th, thetadot=td, best_key=key, status=st)
 sv = st.cpu().numpy()
 rows = f" rows/step {float((sv >> 11).mean()) / H:.1f} max-rows p50/p90/p99 " + "/".join(
     str(int(np.percentile((sv >> 2) & 255, q))) for q in (50, 90, 99))
-tag = f" {entry}/ctrl={ctrl_mode}/geom={geom_mode}/start={os.environ.get('START', '0')}" if entry == "state" else ""
+tag = (f" {entry}/ctrl={ctrl_mode}/geom={geom_mode}/start={os.environ.get('START', '0')}/target={target_mode}"
+       if entry == "state" else "")
 print(f"{os.path.basename(sys.argv[1])}{tag}{occ}{rows} {name} {n}x{H} median {np.median(ts):.3f} ms min {np.min(ts):.3f} "
       f"-> {n / np.median(ts) * 1e3:.0f} rollouts/s  cost0 {float(c4[:, 0].sum()):.6e}")
 if os.environ.get("SAVE"):  # outputs of the last launch, for bitwise comparisons between variants
