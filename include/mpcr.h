@@ -128,7 +128,7 @@ void mpcr_model_free(mpcr_model* m);
 /* The support start table an engine builds for m's convex hulls (model
    format v9 dropped it from the blob; dev_model.h hull_start_table): R x R
    cells on each of the 6 cube faces (R = 0: the library's MPCR_LUT_R), cell
-   (2 axis + negative) R^2 + iu R + iv (rollout.hip lut_cell), each naming
+   (2 axis + negative) R^2 + iu R + iv (csrc/convex_mpr.h lut_cell), each naming
    the global hull vertex extreme along the cell centre (fp64; the lowest
    index among exact ties).  geom_adr[ngeom] (nullable) receives each geom's
    first cell (-1: no hull), cells and exact (nullable) every cell when cap

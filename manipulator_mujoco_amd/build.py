@@ -21,8 +21,8 @@ CSRC = os.path.join(HERE, "csrc")
 # and no trapping; NaN / Inf semantics stay): 2.29 -> 2.25 ms, parity unchanged.
 # The CEM TU does not get it (top-k orders -0 before +0 like the reference).
 # The rollout kernel (rollout.hip, device code only) is built in two units that
-# include it: rollout_narrow.hip, the single-arm kernels and the launch logic,
-# with those flags; rollout_wide.hip,
+# include it: rollout_narrow.hip, the single-arm kernels, with those flags
+# (the launch planning is host code, rollout_plan.h in engine.hip); rollout_wide.hip,
 # the dual-arm kernels, precise -- the fast-math device flags dropped
 # (_drop_fast: IEEE division / square root, no reassociation): the
 # latency-bound dual arm pays ~5 % (C4 45.9 -> 48.3 ms) and its rollouts keep
@@ -39,8 +39,13 @@ SRC = [u[0] for u in UNITS]
 # missing): the rebuild check and source_hash() read this list.  The MJCF
 # library's source and ABI header are listed too, so the hash names the whole
 # native build.
-DEPS = SRC + [os.path.join(CSRC, f) for f in ("rollout.hip", "rollout.h", "step_table.h", "model_frames.h", "dev_model.h",
-                                              "cem.hip", "comm.hip", "mpcr_device.h", "mjcf_embed.cpp")] + [
+# the rollout kernel's device headers, in rollout.hip's include order
+ROLLOUT_HEADERS = ("rollout_instruments.h", "rollout_switches.h", "wave.h", "vecmath.h", "spd_solve.h", "narrow_prims.h",
+                   "convex_mpr.h", "manifold.h", "narrow_lane.h", "box_box.h", "kernarg.h", "contacts.h", "linesearch.h",
+                   "jrows.h")
+DEPS = SRC + [os.path.join(CSRC, f) for f in ("rollout.hip", "rollout.h", "rollout_plan.h", "step_table.h", "model_frames.h",
+                                              "dev_model.h", "cem.hip", "comm.hip", "mpcr_device.h", "mjcf_embed.cpp") +
+              ROLLOUT_HEADERS] + [
     os.path.join(os.path.dirname(HERE), "include", f) for f in ("mpcr.h", "mpcr_model.h", "mpcr_mjcf.h")]
 OUT = os.path.join(HERE, "libmpcr.so")
 ARCH = os.environ.get("MPCR_OFFLOAD_ARCH", "gfx950")

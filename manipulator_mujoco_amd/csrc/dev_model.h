@@ -58,7 +58,7 @@ inline int dev_fail(std::string& err, int code, const char* fmt, ...) {
 }
 
 // ---- support start table (model v9: built here from hull_vert, not packed) ----
-// Per hull and cube-map cell (6 faces x R x R, rollout.hip lut_cell order) the
+// Per hull and cube-map cell (6 faces x R x R, convex_mpr.h lut_cell order) the
 // vertex extreme along the cell centre, in fp64.  The cells of a hull run in
 // scan order, each climbing the hull graph (strict ascent) from the previous
 // cell's vertex -- neighbouring cells mostly share one, so a cell costs a

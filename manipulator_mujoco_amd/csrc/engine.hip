@@ -18,9 +18,11 @@
 #include "mpcr_device.h"
 
 // kernels: the fused rollout has its own translation units (rollout.hip, built through
-// rollout_narrow.hip and rollout_wide.hip; its launchers declared in rollout.h); cem.hip:
+// rollout_narrow.hip and rollout_wide.hip; their launchers declared in rollout.h, the launch
+// planning over them in rollout_plan.h); cem.hip:
 // the CEM distribution step
 #include "rollout.h"
+#include "rollout_plan.h"
 #include "dev_model.h"
 #include "step_table.h"
 
@@ -508,11 +510,9 @@ struct Launch {
   float* dbg = nullptr;
   bool reset_key = false;
   int nprob = 1, prob_n = 0;  // nprob > 1: problems of prob_n candidates each (0: one problem)
-  // the call's state blocks (rollout.h: start / final_state, ctrl, geom_pose; strides in floats) and
-  // the scenarios per planning problem that share its input rows (0: none; scen_count)
-  StateArgs sa = {};
-  int nscen = 0;
-  TargetArgs ta = {};  // the call's target schedule (rollout.h; null: the parameter block's target)
+  // the call's blocks (rollout.h: start / final_state, ctrl, geom_pose, strides in floats; the scenarios per
+  // planning problem that share its input rows, 0: none; the target schedule, null: the parameter block's target)
+  CallBlocks blk = {};
 };
 
 // the kernel's arguments for launch l of engine e (the one place they are filled)
@@ -550,15 +550,14 @@ static int rollout_args(const mpcr_engine* e, const Launch& l, RolloutArgs& a) {
   a.seg_min_n = e->seg_min_n;
   a.prob_n = l.prob_n;
   a.prob_off = 0;
-  // a call with a device parameter block carries its StateArgs in par's
-  // bytes (rollout.h; null pointers when it has no state blocks) and never
+  // a call with a device parameter block carries its CallBlocks in par's
+  // bytes (rollout.h; null pointers when it has no blocks) and never
   // parameter values, so has_state() cannot read those as pointers
   if (l.dpar) {
-    set_state_args(a, l.sa);
-    set_scen_count(a, l.nscen);
-    set_target_args(a, l.ta);
+    a.blk = l.blk;
   } else {
-    if (l.sa.start || l.sa.final_state || l.sa.ctrl || l.sa.geom_pose || l.nscen || l.ta.target)
+    const StateArgs& s = l.blk.st;
+    if (s.start || s.final_state || s.ctrl || s.geom_pose || l.blk.nscen || l.blk.tg.target)
       return fail(MPCR_EINVAL, "state, control and geom-pose blocks need a device parameter block");
     std::memcpy(a.par, l.par, sizeof(a.par));
   }
@@ -584,7 +583,7 @@ extern "C" int mpcr_engine_dispatches(const mpcr_engine* e, int n, int* out) {
   Launch l;
   l.n = n;
   if (int rc = rollout_args(e, l, a)) return rc;
-  *out = rollout_dispatches(e->wide, a, n, e->seg_groups, e->seg_stream[0] != nullptr);
+  *out = rollout_dispatches(e->wide, a, n, e->seg_groups, e->seg_stream[0] != nullptr, plan_thresholds());
   return MPCR_OK;
 }
 
@@ -734,7 +733,7 @@ static int check_block(const mpcr_engine* e, const char* name, const char* stem,
 // one-problem kernels through any entry (prob_n = 0): the MULTI
 // instantiations' problem lookup is paid only where there is one to make.
 static int rollout_call(mpcr_engine* e, Launch& l, int flags, void* stream) {
-  StateArgs& s = l.sa;
+  StateArgs& s = l.blk.st;
   if (s.start && s.start_stride != 0 && s.start_stride < ST_N)
     return fail(MPCR_EINVAL, "start_stride=%d: 0 (one block for every problem) or at least the block's %d floats",
                 s.start_stride, (int)ST_N);
@@ -753,7 +752,7 @@ static int rollout_call(mpcr_engine* e, Launch& l, int flags, void* stream) {
   if (!s.start) s.start_stride = 0;
   if (!s.ctrl) s.ctrl_stride = s.ctrl_step_stride = 0;
   if (!s.geom_pose) s.geom_stride = s.geom_step_stride = 0;
-  TargetArgs& tg = l.ta;
+  TargetArgs& tg = l.blk.tg;
   if (tg.target) {
     if (int rc = check_block(e, "target", "target", tg.target, tg.stride, tg.step_stride, "a target row", 8, 16))
       return rc;
@@ -815,10 +814,10 @@ extern "C" int mpcr_rollout_cost_target(mpcr_engine* e, const float* input, int 
   l.in = input; l.layout = layout; l.nprob = nprob; l.n = nprob * n_per; l.dpar = params; l.index_base = index_base;
   l.cost4 = cost4; l.theta = theta; l.thetadot = thetadot; l.status = status;
   l.key = reinterpret_cast<unsigned long long*>(best_keys);
-  l.sa.start = start; l.sa.start_stride = start_stride; l.sa.final_state = final_state;
-  l.sa.ctrl = ctrl; l.sa.ctrl_stride = ctrl_stride; l.sa.ctrl_step_stride = ctrl_step_stride;
-  l.sa.geom_pose = geom_pose; l.sa.geom_stride = geom_stride; l.sa.geom_step_stride = geom_step_stride;
-  l.ta.target = target; l.ta.stride = target_stride; l.ta.step_stride = target_step_stride;
+  l.blk.st.start = start; l.blk.st.start_stride = start_stride; l.blk.st.final_state = final_state;
+  l.blk.st.ctrl = ctrl; l.blk.st.ctrl_stride = ctrl_stride; l.blk.st.ctrl_step_stride = ctrl_step_stride;
+  l.blk.st.geom_pose = geom_pose; l.blk.st.geom_stride = geom_stride; l.blk.st.geom_step_stride = geom_step_stride;
+  l.blk.tg.target = target; l.blk.tg.stride = target_stride; l.blk.tg.step_stride = target_step_stride;
   return rollout_call(e, l, flags, stream);
 }
 
@@ -892,12 +891,12 @@ extern "C" int mpcr_rollout_cost_scenarios_target(mpcr_engine* e, const float* i
   // problem (input, theta and thetadot hold nprob n_per rows; no keys: the reduction's), then the fold
   Launch l;
   l.in = input; l.layout = layout; l.nprob = nprob * nscen; l.n = l.nprob * n_per; l.dpar = params;
-  l.index_base = index_base; l.nscen = nscen > 1 ? nscen : 0;
+  l.index_base = index_base; l.blk.nscen = nscen > 1 ? nscen : 0;
   l.cost4 = cost4_scen; l.theta = theta; l.thetadot = thetadot; l.status = status;
-  l.sa.start = start; l.sa.start_stride = start_stride; l.sa.final_state = final_state;
-  l.sa.ctrl = ctrl; l.sa.ctrl_stride = ctrl_stride; l.sa.ctrl_step_stride = ctrl_step_stride;
-  l.sa.geom_pose = geom_pose; l.sa.geom_stride = geom_stride; l.sa.geom_step_stride = geom_step_stride;
-  l.ta.target = target; l.ta.stride = target_stride; l.ta.step_stride = target_step_stride;
+  l.blk.st.start = start; l.blk.st.start_stride = start_stride; l.blk.st.final_state = final_state;
+  l.blk.st.ctrl = ctrl; l.blk.st.ctrl_stride = ctrl_stride; l.blk.st.ctrl_step_stride = ctrl_step_stride;
+  l.blk.st.geom_pose = geom_pose; l.blk.st.geom_stride = geom_stride; l.blk.st.geom_step_stride = geom_step_stride;
+  l.blk.tg.target = target; l.blk.tg.stride = target_stride; l.blk.tg.step_stride = target_step_stride;
   if (int rc = rollout_call(e, l, flags & ~(MPCR_F_SYNC | MPCR_F_RESET_BEST), stream)) return rc;
   if (cost4)
     return mpcr_scenario_reduce(e, cost4_scen, nprob, nscen, n_per, worst, cost4, best_keys, index_base, flags,

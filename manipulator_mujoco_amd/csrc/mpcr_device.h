@@ -31,7 +31,7 @@ constexpr int DX_NTEN = 2;     // spatial (two-site) tendons with length limits
 // CONE_R x CONE_R per cube face (built on the host from the face planes)
 constexpr int CONE_R = 8;
 constexpr int CONE_CELLS = 6 * CONE_R * CONE_R;
-constexpr double CONE_COS = 0.94;  // the kernel's and the oracle's cone (rollout.hip kPolyConeCos)
+constexpr double CONE_COS = 0.94;  // the kernel's and the oracle's cone (manifold.h kPolyConeCos)
 
 // The model's table pointers are global memory: typed so in the device pass
 // (same 8-byte layout as the host's plain pointers), so the kernel's loads
@@ -56,7 +56,7 @@ enum { BK_STATIC = 0, BK_FREE = 1, BK_HINGE = 2, BK_SLIDE = 3, BK_WELD = 4 };
 // warm-start choice computed (rollout.hip; MPCR_NEWTON_REUSE=0, tests)
 constexpr int DEV_NO_NEWTON_REUSE = 1 << 30;
 // ... and this one: every lane with a capsule-box pair computes its contact
-// points and normals, not only the lanes that emit a contact (rollout.hip,
+// points and normals, not only the lanes that emit a contact (narrow_lane.h,
 // narrow_lane, single-arm kernels; MPCR_NARROW_EAGER=1, tests)
 constexpr int DEV_NARROW_EAGER = 1 << 29;
 // ... and this one: the single-arm step keeps its former one-lane and repeated

@@ -1,7 +1,8 @@
 // rollout.h -- what the host side (engine.hip) shares with the rollout
 // kernel (rollout.hip) and its two translation units (rollout_narrow.hip,
 // rollout_wide.hip): the launch arguments, the plant state layout, the
-// per-block LDS images (sizes for the HBM slabs), and the launchers.  The two
+// per-block LDS images (sizes for the HBM slabs), and the class launchers
+// (the launch planning over them is rollout_plan.h).  The two
 // units are compiled on their own, each with its own flags (see
 // manipulator_mujoco_amd/build.py).
 #pragma once
@@ -48,6 +49,87 @@ constexpr int SEG_QPOS = 0, SEG_QVEL = DX_NQ, SEG_QWS = DX_NQ + 32, SEG_COSTC = 
 // pacing table: (XCC 8 x SE 8 x SH 2 x CU 16 x SIMD 4) groups of 16 wave slots
 constexpr unsigned MPCR_PACE_SLOTS = 8u * 8u * 2u * 16u * 4u * 16u;
 
+// The blocks of a call with a device parameter block (CallBlocks below; the
+// state, scenario and target entries of include/mpcr.h, which always pass
+// dpar).  Such a call does not use RolloutArgs::par, and carries its
+// CallBlocks in the same bytes (RolloutArgs::blk, one union): the argument
+// block keeps its layout, and the kernels that do not read the blocks compile
+// to the code they had.  Every block is nullable, addressed per problem p and
+// therefore left alone by group_args (rollout_plan.h) -- final_state, per
+// candidate, is the exception.
+// st.start: the candidates of problem p begin from qpos | qvel |
+// qacc_warmstart of the ST_* block at start + p start_stride (stride 0: one
+// block for every problem) where they otherwise take the template's and a
+// zero warm start; read-only, the init_pos override, fresh hull-climb hints
+// and the slot history as ever.  st.final_state: candidate b's block at
+// final_state + b ST_N receives what a plant holds after the same H steps.
+// Neither is plant mode: plant stays 0 and segments stay eligible.
+// st.ctrl: the actuator controls as an input of the call, nu floats in
+// actuator order, read when the kernel runs and clamped there to
+// DevModel::act_ctrlrange; null keeps the model's own (DevModel::act_gain[a][3]).
+// Step t (absolute, so segments agree) of problem p reads the block at ctrl +
+// p ctrl_stride + t ctrl_step_stride: stride 0 is one block for every problem,
+// step stride 0 one block for the whole horizon.  Only the dual-arm class has
+// actuators.
+// st.geom_pose: the static collision geoms' world poses as an input of the
+// call, a block of DevModel::ngeom rows of 8 floats in the device model's geom
+// order, x y z 0 | qw qx qy qz, rows 16-byte aligned; only rows of static
+// geoms (geom_body < 0) are read, and used as they are where the kernel
+// otherwise takes DevModel::geom_pos / geom_quat.  Addressed like ctrl: step t
+// (absolute) of problem p reads the block at geom_pose + p geom_stride + t
+// geom_step_stride (floats, multiples of 4).
+struct StateArgs {
+  const float* start;
+  float* final_state;
+  int start_stride;
+  int ctrl_stride, ctrl_step_stride;
+  const float* ctrl;
+  const float* geom_pose;
+  int geom_stride, geom_step_stride;
+};
+// tg: the pose the cost's two terms read, as a schedule
+// (mpcr_rollout_cost_target).  A target row is 8 floats, x y z 0 | qw qx qy qz
+// -- floats PAR_PT.. of a parameter block -- 16-byte aligned; float 3 is never
+// read, the quaternion may have any norm (normalised by target_quat_unit, like
+// the parameter block's).  Addressed like ctrl: step t (absolute) of problem p
+// reads the row at target + p stride + t step_stride (floats, multiples of 4;
+// 0: one schedule for every problem / one row for the whole horizon).  Null
+// keeps the parameter block's ptgt / qtgt; with a schedule they are not used.
+struct TargetArgs {
+  const float* target;
+  int stride, step_stride;
+};
+// nscen: the scenarios per planning problem (mpcr_rollout_cost_scenarios); 0
+// or 1: none.  Rollout problem r = p nscen + s is scenario s of planning
+// problem p: an ordinary problem of the launch (its own parameter, start, ctrl
+// and geom-pose block, its own prob_n rows of cost4 / status / final_state),
+// except that every scenario of p reads the same prob_n input rows --
+// candidate gi = prob_off + b reads row (r / nscen) prob_n + gi % prob_n -- and
+// that theta and thetadot are written by scenario 0 alone, to that row.  The
+// mapping goes through prob_off, so group_args leaves input, theta and
+// thetadot where they are.
+// The kernels: st and tg are read by the STATE instantiations of
+// rollout_kernel, which the launchers pick when has_state(); nscen by the SCEN
+// ones (on top of STATE), picked when scenarios().
+struct CallBlocks {
+  StateArgs st;
+  int nscen;
+  int pad_;
+  TargetArgs tg;
+};
+static_assert(sizeof(StateArgs) == 56 && offsetof(StateArgs, start) == 0 && offsetof(StateArgs, final_state) == 8 &&
+                  offsetof(StateArgs, start_stride) == 16 && offsetof(StateArgs, ctrl_stride) == 20 &&
+                  offsetof(StateArgs, ctrl_step_stride) == 24 && offsetof(StateArgs, ctrl) == 32 &&
+                  offsetof(StateArgs, geom_pose) == 40 && offsetof(StateArgs, geom_stride) == 48 &&
+                  offsetof(StateArgs, geom_step_stride) == 52,
+              "StateArgs keeps its layout");
+static_assert(sizeof(TargetArgs) == 16 && offsetof(TargetArgs, target) == 0 && offsetof(TargetArgs, stride) == 8 &&
+                  offsetof(TargetArgs, step_stride) == 12,
+              "TargetArgs: one pointer and two ints");
+static_assert(offsetof(CallBlocks, nscen) == 56 && offsetof(CallBlocks, tg) == 64 &&
+                  sizeof(CallBlocks) == sizeof(float) * PAR_N,
+              "CallBlocks fills par's bytes: the count at 56, the target schedule at 64..80");
+
 struct RolloutArgs {
   const DevModel* m;
   const float* input;
@@ -88,9 +170,12 @@ struct RolloutArgs {
   float* state;
   int layout, n, H, nbasis, index_base, plant;
   // q0[8] | w[4] | ptgt[4] | qtgt[4] (any norm), for calls without dpar.  A
-  // call with dpar does not use it, and carries a StateArgs in its first
-  // bytes instead (below; launch_rollout writes one or the other)
-  float par[PAR_N];
+  // call with dpar does not use it, and carries its CallBlocks instead
+  // (above; rollout_args writes one or the other)
+  union {
+    float par[PAR_N];
+    CallBlocks blk;
+  };
   // several independent problems in one call (mpcr_rollout_cost_multi):
   // problem p owns candidates [p prob_n, (p + 1) prob_n) of the call, reads
   // its parameter block from dpar + p PAR_N and reduces into best_key[p] with
@@ -100,102 +185,6 @@ struct RolloutArgs {
   // instantiations of rollout_kernel, which the launchers pick for prob_n > 0.
   int prob_n, prob_off;
 };
-// A batch's start and final states (mpcr_rollout_cost_state, which always
-// passes dpar), ST_* blocks like the plant's.  Kept in the bytes of
-// RolloutArgs::par, which such a call does not use, and copied out with
-// state_args(): the argument block keeps its layout, and the kernels that do
-// not read it compile to the code they had.  start (nullable): the candidates
-// of problem p begin from qpos | qvel | qacc_warmstart of the block at start +
-// p start_stride (stride 0: one block for every problem) where they
-// otherwise take the template's and a zero warm start; read-only, the
-// init_pos override, fresh hull-climb hints and the slot history as ever.
-// Per problem, so candidate groups leave it alone (group_args).  final_state
-// (nullable): candidate b's block at final_state + b ST_N receives what a
-// plant holds after the same H steps.  Neither is plant mode: plant stays 0
-// and segments stay eligible.  Read by the STATE instantiations of
-// rollout_kernel, which the launchers pick when has_state().
-// ctrl (nullable): the actuator controls as an input of the call, nu floats
-// in actuator order, read when the kernel runs and clamped there to
-// DevModel::act_ctrlrange; null keeps the model's own (DevModel::act_gain[a][3]).
-// Step t (absolute, so segments agree) of problem p reads the block at ctrl +
-// p ctrl_stride + t ctrl_step_stride: stride 0 is one block for every problem,
-// step stride 0 one block for the whole horizon.  Per problem like start, so
-// group_args leaves it alone too.  Only the dual-arm class has actuators.
-// geom_pose (nullable): the static collision geoms' world poses as an input
-// of the call, a block of DevModel::ngeom rows of 8 floats in the device
-// model's geom order, x y z 0 | qw qx qy qz, rows 16-byte aligned; only rows
-// of static geoms (geom_body < 0) are read, and used as they are where the
-// kernel otherwise takes DevModel::geom_pos / geom_quat.  Addressed like
-// ctrl: step t (absolute) of problem p reads the block at geom_pose + p
-// geom_stride + t geom_step_stride (floats, multiples of 4).  Per problem, so
-// group_args leaves it alone.
-struct StateArgs {
-  const float* start;
-  float* final_state;
-  int start_stride;
-  int ctrl_stride, ctrl_step_stride;
-  const float* ctrl;
-  const float* geom_pose;
-  int geom_stride, geom_step_stride;
-};
-static_assert(sizeof(StateArgs) <= 56, "StateArgs: 56 of par's 80 bytes");
-static_assert(sizeof(StateArgs) <= sizeof(float) * PAR_N, "StateArgs inside par");
-__host__ __device__ inline StateArgs state_args(const RolloutArgs& a) {
-  StateArgs s;
-  __builtin_memcpy(&s, a.par, sizeof(s));
-  return s;
-}
-inline void set_state_args(RolloutArgs& a, const StateArgs& s) { __builtin_memcpy(a.par, &s, sizeof(s)); }
-// Scenarios (mpcr_rollout_cost_scenarios): the count, for the same calls, in
-// par's bytes right behind the StateArgs (whose size and field order stay as
-// they are); 0 or 1: none.  Rollout problem r = p nscen + s is scenario s of
-// planning problem p: an ordinary problem of the launch (its own parameter,
-// start, ctrl and geom-pose block, its own prob_n rows of cost4 / status /
-// final_state), except that every scenario of p reads the same prob_n input
-// rows -- candidate gi = prob_off + b reads row (r / nscen) prob_n + gi %
-// prob_n -- and that theta and thetadot are written by scenario 0 alone, to
-// that row.  The mapping goes through prob_off, so group_args leaves input,
-// theta and thetadot where they are.  Read by the SCEN instantiations (on top
-// of STATE), which the launchers pick when scenarios().
-constexpr size_t kScenOff = 56;
-static_assert(sizeof(StateArgs) <= kScenOff && kScenOff + sizeof(int) <= sizeof(float) * PAR_N,
-              "the scenario count behind StateArgs, inside par");
-__host__ __device__ inline int scen_count(const RolloutArgs& a) {
-  int n;
-  __builtin_memcpy(&n, reinterpret_cast<const char*>(a.par) + kScenOff, sizeof(n));
-  return n;
-}
-inline void set_scen_count(RolloutArgs& a, int n) {
-  __builtin_memcpy(reinterpret_cast<char*>(a.par) + kScenOff, &n, sizeof(n));
-}
-// Target schedule (mpcr_rollout_cost_target): the pose the cost's two terms
-// read as an input of the call, for the same calls, in par's bytes behind the
-// scenario count (64..80; StateArgs and the count stay where they are).  A
-// target row is 8 floats, x y z 0 | qw qx qy qz -- floats PAR_PT.. of a
-// parameter block -- 16-byte aligned; float 3 is never read, the quaternion
-// may have any norm (normalised by target_quat_unit, like the parameter
-// block's).  Addressed like ctrl: step t (absolute) of problem p reads the row
-// at target + p stride + t step_stride (floats, multiples of 4; 0: one
-// schedule for every problem / one row for the whole horizon).  Null keeps the
-// parameter block's ptgt / qtgt; with a schedule they are not used.  Per
-// problem, so group_args leaves it alone.  Read by the STATE instantiations.
-struct TargetArgs {
-  const float* target;
-  int stride, step_stride;
-};
-constexpr size_t kTargetOff = 64;
-static_assert(sizeof(StateArgs) == 56 && offsetof(StateArgs, geom_step_stride) == 52, "StateArgs keeps its layout");
-static_assert(kScenOff + sizeof(int) <= kTargetOff && kTargetOff % 8 == 0 && sizeof(TargetArgs) == 16 &&
-                  kTargetOff + sizeof(TargetArgs) <= sizeof(float) * PAR_N,
-              "the target schedule behind the scenario count, inside par");
-__host__ __device__ inline TargetArgs target_args(const RolloutArgs& a) {
-  TargetArgs t;
-  __builtin_memcpy(&t, reinterpret_cast<const char*>(a.par) + kTargetOff, sizeof(t));
-  return t;
-}
-inline void set_target_args(RolloutArgs& a, const TargetArgs& t) {
-  __builtin_memcpy(reinterpret_cast<char*>(a.par) + kTargetOff, &t, sizeof(t));
-}
 // the unit quaternion of a target's (parameter block or schedule row): the one
 // expression both go through
 __host__ __device__ inline void target_quat_unit(const float q[4], float out[4]) {
@@ -207,15 +196,11 @@ __host__ __device__ inline void target_quat_unit(const float q[4], float out[4])
 // kernels are STATE ones, block pointers or not)
 inline bool has_state(const RolloutArgs& a) {
   if (!a.dpar) return false;
-  const StateArgs s = state_args(a);
-  return s.start || s.final_state || s.ctrl || s.geom_pose || scen_count(a) > 1 || target_args(a).target;
+  const StateArgs& s = a.blk.st;
+  return s.start || s.final_state || s.ctrl || s.geom_pose || a.blk.nscen > 1 || a.blk.tg.target;
 }
 // the scenarios of a launch (0: none)
-inline int scenarios(const RolloutArgs& a) {
-  if (!a.dpar) return 0;
-  const int n = scen_count(a);
-  return n > 1 ? n : 0;
-}
+inline int scenarios(const RolloutArgs& a) { return a.dpar && a.blk.nscen > 1 ? a.blk.nscen : 0; }
 
 // Per-block LDS image, sized by the kernel variant: NVW = dense-solve width
 // (16 or 32 dofs), NBW = moving bodies, NGW = collision geoms.  Row stride
@@ -292,9 +277,9 @@ struct __align__(16) SmemT {
   };
   alignas(16) float gxpos[NGW][4];   // gxpos+gxmat (dead during Newton) double as the
   float gxmat[NGW][12];  // Hessian solve's LDS scratch (NGW*16 >= NVW*LD)
-  // keeps the layout (the previous slot distances live in HBM, RolloutArgs::slot_prev); the STATE kernels park
-  // the problem's target-schedule offset here, as bits (TargetArgs)
-  float cprev_pad_;
+  // the problem's offset into the target schedule, in quads (TargetArgs; STATE kernels).  The word keeps the
+  // layout: the previous slot distances it once began live in HBM (RolloutArgs::slot_prev)
+  unsigned tgt_quad0;
   float par[PAR_N];       // q0 | w | ptgt | qtgt (normalised)
   float eqp[NEQP][2][4];  // connect anchors in world (body1, body2)
   float tenp[WIDE ? DX_NTEN : 1][2][4];  // spatial-tendon sites in world
@@ -439,27 +424,18 @@ static_assert(sizeof(SmemW) <= 20448, "dual-arm LDS image must fit 8 blocks per 
 #endif
 
 
-// launchers (defined in rollout_narrow.hip): the rollout kernel variant for the
-// model class over `grid` blocks of one wave
-// Dual-arm batches of the one-wave variant with a.seg > 0 and H > a.seg run as
-// horizon segments of a.seg steps over `groups` candidate groups, group g on
-// gstream[g] (forked from st by gev[0] and joined back by gev[1 + g]); every
-// group's segments in stream order.  The launches of different groups overlap,
-// so one segment's tail is filled by the other groups' work.
-void rollout_launch(bool wide, const RolloutArgs& a, const DevModel* dm, unsigned grid, hipStream_t st,
-                    int groups = 0, hipStream_t* gstream = nullptr, hipEvent_t* gev = nullptr);
-// the dual-arm kernels' launches and occupancy (their own translation unit,
-// rollout_wide.hip): wpc 1 (one wave per candidate, block
-// per candidate) or 2 (two waves); info[0..2] blocks per CU, LDS, VGPRs
+// launchers: the rollout kernels of a model class over `grid` blocks of wpc
+// waves (1: one wave per candidate, 2: two), each class in its own translation
+// unit; rollout_plan.h decides wpc, horizon segments and candidate groups
+// the single-arm kernels' (rollout_narrow.hip)
+void rollout_narrow_launch(int wpc, unsigned grid, hipStream_t st, const RolloutArgs& a, const DevModel* dm);
+// the dual-arm kernels' launches and occupancy (rollout_wide.hip); info[0..2]
+// blocks per CU, LDS, VGPRs
 void rollout_wide_launch(int wpc, unsigned grid, hipStream_t st, const RolloutArgs& a, const DevModel* dm);
 hipError_t rollout_wide_occupancy(int* info);
-// kernel dispatches rollout_launch issues for the same arguments (gstream /
-// gev given: streams)
-int rollout_dispatches(bool wide, const RolloutArgs& a, unsigned grid, int groups, bool streams);
 // resident blocks per CU, static LDS bytes, VGPRs: narrow (0..2), wide (3..5)
 hipError_t rollout_occupancy(int* info);
 constexpr int REDUCE_SELFTEST_OUT = 12;  // floats per vector of mpcr_selftest_reduce (include/mpcr.h)
 hipError_t rollout_selftest_reduce(const float* in, int n, float* out);  // host pointers
-int rollout_set_wpc2_max_n(int n);  // two waves per candidate up to n (narrow variant); returns the previous
 
 }  // namespace mpcr

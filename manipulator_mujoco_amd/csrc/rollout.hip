@@ -7,7 +7,9 @@
 // (impedance, Newton line search).  The two dense SPD solves per step
 // (M and the Newton Hessian) are done row-per-lane in registers with DPP
 // row broadcasts (nv <= 16) or v_readlane (the 32-wide dual-arm variant): no
-// LDS round trips inside the factorisation.  Device code only, not built on
+// LDS round trips inside the factorisation.  This file is the kernel; the
+// device functions it calls are the headers below, one per subject.  Device
+// code only, not built on
 // its own: included by the two translation units that launch it,
 // rollout_narrow.hip (single-arm kernels) and rollout_wide.hip (dual-arm
 // kernels), each with its own flags (manipulator_mujoco_amd/build.py); host
@@ -20,2827 +22,23 @@
 #pragma once
 #include "rollout.h"
 #include "step_table.h"
-#include "../../include/mpcr_model.h"  // MPCR_LUT_R (the engine's hull start table)
+// (in the order the one file had them)
+#include "rollout_instruments.h"
+#include "rollout_switches.h"
+#include "wave.h"
+#include "vecmath.h"
+#include "spd_solve.h"
+#include "narrow_prims.h"
+#include "convex_mpr.h"
+#include "manifold.h"
+#include "narrow_lane.h"
+#include "box_box.h"
+#include "kernarg.h"
+#include "contacts.h"
+#include "linesearch.h"
+#include "jrows.h"
 
 namespace mpcr {
-
-// ---------------------------------------------------------------------------
-// diagnostic phase stamps (separate -DMPCR_PROFILE build; never in the timed one)
-#ifdef MPCR_PROFILE
-#define PROF_DECL unsigned long long prof_acc[32] = {0}; unsigned long long prof_last = __builtin_amdgcn_s_memtime();
-#define STAMP(i)                                              \
-  do {                                                        \
-    unsigned long long now_ = __builtin_amdgcn_s_memtime();   \
-    prof_acc[i] += now_ - prof_last;                          \
-    prof_last = now_;                                         \
-  } while (0)
-// (a candidate's second wave, WPC = 2, into slots 32..63: per-wave critical paths)
-#define PROF_FLUSH                                                          \
-  if (lane == 0 && KA->prof)                                               \
-    for (int i_ = 0; i_ < 32; i_++) atomicAdd(&KA->prof[i_ + 32 * (threadIdx.x >> 6)], prof_acc[i_]);
-// wave-level event counter (first active lane adds 1; -DMPCR_PROFILE_COUNTS
-// only: the shared atomics distort the cycle shares)
-#ifdef MPCR_PROFILE_COUNTS
-#define PROF_COUNT(m, i)                                                                  \
-  do {                                                                                    \
-    if ((m)->prof && (int)__lane_id() == __builtin_ctzll(__ballot(1))) atomicAdd((m)->prof + (i), 1ull); \
-  } while (0)
-#else
-#define PROF_COUNT(m, i)
-#endif
-// sub-phase stamps inside a device function (one atomic per stamp and wave)
-#define PSTAMP_DECL unsigned long long pst_ = __builtin_amdgcn_s_memtime();
-#define PSTAMP(m, i)                                                                       \
-  do {                                                                                     \
-    const unsigned long long now_ = __builtin_amdgcn_s_memtime();                          \
-    if ((m)->prof && (int)__lane_id() == 0) atomicAdd((m)->prof + (i) + 32 * (threadIdx.x >> 6), now_ - pst_); \
-    pst_ = now_;                                                                           \
-  } while (0)
-#else
-#define PSTAMP_DECL
-#define PSTAMP(m, i)
-#define PROF_DECL
-#define STAMP(i)
-#define PROF_FLUSH
-#define PROF_COUNT(m, i)
-#endif
-// Pacing (load balance of a one-round launch): at N = 4096 every candidate is
-// resident at once (4 waves per SIMD) and the launch ends with the slowest
-// candidate, ~18 % after the mean one (tools/wavetime.py).  Each wave posts
-// the step it is on in its SIMD's slot group and takes an issue priority
-// equal to the number of its SIMD mates ahead of it, so the waves sharing a
-// SIMD progress together and the SIMD drains when its total work is done.
-// Pacing in the dual-arm kernel too: 1.7 % slower at 7 blocks per CU (2.3
-// backfilled rounds), ~0.8 % faster at 8 (C4 4096 x 100: 33.6-34.0 vs
-// 34.1 ms; 8192 x 50: 30.35-30.45 vs 30.57-30.79 ms).
-// The mates' progress read at the step start is consumed before the
-// collision phase (mid-step).
-#define PACE_SETPRIO() \
-  if (pace) {  /* priority = SIMD mates ahead of this wave (0..3) */ \
-  const int ahead = __popcll(__ballot(lane < 16 && lane != pace_own && pace_v != ~0u && pace_v > (unsigned)t)); \
-  if (ahead >= 3) __builtin_amdgcn_s_setprio(3); \
-  else if (ahead == 2) __builtin_amdgcn_s_setprio(2); \
-  else if (ahead == 1) __builtin_amdgcn_s_setprio(1); \
-  else __builtin_amdgcn_s_setprio(0); \
-  }
-
-#ifndef MPCR_CB_SKIP
-#define MPCR_CB_SKIP 1  // capsule-box: skip the interior knots when no lane's minimum is inside (narrow_lane)
-#endif
-// instruction-count attribution builds (-DMPCR_STOP_AFTER=k, diagnostic only):
-// the step ends right after phase stamp k, so PMC differences between k and
-// the previous stop are that phase's instructions
-#ifdef MPCR_STOP_AFTER
-#define STOP_AT(k) \
-  if (MPCR_STOP_AFTER == (k)) continue;
-#else
-#define STOP_AT(k)
-#endif
-// sub-stamps inside the constraint-rows phase (-DMPCR_PROFILE -DMPCR_PROFILE_ROWS,
-// single-arm kernels: slots 23..25 are the dual-arm polyhedron manifold's):
-// 23 head, 24 equality / limit Jacobians, 25 contact Jacobians; the row
-// parameters are then what is left in slot 8
-#if defined(MPCR_PROFILE) && defined(MPCR_PROFILE_ROWS)
-#define ROWS_STAMP(i) STAMP(i)
-#else
-#define ROWS_STAMP(i)
-#endif
-
-// ---------------------------------------------------------------------------
-// wave helpers
-
-// Address spaces at the entry of a non-inlined device function: its pointer
-// arguments are generic, so without these the model reads, the LDS image and
-// the caller's contact arrays all go through flat instructions (which also
-// count against the LDS wait counter)
-// (device pass only: the host pass parses device bodies with other builtin signatures)
-#if defined(__HIP_DEVICE_COMPILE__)
-#define ASSUME_GLOBAL(p) __builtin_assume(!__builtin_amdgcn_is_shared((const void*)(p)) && \
-                                          !__builtin_amdgcn_is_private((const void*)(p)))
-#define ASSUME_LDS(p) __builtin_assume(__builtin_amdgcn_is_shared((const void*)(p)))
-#define ASSUME_PRIVATE(p) __builtin_assume(__builtin_amdgcn_is_private((const void*)(p)))
-#else
-#define ASSUME_GLOBAL(p)
-#define ASSUME_LDS(p)
-#define ASSUME_PRIVATE(p)
-#endif
-// the model pointer as a wave-uniform (SGPR) global pointer: a non-inlined
-// function receives it in VGPRs, and its field reads then become per-lane
-// vector loads instead of scalar ones
-__device__ __forceinline__ const MPCR_GMEM DevModel* uniform_model(const DevModel* p) {
-  const unsigned long long a = reinterpret_cast<unsigned long long>(p);
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-  return reinterpret_cast<const MPCR_GMEM DevModel*>(((unsigned long long)hi << 32) | lo);
-}
-
-// MPCR_STEP_TABLE: which phases of the single-arm kernels read the step table
-// (bit 0 kinematics, 1 motion subspaces, 2 constraint rows, 3 the load
-// records: one-level batched loads in place of dependent chains -- rows
-// phase, mass matrix, collision cull, narrow_lane's head, emit_contacts); 15
-// is the shipped build, the others attribute a change in results or time
-#ifndef MPCR_STEP_TABLE
-#define MPCR_STEP_TABLE 15
-#endif
-template <class S> constexpr bool kStepKin = !S::WIDE && (MPCR_STEP_TABLE & 1) != 0;
-template <class S> constexpr bool kStepDof = !S::WIDE && (MPCR_STEP_TABLE & 2) != 0;
-template <class S> constexpr bool kStepRow = !S::WIDE && (MPCR_STEP_TABLE & 4) != 0;
-template <class S> constexpr bool kStepLoad = !S::WIDE && (MPCR_STEP_TABLE & 8) != 0;
-// MPCR_LANE_WORK: which one-lane or repeated work of the single-arm step is
-// built in its cheaper form (bit 0 the pose cost's transcendental tail deferred
-// and spread over lanes, 1 the trees' centres of mass in one reduction, 2
-// Newton's first rows from the warm-start choice, 3 the line search's q0 at
-// alpha = 0 from Newton's cost).  Every built form sits behind
-// DEV_NO_LANE_WORK in the device model's flags (the environment's
-// MPCR_LANE_WORK=0 at engine creation, tests -- an on / off switch for all
-// items, not this mask): the former path stays reachable in the same build.
-// 15 is the shipped build; the others attribute a change in results or time
-// (tools/build_variant.py).
-#ifndef MPCR_LANE_WORK
-#define MPCR_LANE_WORK 15
-#endif
-template <class S> constexpr bool kLanePose = !S::WIDE && (MPCR_LANE_WORK & 1) != 0;
-template <class S> constexpr bool kLaneCom = !S::WIDE && (MPCR_LANE_WORK & 2) != 0;
-template <class S> constexpr bool kLaneJar = !S::WIDE && (MPCR_LANE_WORK & 4) != 0;
-template <class S> constexpr bool kLaneQ0 = !S::WIDE && (MPCR_LANE_WORK & 8) != 0;
-// The step table (step_table.h) behind the device model, and quad q (16
-// bytes: one dwordx4 load) of one of its records.  Single-arm kernels only.
-__device__ __forceinline__ const StepTable* step_table(const DevModel* m) {
-  return reinterpret_cast<const StepTable*>(m + 1);
-}
-// ... and the load records behind the table
-__device__ __forceinline__ const StepRecords* step_records(const DevModel* m) {
-  return reinterpret_cast<const StepRecords*>(step_table(m) + 1);
-}
-template <class R>
-__device__ __forceinline__ float4 recq(const R& r, int q) {
-  return reinterpret_cast<const float4*>(&r)[q];
-}
-
-__device__ __forceinline__ float rdlane(float v, int l) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
-}
-template <int CTRL>
-__device__ __forceinline__ float dppf(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false));
-}
-// full-wave sum, result uniform: DPP inside each 16-lane row (quad_perm
-// [1,0,3,2], [2,3,0,1], row_ror:4, row_ror:8), then the GCN row_bcast:15 /
-// row_bcast:31 steps carry the row sums into lane 63, one readlane.  No LDS
-// traffic (a __shfl_xor butterfly is 6 dependent ds_bpermute round trips).
-template <int CTRL, int ROWS>
-__device__ __forceinline__ float dppf_rows(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROWS, 0xF, false));
-}
-// the reference form, every step a builtin: the compiler folds the in-row
-// steps into v_add_f32_dpp but leaves each cross-row step as v_mov (old = 0),
-// v_mov_b32_dpp, v_add_f32 -- 11 VALU.  Kept for mpcr_selftest_reduce, which
-// holds every production form below to its bits.
-__device__ __forceinline__ float wsum_ref(float v) {
-  v += dppf<0xB1>(v);
-  v += dppf<0x4E>(v);
-  v += dppf<0x124>(v);
-  v += dppf<0x128>(v);
-  v += dppf_rows<0x142, 0xA>(v);  // row_bcast:15 into rows 1, 3
-  v += dppf_rows<0x143, 0xC>(v);  // row_bcast:31 into rows 2, 3
-  return rdlane(v, 63);
-}
-// the four in-row steps: lane 15 of each row ends with its row's sum
-__device__ __forceinline__ float wsum_row(float v) {
-  v += dppf<0xB1>(v);
-  v += dppf<0x4E>(v);
-  v += dppf<0x124>(v);
-  v += dppf<0x128>(v);
-  return v;
-}
-// The cross-row steps as one v_add_f32_dpp each (the rows a step does not
-// write keep their value where the reference adds 0 to it; only lane 63 is
-// read, and it sees the same sums in the same order): 7 VALU.  The hazard
-// recogniser does not look inside the string, so the two wait states between a
-// VALU write and a DPP read of the same register stand in it, and the one
-// ahead of the caller's v_readlane closes it.  wsum2 / wsum3 reduce
-// independent values side by side, each in its own six-step order: the other
-// values' adds stand where the s_nop would.
-#define MPCR_DPP15 " row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
-#define MPCR_DPP31 " row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"
-__device__ __forceinline__ float wsum(float v) {
-  v = wsum_row(v);
-  asm("s_nop 1\n\t"
-      "v_add_f32_dpp %0, %0, %0" MPCR_DPP15
-      "s_nop 1\n\t"
-      "v_add_f32_dpp %0, %0, %0" MPCR_DPP31
-      "s_nop 0"
-      : "+v"(v));
-  return rdlane(v, 63);
-}
-__device__ __forceinline__ void wsum2(float& a, float& b) {
-  a = wsum_row(a);
-  b = wsum_row(b);
-  asm("s_nop 1\n\t"
-      "v_add_f32_dpp %0, %0, %0" MPCR_DPP15
-      "v_add_f32_dpp %1, %1, %1" MPCR_DPP15
-      "s_nop 0\n\t"
-      "v_add_f32_dpp %0, %0, %0" MPCR_DPP31
-      "v_add_f32_dpp %1, %1, %1" MPCR_DPP31
-      "s_nop 0"
-      : "+v"(a), "+v"(b));
-  a = rdlane(a, 63);
-  b = rdlane(b, 63);
-}
-__device__ __forceinline__ void wsum3(float& a, float& b, float& c) {
-  a = wsum_row(a);
-  b = wsum_row(b);
-  c = wsum_row(c);
-  asm("s_nop 1\n\t"
-      "v_add_f32_dpp %0, %0, %0" MPCR_DPP15
-      "v_add_f32_dpp %1, %1, %1" MPCR_DPP15
-      "v_add_f32_dpp %2, %2, %2" MPCR_DPP15
-      "v_add_f32_dpp %0, %0, %0" MPCR_DPP31
-      "v_add_f32_dpp %1, %1, %1" MPCR_DPP31
-      "v_add_f32_dpp %2, %2, %2" MPCR_DPP31
-      "s_nop 0"
-      : "+v"(a), "+v"(b), "+v"(c));
-  a = rdlane(a, 63);
-  b = rdlane(b, 63);
-  c = rdlane(c, 63);
-}
-// Sum of a value that is +0 in every lane from W on (W = 16: one row, the
-// in-row steps alone; W = 32: two rows, the row_bcast:15 step joins them):
-// the steps left out add +0 in the reference.  Its one visible effect, -0
-// becoming +0 (a row whose lanes are all -0), is restored on the scalar unit,
-// so the value is wsum's bit for bit.  5 VALU (W = 16), 6 (W = 32).
-template <int W>
-__device__ __forceinline__ float wsum_lo(float v) {
-  static_assert(W == 16 || W == 32, "one or two rows");
-  v = wsum_row(v);
-  if constexpr (W == 32)
-    asm("s_nop 1\n\t"
-        "v_add_f32_dpp %0, %0, %0" MPCR_DPP15
-        "s_nop 0"
-        : "+v"(v));
-  const unsigned u = (unsigned)__builtin_amdgcn_readlane(__float_as_int(v), W - 1);
-  return __uint_as_float(u == 0x80000000u ? 0u : u);
-}
-__device__ __forceinline__ int lanes_below(unsigned long long mask) {
-  return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-}
-// exclusive prefix sum of small per-lane counts (0 .. 2^BITS - 1) by bit-plane ballots
-template <int BITS = 3>
-__device__ __forceinline__ int wscan_excl(int v, int& total) {
-  int pre = 0, tot = 0;
-#pragma unroll
-  for (int bit = 0; bit < BITS; bit++) {
-    const unsigned long long mk = __ballot((v >> bit) & 1);
-    pre += lanes_below(mk) << bit;
-    tot += __popcll(mk) << bit;
-  }
-  total = tot;
-  return pre;
-}
-// Phase barrier of one candidate's wave: orders its lanes' LDS / global
-// accesses (the workgroup-scope fences of __syncthreads, without s_barrier).
-// A one-wave workgroup measured the same with either (1.963 vs 1.964 ms on C3);
-// the two-wave variant (WPC = 2) needs the wave-local form, its waves meet at
-// block_sync() only.
-__device__ __forceinline__ void sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-__device__ __forceinline__ void block_sync() { __syncthreads(); }
-// __shfl behind a forceinline wrapper, for the kinematics' ancestor reads and
-// the constraint-row count: inlined with the kernel's other helpers, ahead of
-// the optimiser (called directly there, __shfl is inlined later and the
-// source-lane mask of a lane known to be in range is no longer folded away)
-template <class T>
-__device__ __forceinline__ T wshfl(T x, int src) { return __shfl(x, src); }
-
-// ---------------------------------------------------------------------------
-// small vector math
-
-__device__ __forceinline__ void qmul(float r[4], const float a[4], const float b[4]) {
-  float t0 = a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3];
-  float t1 = a[0] * b[1] + a[1] * b[0] + a[2] * b[3] - a[3] * b[2];
-  float t2 = a[0] * b[2] - a[1] * b[3] + a[2] * b[0] + a[3] * b[1];
-  float t3 = a[0] * b[3] + a[1] * b[2] - a[2] * b[1] + a[3] * b[0];
-  r[0] = t0; r[1] = t1; r[2] = t2; r[3] = t3;
-}
-__device__ __forceinline__ void q2m(float m[9], const float q[4]) {
-  float w = q[0], x = q[1], y = q[2], z = q[3];
-  m[0] = 1 - 2 * (y * y + z * z); m[1] = 2 * (x * y - w * z); m[2] = 2 * (x * z + w * y);
-  m[3] = 2 * (x * y + w * z); m[4] = 1 - 2 * (x * x + z * z); m[5] = 2 * (y * z - w * x);
-  m[6] = 2 * (x * z - w * y); m[7] = 2 * (y * z + w * x); m[8] = 1 - 2 * (x * x + y * y);
-}
-__device__ __forceinline__ void mv(float r[3], const float m[9], const float v[3]) {
-  float a = m[0] * v[0] + m[1] * v[1] + m[2] * v[2];
-  float b = m[3] * v[0] + m[4] * v[1] + m[5] * v[2];
-  float c = m[6] * v[0] + m[7] * v[1] + m[8] * v[2];
-  r[0] = a; r[1] = b; r[2] = c;
-}
-__device__ __forceinline__ void mtv(float r[3], const float m[9], const float v[3]) {
-  float a = m[0] * v[0] + m[3] * v[1] + m[6] * v[2];
-  float b = m[1] * v[0] + m[4] * v[1] + m[7] * v[2];
-  float c = m[2] * v[0] + m[5] * v[1] + m[8] * v[2];
-  r[0] = a; r[1] = b; r[2] = c;
-}
-__device__ __forceinline__ void cross(float r[3], const float a[3], const float b[3]) {
-  float x = a[1] * b[2] - a[2] * b[1];
-  float y = a[2] * b[0] - a[0] * b[2];
-  float z = a[0] * b[1] - a[1] * b[0];
-  r[0] = x; r[1] = y; r[2] = z;
-}
-__device__ __forceinline__ float dot3(const float a[3], const float b[3]) {
-  return a[0] * b[0] + a[1] * b[1] + a[2] * b[2];
-}
-__device__ __forceinline__ float clampf(float x, float lo, float hi) { return fminf(fmaxf(x, lo), hi); }
-// N-wide dot product of an LDS row (16-byte aligned) with an LDS vector
-template <int N>
-__device__ __forceinline__ float dotN(const float* row, const float* vec) {
-  const float4* r = reinterpret_cast<const float4*>(row);
-  const float4* v = reinterpret_cast<const float4*>(vec);
-  float acc = 0.f;
-#pragma unroll
-  for (int q = 0; q < N / 4; q++) {
-    const float4 a = r[q], x = v[q];
-    acc = fmaf(a.x, x.x, acc); acc = fmaf(a.y, x.y, acc); acc = fmaf(a.z, x.z, acc); acc = fmaf(a.w, x.w, acc);
-  }
-  return acc;
-}
-
-// spatial algebra (MuJoCo layout, see oracle/mpcr_oracle.c)
-__device__ __forceinline__ void mul_inert_vec(float r[6], const float* i, const float* v) {
-  r[0] = i[0] * v[0] + i[3] * v[1] + i[4] * v[2] - i[8] * v[4] + i[7] * v[5];
-  r[1] = i[3] * v[0] + i[1] * v[1] + i[5] * v[2] + i[8] * v[3] - i[6] * v[5];
-  r[2] = i[4] * v[0] + i[5] * v[1] + i[2] * v[2] - i[7] * v[3] + i[6] * v[4];
-  r[3] = i[8] * v[1] - i[7] * v[2] + i[9] * v[3];
-  r[4] = i[6] * v[2] - i[8] * v[0] + i[9] * v[4];
-  r[5] = i[7] * v[0] - i[6] * v[1] + i[9] * v[5];
-}
-__device__ __forceinline__ void cross_motion(float r[6], const float v[6], const float u[6]) {
-  float a[3], b[3], c[3];
-  cross(a, v, u);
-  cross(b, v, u + 3);
-  cross(c, v + 3, u);
-  r[0] = a[0]; r[1] = a[1]; r[2] = a[2];
-  r[3] = b[0] + c[0]; r[4] = b[1] + c[1]; r[5] = b[2] + c[2];
-}
-__device__ __forceinline__ void cross_force(float r[6], const float v[6], const float f[6]) {
-  float a[3], b[3], c[3];
-  cross(a, v, f);
-  cross(b, v + 3, f + 3);
-  cross(c, v, f + 3);
-  r[0] = a[0] + b[0]; r[1] = a[1] + b[1]; r[2] = a[2] + b[2];
-  r[3] = c[0]; r[4] = c[1]; r[5] = c[2];
-}
-
-// ---------------------------------------------------------------------------
-// dense SPD solve, row-per-lane in registers.  Lane i (< DX_NV) holds row i
-// of A in a[]; rows >= n must be identity rows.  On return a[] holds row i of
-// the lower Cholesky factor.  x = A^-1 b for b held one value per lane.
-
-// All DX_NV pivots run even when nv is smaller: a run-time exit inside the
-// unrolled chain breaks it into blocks the scheduler cannot overlap
-// (measured 4.07 -> 4.94 ms), while the padded pivots cost 2/16 of it.
-template <int N>
-__device__ __forceinline__ void chol_rows(float (&a)[N], int lane) {
-#pragma unroll
-  for (int k = 0; k < N; k++) {
-    float dkk = sqrtf(fmaxf(rdlane(a[k], k), kMinVal));
-    float lik = lane == k ? dkk : (lane > k ? a[k] / dkk : 0.f);
-    a[k] = lik;
-#pragma unroll
-    for (int j = k + 1; j < N; j++) {
-      float ljk = rdlane(lik, j);
-      a[j] = fmaf(-lik, ljk, a[j]);
-    }
-  }
-}
-
-// x = L^-T L^-1 b with lane i holding row i of L in l[].  Forward pass: lane
-// k finalises y_k, one v_readlane broadcasts it, every lane updates its own
-// accumulator with its own register l[k].  For the backward pass each lane
-// needs its COLUMN of L: the rows are scattered transposed to the LDS scratch
-// Lt[DX_NV][LDL] once, each lane reads its column back with 4 ds_read_b128,
-// and the same broadcast chain runs backwards.  32 readlanes per solve.
-// Returns x[lane].  Must be called by all lanes (one barrier).
-template <int N, int LDL>
-__device__ __forceinline__ float chol_solve(const float (&l)[N], float b, int lane, float* Lt) {
-  if (lane < N) {
-#pragma unroll
-    for (int j = 0; j < N; j++) Lt[j * LDL + lane] = l[j];
-  }
-  float acc = b, y = 0.f;
-#pragma unroll
-  for (int k = 0; k < N; k++) {
-    const float yk = rdlane(acc, k) / rdlane(l[k], k);
-    if (lane > k) acc = fmaf(-l[k], yk, acc);
-    if (lane == k) y = yk;
-  }
-  sync();
-  float lt[N];
-  {
-    const float4* col = reinterpret_cast<const float4*>(Lt + (lane < N ? lane : 0) * LDL);
-#pragma unroll
-    for (int q = 0; q < N / 4; q++) {
-      const float4 v = col[q];
-      lt[4 * q] = v.x; lt[4 * q + 1] = v.y; lt[4 * q + 2] = v.z; lt[4 * q + 3] = v.w;
-    }
-  }
-  float x = 0.f;
-  acc = y;
-#pragma unroll
-  for (int k = N - 1; k >= 0; k--) {
-    const float xk = rdlane(acc, k) / rdlane(l[k], k);
-    if (lane < k) acc = fmaf(-lt[k], xk, acc);
-    if (lane == k) x = xk;
-  }
-  sync();
-  return x;
-}
-
-// The same factorisation and solve for N = 16 (narrow variant) with DPP row
-// broadcasts instead of v_readlane: row_newbcast:j hands lane j's value to
-// every lane of its 16-lane row, and as the src0 modifier of v_fmac_f32 it
-// makes each (k, j) update of the right-looking factorisation ONE VALU
-// instruction (readlane + fma before, plus the SGPR hazards).  Lanes 16..63
-// run the same code on their own rows and their results are ignored.
-template <int J>
-__device__ __forceinline__ float rbc(float v) {
-  return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x150 + J, 0xF, 0xF, true));
-}
-// acc -= bcast_J(src) * own.  NOP: src was just written by a VALU op (DPP
-// reads need 2 wait states; the compiler does not track them in inline asm)
-template <int J, bool NOP>
-__device__ __forceinline__ void fnmac_bc(float& acc, float src, float own) {
-  if constexpr (NOP)
-    asm("s_nop 1\n\tv_fmac_f32_dpp %0, -%1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf"
-        : "+v"(acc) : "v"(src), "v"(own), "n"(J));
-  else
-    asm("v_fmac_f32_dpp %0, -%1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf"
-        : "+v"(acc) : "v"(src), "v"(own), "n"(J));
-}
-template <int K, int J>
-struct Chol16Upd {  // a[j] -= l[j][k] * l[i][k] for j = J..15
-  static __device__ __forceinline__ void run(float (&a)[16], float lik) {
-    fnmac_bc<J, J == K + 1>(a[J], lik, lik);
-    Chol16Upd<K, J + 1>::run(a, lik);
-  }
-};
-template <int K>
-struct Chol16Upd<K, 16> {
-  static __device__ __forceinline__ void run(float (&)[16], float) {}
-};
-// The factor is kept with a ZERO diagonal: l[i][i] lives only as its inverse
-// in dinv (lane i).  The sweeps then leave lane K's accumulator alone when
-// they broadcast its value, and read every result off at the end (acc * dinv)
-// instead of capturing it with a per-step select.
-template <int K>
-struct Chol16 {  // column K; dinv collects 1 / l[i][i] at lane i
-  static __device__ __forceinline__ void run(float (&a)[16], float& dinv, int lane) {
-    const float dkk = sqrtf(fmaxf(rbc<K>(a[K]), kMinVal));
-    const float inv = 1.f / dkk;
-    const float lik = lane > K ? a[K] * inv : 0.f;
-    a[K] = lik;
-    dinv = lane == K ? inv : dinv;
-    Chol16Upd<K, K + 1>::run(a, lik);
-    Chol16<K + 1>::run(a, dinv, lane);
-  }
-};
-template <>
-struct Chol16<16> {
-  static __device__ __forceinline__ void run(float (&)[16], float&, int) {}
-};
-// forward (L y = b) / backward (L^T x = y) sweeps: lane K's value is final
-// at step K, t = acc / l_KK, and one fused DPP FMA hands it to the other
-// lanes' updates (lanes already final and lane K see zero coefficients: l is
-// triangular with a zero diagonal); the results are acc * dinv afterwards
-template <int K, int STEP>
-struct Sweep16 {
-  static __device__ __forceinline__ void run(const float (&c)[16], float& acc, float dinv) {
-    const float t = acc * dinv;
-    fnmac_bc<K, true>(acc, t, c[K]);
-    Sweep16<K + STEP, STEP>::run(c, acc, dinv);
-  }
-};
-template <int STEP>
-struct Sweep16<16, STEP> {
-  static __device__ __forceinline__ void run(const float (&)[16], float&, float) {}
-};
-template <int STEP>
-struct Sweep16<-1, STEP> {
-  static __device__ __forceinline__ void run(const float (&)[16], float&, float) {}
-};
-// The solves launder their lane argument: the lane compares inside are
-// re-derived (one v_cmp each) instead of being hoisted into spilled SGPR pairs
-__device__ __forceinline__ void chol16(float (&a)[16], float& dinv, int lane) {
-  asm volatile("" : "+v"(lane));
-  dinv = 0.f;
-  Chol16<0>::run(a, dinv, lane);
-}
-// Blocked variant for block-diagonal systems (the mass matrix is block
-// diagonal by kinematic tree): tree t's <= 8 dofs are rows of lanes 16 t ..
-// 16 t + 7, and row_newbcast:K broadcasts each tree's K-th row to its own
-// lanes, so all trees factor in ONE 8-column chain (36 fused updates instead
-// of 120) -- the same operations per block as the dense factorisation
-// (off-block entries are exact zeros there), in the same order.
-template <int N, int K, int J>
-struct CholNUpd {
-  static __device__ __forceinline__ void run(float (&a)[N], float lik) {
-    fnmac_bc<J, J == K + 1>(a[J], lik, lik);
-    CholNUpd<N, K, J + 1>::run(a, lik);
-  }
-};
-template <int N, int K>
-struct CholNUpd<N, K, N> {
-  static __device__ __forceinline__ void run(float (&)[N], float) {}
-};
-template <int N, int K>
-struct CholN {  // lr: the lane's row within its 16-lane DPP row
-  static __device__ __forceinline__ void run(float (&a)[N], float& dinv, int lr) {
-    const float dkk = sqrtf(fmaxf(rbc<K>(a[K]), kMinVal));
-    const float inv = 1.f / dkk;
-    const float lik = lr > K ? a[K] * inv : 0.f;
-    a[K] = lik;
-    dinv = lr == K ? inv : dinv;
-    CholNUpd<N, K, K + 1>::run(a, lik);
-    CholN<N, K + 1>::run(a, dinv, lr);
-  }
-};
-template <int N>
-struct CholN<N, N> {
-  static __device__ __forceinline__ void run(float (&)[N], float&, int) {}
-};
-template <int N, int K, int STEP>
-struct SweepN {
-  static __device__ __forceinline__ void run(const float (&c)[N], float& acc, float dinv) {
-    const float t = acc * dinv;
-    fnmac_bc<K, true>(acc, t, c[K]);
-    SweepN<N, K + STEP, STEP>::run(c, acc, dinv);
-  }
-};
-template <int N, int STEP>
-struct SweepN<N, N, STEP> {
-  static __device__ __forceinline__ void run(const float (&)[N], float&, float) {}
-};
-template <int N, int STEP>
-struct SweepN<N, -1, STEP> {
-  static __device__ __forceinline__ void run(const float (&)[N], float&, float) {}
-};
-// x = A^-1 b for a symmetric A that is block diagonal by kinematic tree (tree
-// t's <= N dofs on lanes 16 t ..), elem(d, dj) = A[d][dj]; b and x are
-// dof-indexed LDS vectors (x may alias b).  Lt: 4 N^2-float LDS scratch (it
-// may alias A's storage: every element is read before the first write).  Must
-// be called by all lanes (two barriers).
-// (split in two for a factor computed ahead of its solve, possibly on
-// another wave: blocked_factor, then blocked_sweep -- the same operations)
-template <int N, class F>
-__device__ __forceinline__ void blocked_factor(const DevModel* __restrict__ m, F&& elem, int lane, float (&a)[N],
-                                               float& dinv) {
-  static_assert(N == 8 || N == 16, "blocked Cholesky width");
-  asm volatile("" : "+v"(lane));
-  const int lr = lane & 15, lb = lane & ~15;
-  const int d = m->blane_dof[lane];
-#pragma unroll
-  for (int j = 0; j < N; j++) {
-    const int dj = m->blane_dof[lb + j];
-    a[j] = (d >= 0 && dj >= 0) ? elem(d, dj) : (j == lr ? 1.f : 0.f);
-  }
-  dinv = 0.f;
-  CholN<N, 0>::run(a, dinv, lr);
-}
-template <int N>
-__device__ __forceinline__ void blocked_sweep(const DevModel* __restrict__ m, const float (&a)[N], float dinv,
-                                              const float* bv, float* xv, int lane, float* Lt) {
-  asm volatile("" : "+v"(lane));
-  const int lr = lane & 15, t = lane >> 4;
-  const int d = m->blane_dof[lane];
-  float acc = d >= 0 ? bv[d] : 0.f;
-  SweepN<N, 0, 1>::run(a, acc, dinv);
-  const float y = acc * dinv;
-  if (lr < N) {
-#pragma unroll
-    for (int j = 0; j < N; j++) Lt[t * N * N + j * N + lr] = a[j];
-  }
-  sync();
-  float lt[N];
-  {
-    const float4* col = reinterpret_cast<const float4*>(Lt + t * N * N + (lr & (N - 1)) * N);
-#pragma unroll
-    for (int q = 0; q < N / 4; q++) {
-      const float4 v = col[q];
-      lt[4 * q] = v.x; lt[4 * q + 1] = v.y; lt[4 * q + 2] = v.z; lt[4 * q + 3] = v.w;
-    }
-  }
-  acc = y;
-  SweepN<N, N - 1, -1>::run(lt, acc, dinv);
-  const float x = acc * dinv;
-  sync();
-  if (d >= 0) xv[d] = x;
-}
-template <int N, class F>
-__device__ __forceinline__ void blocked_solve(const DevModel* __restrict__ m, F&& elem, const float* bv, float* xv,
-                                              int lane, float* Lt) {
-  float a[N], dinv;
-  blocked_factor<N>(m, elem, lane, a, dinv);
-  blocked_sweep<N>(m, a, dinv, bv, xv, lane, Lt);
-}
-// the blocked (per-tree) Cholesky for M and uncoupled Newton Hessians, for a
-// kernel variant of NVW dofs: 8-wide chains in the
-// narrow kernel (trees <= 8 dofs), 16-wide in the dual-arm one (trees <= 16)
-template <int NVW>
-__device__ __forceinline__ bool blk_usable(const DevModel* __restrict__ m) {
-  return NVW == 16 ? m->blk_n == 8 : m->blk_n != 0;
-}
-template <int NVW, class F>
-__device__ __forceinline__ void blk_solve(const DevModel* __restrict__ m, F&& elem, const float* bv, float* xv,
-                                          int lane, float* Lt) {
-  blocked_solve<NVW == 16 ? 8 : 16>(m, elem, bv, xv, lane, Lt);
-}
-
-// x = L^-T L^-1 b (lane i: row i of L in l[]); Lt: LDS transpose scratch
-template <int LDL>
-__device__ __forceinline__ float chol16_solve(const float (&l)[16], float dinv, float b, int lane, float* Lt) {
-  asm volatile("" : "+v"(lane));
-  if (lane < 16) {
-#pragma unroll
-    for (int j = 0; j < 16; j++) Lt[j * LDL + lane] = l[j];
-  }
-  float acc = b;
-  Sweep16<0, 1>::run(l, acc, dinv);
-  const float y = acc * dinv;
-  sync();
-  float lt[16];
-  {
-    const float4* col = reinterpret_cast<const float4*>(Lt + (lane & 15) * LDL);
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-      const float4 v = col[q];
-      lt[4 * q] = v.x; lt[4 * q + 1] = v.y; lt[4 * q + 2] = v.z; lt[4 * q + 3] = v.w;
-    }
-  }
-  acc = y;
-  Sweep16<15, -1>::run(lt, acc, dinv);
-  const float x = acc * dinv;
-  sync();
-  return x;
-}
-
-// ---------------------------------------------------------------------------
-// narrow phase (contact definitions identical to the oracle's)
-
-__device__ __forceinline__ void seg_seg(const float p1[3], const float d1[3], const float p2[3], const float d2[3],
-                                        float* sc, float* tc) {
-  float r[3] = {p1[0] - p2[0], p1[1] - p2[1], p1[2] - p2[2]};
-  float a = dot3(d1, d1), e = dot3(d2, d2), f = dot3(d2, r);
-  float s, t;
-  if (a <= kMinVal && e <= kMinVal) { *sc = 0; *tc = 0; return; }
-  if (a <= kMinVal) {
-    s = 0; t = clampf(f / e, 0, 1);
-  } else {
-    float c = dot3(d1, r);
-    if (e <= kMinVal) {
-      t = 0; s = clampf(-c / a, 0, 1);
-    } else {
-      float b = dot3(d1, d2), den = a * e - b * b;
-      s = den > 1e-12f * a * e ? clampf((b * f - c * e) / den, 0, 1) : 0.f;
-      t = (b * s + f) / e;
-      if (t < 0) { t = 0; s = clampf(-c / a, 0, 1); }
-      else if (t > 1) { t = 1; s = clampf((b - c) / a, 0, 1); }
-    }
-  }
-  *sc = s; *tc = t;
-}
-
-__device__ __forceinline__ float point_box(const float p[3], const float h[3], float nl[3], float q[3]) {
-  float out2 = 0, o[3];
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    q[k] = clampf(p[k], -h[k], h[k]);
-    o[k] = q[k] - p[k];
-    out2 += o[k] * o[k];
-  }
-  if (out2 > 0) {
-    const float l = sqrtf(out2);
-#pragma unroll
-    for (int k = 0; k < 3; k++) nl[k] = o[k] / l;
-    return l;
-  }
-  // inside: the deepest face is argmax_k |p_k| - h_k; ties within 1 um go to
-  // the lower axis and a point on the box's mid-plane to the + face (the
-  // oracle's point_box rule)
-  const float g0 = fabsf(p[0]) - h[0], g1 = fabsf(p[1]) - h[1], g2 = fabsf(p[2]) - h[2];
-  int best = 0;
-  float g = g0;
-  if (g1 > g + 1e-6f) { g = g1; best = 1; }
-  if (g2 > g + 1e-6f) { g = g2; best = 2; }
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    const float sg = p[k] >= -1e-6f ? 1.f : -1.f;
-    nl[k] = k == best ? -sg : 0.f;
-    q[k] = k == best ? sg * h[k] : p[k];
-  }
-  return g;
-}
-
-// ---------------------------------------------------------------------------
-// general convex narrow phase (dual-arm class only): support functions of
-// sphere / capsule / cylinder / box / mesh convex hull and Minkowski portal
-// refinement, the same algorithm and tolerances as the oracle's mpr()
-// (libccd MPR; one penetration contact per pair)
-
-// gap tolerance (oracle MPR_TOL): MuJoCo's ccd_tolerance (round 3; 1e-5 before)
-constexpr float kMprTol = 1e-6f;
-constexpr int kMprIter = 50;  // MuJoCo's ccd_iterations cap
-constexpr float kMprEps = 1.1920929e-07f;
-__device__ __forceinline__ bool mpr_zero(float x) { return fabsf(x) < kMprEps; }
-
-// Ties in the support mapping resolve as in the oracle's support(): a box /
-// capsule / cylinder axis with |l_k| < kSupTie |l| contributes 0 (its face or
-// segment centre: MuJoCo's mju_sign(0) = 0, widened to the fp32 rounding of a
-// component that is exactly zero in fp64), and the hull climb moves to the
-// neighbour that beats the current vertex the most (strictly; kSupBand > 0
-// would make it the first within that many metres).
-constexpr float kSupTie = 1e-6f;  // < 0: MuJoCo's mju_sign (only an exact zero is a tie)
-// hull support ties (round 6, oracle HULL_TIE): vertices within this many
-// metres of the climb's end are tied with it (hull_tie); 0 = the plain climb
-constexpr float kHullTie = 1e-7f;
-constexpr float kSupBand = 0.f;  // MuJoCo's strict climb (round 3; 1e-5 before)
-__device__ __forceinline__ float tie_sign(float lk, float ln) {
-  if (kSupTie < 0.f) return lk > 0.f ? 1.f : (lk < 0.f ? -1.f : 0.f);
-  return fabsf(lk) < kSupTie * ln ? 0.f : (lk >= 0.f ? 1.f : -1.f);
-}
-
-// examine the neighbours of vertex v along l (unit): one must beat bn (the
-// current vertex + band, then the chosen neighbour + band); -1 if none.
-// Neighbour records carry (index | degree << 16), so the next round's loads
-// need no lookup: the first 8 neighbours (90 % of hull vertices have <= 8)
-// sit in v's NaN-padded head block (addressed by v alone, 8 independent
-// loads), the rest of a longer list in hull_adjv after one hull_info load.
-// Hull support ties (round 6, the oracle's hull_tie): a round also keeps
-// the lowest-index neighbour within kHullTie of the current vertex (tkey:
-// index << 16 | degree, the record's w bits rotated; ~0u: none).  The round
-// that ends the climb thus names the climb end's lowest tied neighbour, and
-// sup_finish walks on to it while one is lower (tie_round).
-__device__ __forceinline__ void climb_scan(const float4 (&w)[8], const float l[3], float& bn, float4& hv, int& nb,
-                                           float lo, uint32_t& tkey) {
-#pragma unroll
-  for (int j = 0; j < 8; j++) {
-    const float du = w[j].x * l[0] + w[j].y * l[1] + w[j].z * l[2];  // NaN pads never win
-    const uint32_t wb = __float_as_uint(w[j].w);
-    if (du >= lo) tkey = min(tkey, __builtin_amdgcn_alignbit(wb, wb, 16));
-    if (du > bn) { bn = du + kSupBand; nb = __float_as_int(w[j].w); hv = w[j]; }
-  }
-}
-__device__ __forceinline__ int climb_round(const DevModel* __restrict__ m, int v, int deg, const float l[3],
-                                           float& best, float4& hv, uint32_t& tkey) {
-  int nb = -1;
-  float bn = best + kSupBand;
-  const float lo = best - kHullTie;
-  tkey = ~0u;
-  float4 w[8];
-#pragma unroll
-  for (int j = 0; j < 8; j++) w[j] = m->hull_head[(size_t)v * 8 + j];
-  climb_scan(w, l, bn, hv, nb, lo, tkey);
-  if (deg > 8) {
-    const int a = m->hull_info[v].x, last = a + deg - 1;
-    for (int k0 = a + 8; k0 <= last; k0 += 8) {
-#pragma unroll
-      for (int j = 0; j < 8; j++) w[j] = m->hull_adjv[min(k0 + j, last)];  // repeats of the last never win twice
-      climb_scan(w, l, bn, hv, nb, lo, tkey);
-    }
-  }
-  if (nb >= 0) best = bn - kSupBand;
-  return nb;
-}
-
-// The support of a hull on a tie.  When the direction is normal (to
-// ~kHullTie) to an edge or a face of the hull, every vertex of it is a
-// maximum, and which one the climb reaches depends on where it started (the
-// start table's cell, the pair's hint) and on the last bits of the dot
-// products (fp32 and fp64 pick differently).  From the climb's end v the
-// support walks to the lowest-index neighbour within kHullTie of v's value
-// while that neighbour's index is lower: the tie's lowest index from
-// whichever of its vertices the climb reached (the oracle's hull_tie), so a
-// start table's resolution stays a performance choice, not a parity change
-// (tests/test_hull_ties.py).  One walk round, out of line with scalar
-// arguments (its call's spills stay on this path; inlined, or folded into
-// the climb loop, the walk cost the hot climb registers or time): v's
-// coordinates and the key of its lowest tied neighbour.
-struct TieStep { float x, y, z; uint32_t tkey; };  // v's coordinates, its lowest tied neighbour's key
-__device__ __noinline__ TieStep tie_round(const DevModel* __restrict__ m, int v, int deg, float lo, float l0,
-                                          float l1, float l2) {
-  uint32_t tkey = ~0u;
-  const float l[3] = {l0, l1, l2};
-  float4 w[8];
-  const float4 x = m->hull_vert[v];
-#pragma unroll
-  for (int j = 0; j < 8; j++) w[j] = m->hull_head[(size_t)v * 8 + j];  // the head block's loads in flight together
-  float bn = 3e38f;  // (no neighbour is climbed to)
-  float4 hv;
-  int nb;
-  climb_scan(w, l, bn, hv, nb, lo, tkey);
-  if (deg > 8) {
-    const int a = m->hull_info[v].x, last = a + deg - 1;
-    for (int k0 = a + 8; k0 <= last; k0 += 8) {
-#pragma unroll
-      for (int j = 0; j < 8; j++) w[j] = m->hull_adjv[min(k0 + j, last)];
-      climb_scan(w, l, bn, hv, nb, lo, tkey);
-    }
-  }
-  return TieStep{x.x, x.y, x.z, tkey};
-}
-
-// cube-map cell of a local direction (the engine's start table order,
-// engine.hip hull_start_table; oracle lut_cell): major axis (lowest on ties), its sign, the other two components
-// (cyclic order) over |l_axis| in MPCR_LUT_R bins
-template <int R = MPCR_LUT_R>
-__device__ __forceinline__ int lut_cell(const float l[3]) {
-  const float a0 = fabsf(l[0]), a1 = fabsf(l[1]), a2 = fabsf(l[2]);
-  const int ax = (a0 >= a1 && a0 >= a2) ? 0 : (a1 >= a2 ? 1 : 2);
-  const float lax = ax == 0 ? l[0] : (ax == 1 ? l[1] : l[2]);
-  const float lu = ax == 0 ? l[1] : (ax == 1 ? l[2] : l[0]);
-  const float lv = ax == 0 ? l[2] : (ax == 1 ? l[0] : l[1]);
-  const float la = fabsf(lax);
-  if (!(la > 0.f)) return 0;
-  const int iu = min(max((int)floorf((lu / la + 1.f) * 0.5f * R), 0), R - 1);
-  const int iv = min(max((int)floorf((lv / la + 1.f) * 0.5f * R), 0), R - 1);
-  return (2 * ax + (lax < 0.f ? 1 : 0)) * R * R + iu * R + iv;
-}
-
-// hint: hull vertex the previous query on this geom ended at (-1: none); the
-// climb starts there (successive MPR directions are close)
-// org (nullable): the result relative to org, with (geom centre - org)
-// formed first -- MPR works relative to the second geom's centre, so the
-// Minkowski points carry cm-scale rounding instead of world-scale (1 m) rounding
-//
-// A query runs in two parts so a caller can put two of them in flight
-// together (MPR's support pair: round 5): sup_start issues the first loads
-// of a mesh query -- the start table cell of the direction and the hint
-// vertex, independent of each other (the hint's index is clamped to the
-// hull: a query without one loads the hull's first vertex and ignores it) --
-// and sup_finish consumes them: the hint if it beats the table vertex, then
-// the climb (none from an exact cell, engine.hip).  Same values and
-// comparisons as one call, so bitwise the same support point.
-struct SupQ {
-  float l[3], lu[3], ln;
-  float4 hv, hh;
-  int type, la;
-};
-// a geom's per-query constants (type, table, first hull vertex), loaded once
-// per MPR run instead of in front of every support query
-struct GeomQ { int type, la, h0; };
-__device__ __forceinline__ GeomQ geom_q(const DevModel* __restrict__ m, int g) {
-  GeomQ q{m->geom_type[g], m->geom_lutadr[g], m->geom_hulladr[g]};
-  asm volatile("" : "+v"(q.type), "+v"(q.la), "+v"(q.h0));  // kept in registers, not re-loaded per query
-  return q;
-}
-template <class S>
-__device__ __forceinline__ void sup_start(const DevModel* __restrict__ m, const S& s, int g, const float dir[3],
-                                          int hint, SupQ& q, const GeomQ* gq = nullptr) {
-  const float* R = s.gxmat[g];
-  mtv(q.l, R, dir);
-  q.ln = sqrtf(dot3(q.l, q.l));
-  q.type = gq ? gq->type : m->geom_type[g];
-  if (q.type == 7) {
-    const float il = q.ln > 0.f ? 1.f / q.ln : 0.f;
-    q.lu[0] = q.l[0] * il; q.lu[1] = q.l[1] * il; q.lu[2] = q.l[2] * il;
-    q.la = gq ? gq->la : m->geom_lutadr[g];
-    const int h0 = gq ? gq->h0 : m->geom_hulladr[g];
-    q.hv = q.la >= 0 ? m->hull_lut[q.la + lut_cell(q.l)] : m->hull_vert[h0];
-    q.hh = m->hull_vert[hint >= 0 ? hint : h0];
-  }
-}
-// MPCR_SAT_TIES 1: the SAT's value-only queries walk the ties too (A/B of
-// the start independence, tools/scramble_check.py)
-#ifndef MPCR_SAT_TIES
-#define MPCR_SAT_TIES 0
-#endif
-template <class S>
-// ties = false: the caller uses the support value only (the SAT's
-// separations), which any tied vertex gives to within kHullTie
-__device__ __forceinline__ void sup_finish(const DevModel* __restrict__ m, const S& s, int g, SupQ& q, float out[3],
-                                           int& hint, const float* org, bool ties = true) {
-  const float* R = s.gxmat[g];
-  const float* sz = m->geom_size[g];
-  const float* l = q.l;
-  const float ln = q.ln;
-  const int type = q.type;
-  float p[3] = {0.f, 0.f, 0.f};
-  if (type == 2 || type == 3) {  // sphere, capsule
-    if (ln > 0.f) { p[0] = sz[0] * l[0] / ln; p[1] = sz[0] * l[1] / ln; p[2] = sz[0] * l[2] / ln; }
-    if (type == 3) p[2] += tie_sign(l[2], ln) * sz[1];
-  } else if (type == 5) {  // cylinder
-    const float r = sqrtf(l[0] * l[0] + l[1] * l[1]);
-    if (r > fmaxf(kSupTie, 0.f) * ln) { p[0] = sz[0] * l[0] / r; p[1] = sz[0] * l[1] / r; }
-    p[2] = tie_sign(l[2], ln) * sz[1];
-  } else if (type == 6) {  // box
-    p[0] = tie_sign(l[0], ln) * sz[0];
-    p[1] = tie_sign(l[1], ln) * sz[1];
-    p[2] = tie_sign(l[2], ln) * sz[2];
-  } else if (type == 7) {  // mesh hull: steepest ascent on the vertex graph
-    // start: the table vertex of l's cube-map cell, or the hint (where the
-    // previous query on this pair ended) when it beats that by the band
-    const float* lu = q.lu;
-    float4 hv = q.hv;
-    const int hw = __float_as_int(hv.w);
-    int v = q.la >= 0 ? (hw & 0x7fff) : m->geom_hulladr[g];
-    if (!(q.la >= 0 && (hw & 0x8000))) {  // not an exact cell (engine.hip): the hint, then the climb
-      int deg = q.la >= 0 ? (hw >> 16) : hw;
-      float best = hv.x * lu[0] + hv.y * lu[1] + hv.z * lu[2];
-      if (hint >= 0) {
-        const float4 hh = q.hh;
-        const float bh = hh.x * lu[0] + hh.y * lu[1] + hh.z * lu[2];
-        // (on equal values the hint: after a tie walk it is the tie's lowest
-        // index, so the climb then ends where it starts, with no walk)
-        if (bh >= best + kSupBand) { v = hint; hv = hh; deg = __float_as_int(hh.w); best = bh; }
-      }
-      uint32_t tkey = ~0u;
-      for (int guard = 0; guard < 4096; guard++) {
-        PROF_COUNT(m, 19);
-        const int nb = climb_round(m, v, deg, lu, best, hv, tkey);
-        if (nb < 0) break;
-        v = nb & 0xffff;
-        deg = nb >> 16;
-      }
-      if (kHullTie > 0.f && ties && (int)(tkey >> 16) < v) {  // a lower-index tied neighbour: walk (hull_tie)
-        const float lo = best - kHullTie;
-        for (int guard = 0; guard < 64 && (int)(tkey >> 16) < v; guard++) {
-          v = tkey >> 16;
-          const TieStep ts = tie_round(m, v, tkey & 0xffff, lo, lu[0], lu[1], lu[2]);
-          hv.x = ts.x; hv.y = ts.y; hv.z = ts.z;
-          tkey = ts.tkey;
-        }
-      }
-    }
-    p[0] = hv.x; p[1] = hv.y; p[2] = hv.z;
-    hint = v;
-  }
-  mv(out, R, p);
-  if (org) {
-    out[0] += s.gxpos[g][0] - org[0]; out[1] += s.gxpos[g][1] - org[1]; out[2] += s.gxpos[g][2] - org[2];
-  } else {
-    out[0] += s.gxpos[g][0]; out[1] += s.gxpos[g][1]; out[2] += s.gxpos[g][2];
-  }
-}
-template <class S>
-__device__ __forceinline__ void support_geom(const DevModel* __restrict__ m, const S& s, int g, const float dir[3],
-                                             float out[3], int& hint, const float* org = nullptr, bool ties = true) {
-  SupQ q;
-  sup_start(m, s, g, dir, hint, q);
-  sup_finish(m, s, g, q, out, hint, org, ties);
-}
-
-struct MprPt { float v[3], a[3], b[3]; };
-
-template <class S>
-__device__ __forceinline__ void mpr_support(const DevModel* __restrict__ m, const S& s, int g1, int g2,
-                                            const float dir[3], MprPt& o, int (&hint)[2], float* trace = nullptr,
-                                            const GeomQ* gq = nullptr) {
-  const float nd[3] = {-dir[0], -dir[1], -dir[2]};
-  SupQ q1, q2;  // both queries' first loads in flight together
-  PROF_COUNT(m, 20);
-  sup_start(m, s, g1, dir, hint[0], q1, gq);
-  sup_start(m, s, g2, nd, hint[1], q2, gq ? gq + 1 : nullptr);
-  sup_finish(m, s, g1, q1, o.a, hint[0], s.gxpos[g2]);  // relative to g2's centre
-  sup_finish(m, s, g2, q2, o.b, hint[1], s.gxpos[g2]);
-  o.v[0] = o.a[0] - o.b[0]; o.v[1] = o.a[1] - o.b[1]; o.v[2] = o.a[2] - o.b[2];
-  if (trace) {
-    const int q = (int)trace[47];
-    if (q < 32) { trace[48 + 2 * q] = (float)hint[0]; trace[49 + 2 * q] = (float)hint[1]; trace[47] = (float)(q + 1); }
-  }
-}
-__device__ __forceinline__ void nrm3(float v[3]) {
-  const float n = sqrtf(dot3(v, v));
-  if (n > 0.f) { v[0] /= n; v[1] /= n; v[2] /= n; }
-}
-__device__ __forceinline__ void mpr_dir(const MprPt p[4], float dir[3]) {
-  float a[3] = {p[2].v[0] - p[1].v[0], p[2].v[1] - p[1].v[1], p[2].v[2] - p[1].v[2]};
-  float b[3] = {p[3].v[0] - p[1].v[0], p[3].v[1] - p[1].v[1], p[3].v[2] - p[1].v[2]};
-  cross(dir, a, b);
-  nrm3(dir);
-}
-__device__ __forceinline__ bool mpr_reach(const MprPt p[4], const MprPt& v4, const float dir[3], float tol) {
-  const float d4 = dot3(v4.v, dir);
-  const float t = fminf(d4 - dot3(p[1].v, dir), fminf(d4 - dot3(p[2].v, dir), d4 - dot3(p[3].v, dir)));
-  return t < tol;
-}
-__device__ __forceinline__ void mpr_expand(MprPt p[4], const MprPt& v4) {
-  float x[3];
-  cross(x, v4.v, p[0].v);
-  if (dot3(p[1].v, x) > 0.f) {
-    if (dot3(p[2].v, x) > 0.f) p[1] = v4; else p[3] = v4;
-  } else {
-    if (dot3(p[3].v, x) > 0.f) p[2] = v4; else p[1] = v4;
-  }
-}
-__device__ __forceinline__ void tri_closest(const float a[3], const float b[3], const float c[3], float out[3]) {
-  float ab[3], ac[3], ap[3], bp[3], cp[3];
-#pragma unroll
-  for (int k = 0; k < 3; k++) { ab[k] = b[k] - a[k]; ac[k] = c[k] - a[k]; ap[k] = -a[k]; bp[k] = -b[k]; cp[k] = -c[k]; }
-  const float d1 = dot3(ab, ap), d2 = dot3(ac, ap);
-  if (d1 <= 0.f && d2 <= 0.f) { out[0] = a[0]; out[1] = a[1]; out[2] = a[2]; return; }
-  const float d3 = dot3(ab, bp), d4 = dot3(ac, bp);
-  if (d3 >= 0.f && d4 <= d3) { out[0] = b[0]; out[1] = b[1]; out[2] = b[2]; return; }
-  const float vc = d1 * d4 - d3 * d2;
-  if (vc <= 0.f && d1 >= 0.f && d3 <= 0.f) {
-    const float t = d1 / (d1 - d3);
-    out[0] = a[0] + t * ab[0]; out[1] = a[1] + t * ab[1]; out[2] = a[2] + t * ab[2];
-    return;
-  }
-  const float d5 = dot3(ab, cp), d6 = dot3(ac, cp);
-  if (d6 >= 0.f && d5 <= d6) { out[0] = c[0]; out[1] = c[1]; out[2] = c[2]; return; }
-  const float vb = d5 * d2 - d1 * d6;
-  if (vb <= 0.f && d2 >= 0.f && d6 <= 0.f) {
-    const float t = d2 / (d2 - d6);
-    out[0] = a[0] + t * ac[0]; out[1] = a[1] + t * ac[1]; out[2] = a[2] + t * ac[2];
-    return;
-  }
-  const float va = d3 * d6 - d5 * d4;
-  if (va <= 0.f && (d4 - d3) >= 0.f && (d5 - d6) >= 0.f) {
-    const float t = (d4 - d3) / ((d4 - d3) + (d5 - d6));
-#pragma unroll
-    for (int k = 0; k < 3; k++) out[k] = b[k] + t * (c[k] - b[k]);
-    return;
-  }
-  // face region: the plane projection n (n.a) / |n|^2 (the oracle's
-  // tri_closest): the barycentric a + v ab + w ac cancels catastrophically in
-  // fp32 for MPR's cm-sized final portal around a sub-mm penetration
-  float n[3];
-  cross(n, ab, ac);
-  const float sc = dot3(n, a) / dot3(n, n);
-#pragma unroll
-  for (int k = 0; k < 3; k++) out[k] = n[k] * sc;
-  (void)va; (void)vb; (void)vc;
-}
-
-// returns true and (depth, dir g1 -> g2, pos) when the geoms overlap.
-// Zero tests are geometric and in metres, identical in the oracle: libccd's
-// are absolute DBL_EPSILON tests on lengths, areas and volumes alike, which
-// in fp32 call two cm-scale vectors parallel (|v0 x v1|^2 ~ 1e-8 < eps);
-// here a length is zero below kMprEps (1.2e-7 m, fp32 resolution of world
-// coordinates), two vectors are parallel when one passes within kMprEps of
-// the other's line, and a point lies on a plane within kMprEps of it.
-template <class S>
-__device__ bool mpr_lane(const DevModel* __restrict__ m, const S& s, int g1, int g2, float& depth, float dir[3],
-                         float pos[3], int (&hint)[2], float* trace = nullptr) {
-  MprPt p[4], v4;
-  float va[3], vb[3], dd;
-  const float tol = kMprTol;
-  const GeomQ gqa[2] = {geom_q(m, g1), geom_q(m, g2)};
-  const GeomQ* const gq = gqa;
-  // point x off the plane through the origin with (unnormalised) normal c by more than kMprEps
-  auto off_plane = [](float x, const float c[3]) { return fabsf(x) >= kMprEps * sqrtf(dot3(c, c)); };
-#pragma unroll
-  for (int k = 0; k < 3; k++) {  // the frame of the Minkowski points: origin at g2's centre
-    p[0].a[k] = s.gxpos[g1][k] - s.gxpos[g2][k];
-    p[0].b[k] = 0.f;
-    p[0].v[k] = p[0].a[k];
-  }
-  if (mpr_zero(p[0].v[0]) && mpr_zero(p[0].v[1]) && mpr_zero(p[0].v[2])) p[0].v[0] += 10.f * kMprEps;
-  dir[0] = -p[0].v[0]; dir[1] = -p[0].v[1]; dir[2] = -p[0].v[2];
-  nrm3(dir);
-  mpr_support(m, s, g1, g2, dir, p[1], hint, trace, gq);
-  dd = dot3(p[1].v, dir);
-  if (mpr_zero(dd) || dd < 0.f) return false;
-  cross(dir, p[0].v, p[1].v);
-  {
-    const float thr = kMprEps * (sqrtf(dot3(p[0].v, p[0].v)) + sqrtf(dot3(p[1].v, p[1].v)));
-    if (dot3(dir, dir) < thr * thr) {  // v1 on the ray from v0 through the origin
-#pragma unroll
-      for (int k = 0; k < 3; k++) pos[k] = 0.5f * (p[1].a[k] + p[1].b[k]) + s.gxpos[g2][k];
-      if (mpr_zero(p[1].v[0]) && mpr_zero(p[1].v[1]) && mpr_zero(p[1].v[2])) {
-        depth = 0.f;
-        dir[0] = dir[1] = dir[2] = 0.f;
-      } else {
-        dir[0] = p[1].v[0]; dir[1] = p[1].v[1]; dir[2] = p[1].v[2];
-        depth = sqrtf(dot3(dir, dir));
-        nrm3(dir);
-      }
-      return true;
-    }
-  }
-  nrm3(dir);
-  mpr_support(m, s, g1, g2, dir, p[2], hint, trace, gq);
-  dd = dot3(p[2].v, dir);
-  if (mpr_zero(dd) || dd < 0.f) return false;
-#pragma unroll
-  for (int k = 0; k < 3; k++) { va[k] = p[1].v[k] - p[0].v[k]; vb[k] = p[2].v[k] - p[0].v[k]; }
-  cross(dir, va, vb);
-  nrm3(dir);
-  if (dot3(dir, p[0].v) > 0.f) {
-    const MprPt t = p[1]; p[1] = p[2]; p[2] = t;
-    dir[0] = -dir[0]; dir[1] = -dir[1]; dir[2] = -dir[2];
-  }
-  for (int guard = 0;; guard++) {
-    if (guard > kMprIter) return false;
-    mpr_support(m, s, g1, g2, dir, p[3], hint, trace, gq);
-    dd = dot3(p[3].v, dir);
-    if (mpr_zero(dd) || dd < 0.f) return false;
-    bool cont = false;
-    cross(va, p[1].v, p[3].v);
-    dd = dot3(va, p[0].v);
-    if (dd < 0.f && off_plane(dd, va)) { p[2] = p[3]; cont = true; }
-    if (!cont) {
-      cross(va, p[3].v, p[2].v);
-      dd = dot3(va, p[0].v);
-      if (dd < 0.f && off_plane(dd, va)) { p[1] = p[3]; cont = true; }
-    }
-    if (trace) trace[9] = (float)guard;
-    if (!cont) break;
-#pragma unroll
-    for (int k = 0; k < 3; k++) { va[k] = p[1].v[k] - p[0].v[k]; vb[k] = p[2].v[k] - p[0].v[k]; }
-    cross(dir, va, vb);
-    nrm3(dir);
-  }
-  for (int it = 0;; it++) {
-    if (trace) trace[10] = (float)it;
-    mpr_dir(p, dir);
-    dd = dot3(dir, p[1].v);
-    if (mpr_zero(dd) || dd > 0.f) break;
-    mpr_support(m, s, g1, g2, dir, v4, hint, trace, gq);
-    dd = dot3(v4.v, dir);
-    if (!(mpr_zero(dd) || dd > 0.f) || mpr_reach(p, v4, dir, tol) || it > kMprIter) return false;
-    mpr_expand(p, v4);
-  }
-  for (int it = 0;; it++) {
-    if (trace) trace[11] = (float)it;
-    mpr_dir(p, dir);
-    mpr_support(m, s, g1, g2, dir, v4, hint, trace, gq);
-    if (mpr_reach(p, v4, dir, tol) || it > kMprIter) break;
-    mpr_expand(p, v4);
-  }
-  if (trace)
-    for (int i = 0; i < 4; i++)
-      for (int k = 0; k < 3; k++) {
-        trace[12 + 9 * i + k] = p[i].v[k];
-        trace[12 + 9 * i + 3 + k] = p[i].a[k];
-        trace[12 + 9 * i + 6 + k] = p[i].b[k];
-      }
-  float w[3];
-  tri_closest(p[1].v, p[2].v, p[3].v, w);
-  depth = sqrtf(dot3(w, w));
-  if (mpr_zero(depth)) { dir[0] = dir[1] = dir[2] = 0.f; }
-  else { dir[0] = w[0] / depth; dir[1] = w[1] / depth; dir[2] = w[2] / depth; }
-  float pd[3], b[4], x[3];
-  {
-    float e1[3] = {p[2].v[0] - p[1].v[0], p[2].v[1] - p[1].v[1], p[2].v[2] - p[1].v[2]};
-    float e2[3] = {p[3].v[0] - p[1].v[0], p[3].v[1] - p[1].v[1], p[3].v[2] - p[1].v[2]};
-    cross(pd, e1, e2);  // portal normal, |pd| = twice the portal's area
-  }
-  cross(x, p[2].v, p[3].v); b[0] = dot3(x, p[1].v);
-  cross(x, p[3].v, p[2].v); b[1] = dot3(x, p[0].v);
-  cross(x, p[0].v, p[1].v); b[2] = dot3(x, p[3].v);
-  cross(x, p[2].v, p[1].v); b[3] = dot3(x, p[0].v);
-  float sum = b[0] + b[1] + b[2] + b[3];
-  // sum = 6 x the tetrahedron's volume: degenerate when v0 lies within kMprEps of the portal's plane
-  if (!off_plane(sum, pd) || sum < 0.f) {
-    nrm3(pd);
-    b[0] = 0.f;
-    cross(x, p[2].v, p[3].v); b[1] = dot3(x, pd);
-    cross(x, p[3].v, p[1].v); b[2] = dot3(x, pd);
-    cross(x, p[1].v, p[2].v); b[3] = dot3(x, pd);
-    sum = b[1] + b[2] + b[3];
-  }
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    float pa = 0.f, pb = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; i++) { pa += b[i] * p[i].a[k]; pb += b[i] * p[i].b[k]; }
-    pos[k] = 0.5f * (pa + pb) / sum + s.gxpos[g2][k];
-  }
-  return true;
-}
-
-__device__ __forceinline__ bool beats(float v, float best) { return v > best + 1e-4f * fabsf(best) + 1e-12f; }
-__device__ __forceinline__ bool near_max(float v, float mx) { return v >= mx - (1e-4f * fabsf(mx) + 1e-12f); }
-__device__ __forceinline__ float wmax(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
-
-// Both manifold callees below are inlined: 241 -> 235 VGPRs, no scratch (the
-// contact arrays stay in registers), C4 48.6 -> 46.7 ms
-// Plane-mesh manifold (MJX plane_convex / _manifold_points, the oracle's
-// col_plane_mesh), wave-cooperative: every lane calls it with the same pair
-// (mesh g, plane normal n through xp, penetration depth) and lane q receives
-// the contacts.  The hull's vertices are scanned 64 at a time -- a first /
-// last ballot for the penetrating set, then per pick a wave max and a ballot
-// for its first index within the tie band (near_max, as the oracle) -- instead
-// of four serial per-lane scans (a 2691-vertex hull touching the table made a
-// handful of dual-arm candidates 3x slower than the rest).
-template <class S>
-__device__ __forceinline__
-void plane_mesh_manifold_wave(const DevModel* __restrict__ m_, const S& s, int g,
-                                                      const float n_[3], const float* xp_, float depth, int q, int lane,
-                                                      float dist[4], float pos[4][3], float nrm[4][3], int& nsl) {
-  const MPCR_GMEM DevModel* __restrict__ m = uniform_model(m_);
-  ASSUME_LDS(&s); ASSUME_PRIVATE(dist); ASSUME_PRIVATE(pos); ASSUME_PRIVATE(nrm); ASSUME_PRIVATE(&nsl);
-  const float n[3] = {n_[0], n_[1], n_[2]}, xp[3] = {xp_[0], xp_[1], xp_[2]};  // in registers (no alias reloads)
-  const float* R = s.gxmat[g];
-  const float* xg = s.gxpos[g];
-  float nl[3], pl[3];
-  mtv(nl, R, n);
-  const float dx[3] = {xp[0] - xg[0], xp[1] - xg[1], xp[2] - xg[2]};
-  mtv(pl, R, dx);
-  const float thr = fmaxf(0.f, depth - 1e-3f);
-  const int v0 = m->geom_hulladr[g], v1 = v0 + m->geom_hullnum[g];
-  const MPCR_GMEM float4* __restrict__ hv = m->hull_vert;
-  auto sup = [&](const float4& v) { return (pl[0] - v.x) * nl[0] + (pl[1] - v.y) * nl[1] + (pl[2] - v.z) * nl[2]; };
-  int ia = -1, il = -1;
-  for (int base = v0; base < v1; base += WAVE) {
-    const int i = base + lane;
-    const unsigned long long bm = __ballot(i < v1 && sup(hv[i < v1 ? i : v0]) > thr);
-    if (bm) {
-      if (ia < 0) ia = base + __builtin_ctzll(bm);
-      il = base + 63 - __builtin_clzll(bm);
-    }
-  }
-  if (ia < 0) {  // the climb's vertex alone (threshold rounding): lane q keeps it
-    if (lane == q) nsl = 1;
-    return;
-  }
-  // max of e over the penetrating set, then its first index within the band
-  auto pick = [&](auto&& ef, float& mx) {
-    float lm = -1.f;
-    for (int base = ia; base <= il; base += WAVE) {
-      const int i = base + lane;
-      if (i <= il) {
-        const float4 v = hv[i];
-        if (sup(v) > thr) lm = fmaxf(lm, ef(v));
-      }
-    }
-    mx = wmax(lm);
-    for (int base = ia; base <= il; base += WAVE) {
-      const int i = base + lane;
-      bool hit = false;
-      if (i <= il) {
-        const float4 v = hv[i];
-        hit = sup(v) > thr && near_max(ef(v), mx);
-      }
-      const unsigned long long bm = __ballot(hit);
-      if (bm) return base + __builtin_ctzll(bm);
-    }
-    return ia;  // unreachable: the maximum itself is within the band
-  };
-  const float4 a = hv[ia];
-  float mx;
-  const int ib = pick([&](const float4& v) {
-    return (a.x - v.x) * (a.x - v.x) + (a.y - v.y) * (a.y - v.y) + (a.z - v.z) * (a.z - v.z);
-  }, mx);
-  const float4 b = hv[ib];
-  float ab[3];
-  {
-    const float amb[3] = {a.x - b.x, a.y - b.y, a.z - b.z};
-    cross(ab, nl, amb);
-  }
-  const int ic = pick([&](const float4& v) {
-    return fabsf((a.x - v.x) * ab[0] + (a.y - v.y) * ab[1] + (a.z - v.z) * ab[2]);
-  }, mx);
-  const float4 c = hv[ic];
-  float ac[3], bc[3];
-  {
-    const float amc[3] = {a.x - c.x, a.y - c.y, a.z - c.z}, bmc[3] = {b.x - c.x, b.y - c.y, b.z - c.z};
-    cross(ac, nl, amc);
-    cross(bc, nl, bmc);
-  }
-  float bbp, bap;
-  const int ibp = pick([&](const float4& v) {
-    return fabsf((b.x - v.x) * bc[0] + (b.y - v.y) * bc[1] + (b.z - v.z) * bc[2]);
-  }, bbp);
-  const int iap = pick([&](const float4& v) {
-    return fabsf((a.x - v.x) * ac[0] + (a.y - v.y) * ac[1] + (a.z - v.z) * ac[2]);
-  }, bap);
-  const int idx[4] = {ia, ib, ic, beats(bap, bbp) ? iap : ibp};
-#pragma unroll
-  for (int k = 0; k < 4; k++) {
-    bool dup = false;
-#pragma unroll
-    for (int t = 0; t < k; t++) dup |= idx[t] == idx[k];
-    const float4 v = hv[idx[k]];
-    const float l[3] = {v.x, v.y, v.z};
-    float w[3];
-    mv(w, R, l);
-    const float d = -sup(v);
-    if (lane == q) {
-      dist[k] = dup ? 1e30f : d;
-#pragma unroll
-      for (int e = 0; e < 3; e++) { pos[k][e] = w[e] + xg[e] - 0.5f * d * n[e]; nrm[k][e] = n[e]; }
-    }
-  }
-  if (lane == q) nsl = 4;
-}
-
-constexpr int kPendingManifold = -4;  // narrow_lane: plane-mesh pair awaiting plane_mesh_manifold_wave
-constexpr float kPolyConeCos = 0.94f;  // ~20 degrees: candidate faces' Gauss-map cone about MPR's normal
-static_assert(kPolyConeCos == (float)CONE_COS, "the host's cone table is built for this cone");
-constexpr int kPendingPoly = -5;      // narrow_lane: polyhedron pair hit by MPR, awaiting poly_manifold_wave
-
-// hull vertex index of geom g's support point along dir (world): the mesh
-// climb from hint (the pair's, read only), or the box corner (+ side on an
-// exactly zero component) -- the oracle's support_vertex
-template <class S>
-__device__ __forceinline__ int support_vertex(const DevModel* __restrict__ m, const S& s, int g, const float dir[3],
-                                              int hint) {
-  if (m->geom_type[g] == 6) {
-    // the corner on the side of each axis; an axis within the tie band of
-    // zero (a face normal from fp32 rounding) takes the + side, as MPR's box
-    // support does (tie_sign)
-    float l[3];
-    mtv(l, s.gxmat[g], dir);
-    const float ln = sqrtf(l[0] * l[0] + l[1] * l[1] + l[2] * l[2]);
-    return m->geom_cornadr[g] + (tie_sign(l[0], ln) >= 0.f ? 1 : 0) + (tie_sign(l[1], ln) >= 0.f ? 2 : 0) +
-           (tie_sign(l[2], ln) >= 0.f ? 4 : 0);
-  }
-  float p[3];
-  support_geom(m, s, g, dir, p, hint);
-  return hint;
-}
-
-// world outward normal of face f of geom g and its plane offset relative to
-// c (nw . (x - c) = off on the face)
-template <class S>
-__device__ __forceinline__ void face_rel_fp(const S& s, int g, const float4 fp, const float* c, float nw[3],
-                                            float& off) {
-  const float nl[3] = {fp.x, fp.y, fp.z};
-  mv(nw, s.gxmat[g], nl);
-  off = fp.w + nw[0] * (s.gxpos[g][0] - c[0]) + nw[1] * (s.gxpos[g][1] - c[1]) + nw[2] * (s.gxpos[g][2] - c[2]);
-}
-template <class S>
-__device__ __forceinline__ void face_rel(const DevModel* __restrict__ m, const S& s, int g, int f, const float* c,
-                                         float nw[3], float& off) {
-  const float4 fp = m->face_plane[f];
-  const float nl[3] = {fp.x, fp.y, fp.z};
-  mv(nw, s.gxmat[g], nl);
-  off = fp.w + nw[0] * (s.gxpos[g][0] - c[0]) + nw[1] * (s.gxpos[g][1] - c[1]) + nw[2] * (s.gxpos[g][2] - c[2]);
-}
-
-// hull vertex v of geom g relative to c
-template <class S>
-__device__ __forceinline__ void vert_rel(const DevModel* __restrict__ m, const S& s, int g, int v, const float* c,
-                                         float w[3]) {
-  const float4 hv = m->hull_vert[v];
-  const float l[3] = {hv.x, hv.y, hv.z};
-  mv(w, s.gxmat[g], l);
-  w[0] += s.gxpos[g][0] - c[0]; w[1] += s.gxpos[g][1] - c[1]; w[2] += s.gxpos[g][2] - c[2];
-}
-
-// Polyhedron pairs (mesh-mesh, box-mesh): the face-clipping manifold
-// (mujoco-mjx 3.3.1 convex_convex; the oracle's poly_manifold, same rules and
-// orders), wave-cooperative: every lane calls it with the same pair and MPR's
-// normal n (g1 -> g2) / depth, lane q receives up to 4 contacts (nsl = 4) or
-// keeps MPR's single one (nsl = 1: an edge axis carries the contact).  One
-// lane per candidate reference face (the faces on both support vertices and
-// those within the Gauss-map cone of MPR's normal) with its own support query
-// for the SAT separation, one lane per candidate
-// incident face, Sutherland-Hodgman against the reference face's side planes
-// with one lane per polygon vertex and scan compaction (as box_box_wave), the
-// _manifold_points picks as wave maxima.  Coordinates relative to g2's
-// centre, as MPR's.
-// PS: the clip polygon / SAT-separation scratch (polyw, satsep): the LDS
-// image's own, or -- the second wave of a two-wave candidate in the joint
-// convex flush -- a PolyScratchT in the dead dynamics region.
-template <class S, class PS>
-__device__ __forceinline__
-void poly_manifold_wave(const DevModel* __restrict__ m_, const S& s, PS& ps, const short* hints, int p,
-                                                const float n_[3], float depth, int q, int lane, float dist[4],
-                                                float pos[4][3], float nrm[4][3], int& nsl) {
-  const MPCR_GMEM DevModel* __restrict__ m = uniform_model(m_);
-  ASSUME_GLOBAL(hints); ASSUME_LDS(&s); ASSUME_LDS(&ps); ASSUME_PRIVATE(dist); ASSUME_PRIVATE(pos); ASSUME_PRIVATE(nrm);
-  ASSUME_PRIVATE(&nsl);
-  const float n[3] = {n_[0], n_[1], n_[2]};  // in registers (no alias reloads)
-  PSTAMP_DECL
-  const int g1 = m->pair_g1[p], g2 = m->pair_g2[p];
-  const float c[3] = {s.gxpos[g2][0], s.gxpos[g2][1], s.gxpos[g2][2]};
-  const int hw = reinterpret_cast<const int*>(hints)[p - m->cvx_base];
-  const int h0 = (int)(short)(hw & 0xffff), h1 = hw >> 16;
-  // support vertices: lane 0 of g1 along n, lane 1 of g2 along -n
-  int sv = 0;
-  if (lane < 2) {
-    const float sg = lane ? -1.f : 1.f;
-    const float d[3] = {sg * n[0], sg * n[1], sg * n[2]};
-    sv = support_vertex(m, s, lane ? g2 : g1, d, lane ? h1 : h0);
-  }
-  const int s1 = __shfl(sv, 0), s2 = __shfl(sv, 1);
-  PSTAMP(m, 23);
-  const int2 i1 = m->vert_finfo[s1], i2 = m->vert_finfo[s2];
-  // a deep penetration between small hulls: every face is a candidate (MPR's
-  // normal, which seeds the cone below, is that deep the portal face MPR
-  // ended on -- fp32 and fp64 ended 70 degrees apart on the Hand-E's
-  // interpenetrating finger pads)
-  const int nf1 = m->geom_facenum[g1], nf2 = m->geom_facenum[g2];
-  const bool allf = POLY_ALLF_ON && depth > POLY_DEEP && nf1 + nf2 <= POLY_ALLF;
-  float bsep = 0.f;
-  int fr = -1;
-  bool rtwo = false, found = false;
-  if (allf) {
-    // SAT separation of every face (lane = face, rounds of 64) into LDS,
-    // the wave max, then the lowest face index within the max's tie band
-    // (MPCR_ALLF_U faces per lane per pass: their face-plane loads, then
-    // their support queries' first loads, in flight together -- a pass was
-    // two dependent load latencies per 64 faces, up to 8 passes in turn)
-    const int fa1 = m->geom_faceadr[g1], fa2 = m->geom_faceadr[g2], nf = nf1 + nf2;
-    constexpr int U = MPCR_ALLF_U;
-    float mxl = -3e38f;  // this lane's maximum (the wave max below: max is exact in any order)
-#pragma unroll 1
-    for (int b0 = 0; b0 < nf; b0 += U * WAVE) {
-      float4 fp[U];
-#pragma unroll
-      for (int u = 0; u < U; u++) {
-        const int k = b0 + u * WAVE + lane;
-        fp[u] = make_float4(0.f, 0.f, 1.f, 0.f);
-        if (k < nf) fp[u] = m->face_plane[k >= nf1 ? fa2 + k - nf1 : fa1 + k];
-      }
-      SupQ q[U];
-      float nw[U][3], off[U];
-#pragma unroll
-      for (int u = 0; u < U; u++) {
-        const int k = b0 + u * WAVE + lane;
-        if (k < nf) {
-          const bool two = k >= nf1;
-          const int g = two ? g2 : g1, go = two ? g1 : g2;
-          face_rel_fp(s, g, fp[u], c, nw[u], off[u]);
-          const float mn[3] = {-nw[u][0], -nw[u][1], -nw[u][2]};
-          sup_start(m, s, go, mn, two ? h0 : h1, q[u]);
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < U; u++) {
-        const int k = b0 + u * WAVE + lane;
-        if (k < nf) {
-          const bool two = k >= nf1;
-          float pt[3];
-          int h = two ? h0 : h1;
-          sup_finish(m, s, two ? g1 : g2, q[u], pt, h, c, MPCR_SAT_TIES != 0);
-          const float sp = nw[u][0] * pt[0] + nw[u][1] * pt[1] + nw[u][2] * pt[2] - off[u];
-          ps.satsep[k] = sp;
-          mxl = fmaxf(mxl, sp);
-        }
-      }
-    }
-    const float mxa = wmax(mxl);
-    sync();
-    // the key 2 f + side keeps the side with the face: two geoms of one mesh
-    // share their face range, and on equal faces g1's wins, the
-    // oracle's first-listed candidate
-    float fmin = 3e38f;
-#pragma unroll 1
-    for (int b0 = 0; b0 < nf; b0 += WAVE) {
-      const int k = b0 + lane;
-      const bool nb = k < nf && near_max(ps.satsep[k], mxa);
-      const int key = k >= nf1 ? 2 * (fa2 + k - nf1) + 1 : 2 * (fa1 + k);
-      fmin = fminf(fmin, -wmax(nb ? -(float)key : -3e38f));
-    }
-    found = fmin < 3e38f;
-    if (found) {
-      const int key = (int)fmin;
-      fr = key >> 1;
-      rtwo = (key & 1) != 0;
-      bsep = ps.satsep[rtwo ? nf1 + fr - fa2 : fr - fa1];
-    }
-    sync();  // satsep shares bytes with the clip buffer below
-  }
-  const int c1 = allf ? 0 : min(i1.y, WAVE), c2 = allf ? 0 : min(i2.y, WAVE - c1), ns = c1 + c2;
-  // candidate reference faces, at most 64 (one per lane), in the oracle's
-  // order: g1's on s1, g2's on s2, then every face whose outward normal lies
-  // within the Gauss-map cone of n (g1) / -n (g2), face index order, those
-  // already listed skipped -- a ballot-compacted scan of both face tables into
-  // an LDS list (the clip buffer's second half, free until the clip)
-  // The faces scanned are the host's cone table entries for the cube-map cell
-  // of the local direction (DevModel::cone_cell: a superset of the faces the
-  // test below accepts, ascending), not all of the geom's faces (up to 5219
-  // on the dual arm's hulls): the same candidates in the same order.  The
-  // support-vertex faces of each side sit one per lane (lane k: entry k) and
-  // the duplicate test reads them with readlane.
-  int* const cl = reinterpret_cast<int*>(&ps.polyw[1][0][0]);
-  int nc = ns;
-  const int vf1 = lane < c1 ? m->vert_face[i1.x + lane] : -1, vf2 = lane < c2 ? m->vert_face[i2.x + lane] : -1;
-#pragma unroll 1
-  for (int sd = 0; sd < 2 && !allf; sd++) {
-    const int g = sd ? g2 : g1;
-    const int cs = sd ? c2 : c1, vfs = sd ? vf2 : vf1;
-    const float sg = sd ? -1.f : 1.f;
-    float l[3];
-    {
-      const float dn[3] = {sg * n[0], sg * n[1], sg * n[2]};
-      mtv(l, s.gxmat[g], dn);
-    }
-    const int2 cc = m->cone_cell[m->geom_coneadr[g] + lut_cell<CONE_R>(l)];
-#pragma unroll 1
-    for (int b0 = 0; b0 < cc.y && nc < WAVE; b0 += WAVE) {
-      bool sel = false;
-      int f = -1;
-      if (b0 + lane < cc.y) {
-        f = m->cone_face[cc.x + b0 + lane];
-        const float4 fp = m->face_plane[f];
-        const float nl[3] = {fp.x, fp.y, fp.z};
-        float nw[3];
-        mv(nw, s.gxmat[g], nl);
-        sel = sg * (nw[0] * n[0] + nw[1] * n[1] + nw[2] * n[2]) >= kPolyConeCos;
-      }
-#pragma unroll 1
-      for (int k = 0; k < cs; k++) sel &= __builtin_amdgcn_readlane(vfs, k) != f;
-      int tot;
-      const int o = wscan_excl(sel ? 1 : 0, tot);
-      if (sel && nc + o < WAVE) cl[nc - ns + o] = f | (sd << 24);
-      nc = min(nc + tot, WAVE);
-    }
-  }
-  sync();
-  PSTAMP(m, 24);
-  // SAT separation along each candidate's outward normal
-  float sep = -3e38f;
-  int fid = -1, two = 0;
-  if (!allf && lane < nc) {
-    if (lane < ns) {
-      two = lane >= c1;
-      fid = m->vert_face[two ? i2.x + lane - c1 : i1.x + lane];
-    } else {
-      const int e = cl[lane - ns];
-      two = e >> 24;
-      fid = e & 0xffffff;
-    }
-    const int g = two ? g2 : g1, go = two ? g1 : g2;
-    float nw[3], off, pt[3];
-    face_rel(m, s, g, fid, c, nw, off);
-    const float mn[3] = {-nw[0], -nw[1], -nw[2]};
-    int h = two ? h0 : h1;
-    support_geom(m, s, go, mn, pt, h, c, MPCR_SAT_TIES != 0);
-    sep = nw[0] * pt[0] + nw[1] * pt[1] + nw[2] * pt[2] - off;
-  }
-  // the maximum's tie band: the lowest face index (a flush face pair has the
-  // same separation from either side)
-  if (!allf) {
-    const float mx = wmax(sep);
-    const bool nb = lane < nc && near_max(sep, mx);
-    const float fmn = -wmax(nb ? -(float)fid : -3e38f);
-    const unsigned long long bm = __ballot(nb && (float)fid == fmn);
-    const int kb = bm ? __builtin_ctzll(bm) : 0;
-    found = bm != 0;
-    bsep = __shfl(sep, kb);
-    fr = __shfl(fid, kb);
-    rtwo = __shfl(two, kb) != 0;
-  }
-  PSTAMP(m, 25);
-  if (!found || -bsep > 1.05f * depth + 1e-5f) {  // an edge axis: MPR's single contact
-    if (lane == q) nsl = 1;
-    return;
-  }
-  const int gr = rtwo ? g2 : g1, gi = rtwo ? g1 : g2;
-  float nr[3], offr;
-  face_rel(m, s, gr, fr, c, nr, offr);
-  // the reference polygon's vertices (lane k: vertex k), loaded here so their
-  // latency hides behind the incident face's support climb
-  const int2 fri = m->face_vinfo[fr];
-  const int nrv = fri.y;
-  float A[3] = {0.f, 0.f, 0.f}, sn[3];
-  if (lane < nrv) vert_rel(m, s, gr, m->face_vert[fri.x + lane], c, A);
-  // incident face: the most anti-parallel face on gi's support vertex along -nr
-  int si = 0;
-  if (lane == 0) {
-    const float d[3] = {-nr[0], -nr[1], -nr[2]};
-    si = support_vertex(m, s, gi, d, rtwo ? h0 : h1);
-  }
-  si = __shfl(si, 0);
-  const int2 ii = m->vert_finfo[si];
-  const int ci = min(ii.y, WAVE);
-  float al = -3e38f;
-  int finc = -1;
-  if (lane < ci) {
-    finc = m->vert_face[ii.x + lane];
-    const float4 fp = m->face_plane[finc];
-    const float nl[3] = {fp.x, fp.y, fp.z};
-    float nw[3];
-    mv(nw, s.gxmat[gi], nl);
-    al = -(nw[0] * nr[0] + nw[1] * nr[1] + nw[2] * nr[2]);
-  }
-  const float mxa = wmax(al);
-  const unsigned long long bma = __ballot(lane < ci && near_max(al, mxa));
-  if (!bma) {
-    if (lane == q) nsl = 1;
-    return;
-  }
-  const int fi = __shfl(finc, __builtin_ctzll(bma));
-  // reference polygon (lane k: vertex k and its edge's outward side-plane
-  // normal), incident polygon into the clip buffer
-  const int2 fii = m->face_vinfo[fi];
-  const int ninc = fii.y;
-  {
-    const int ln = lane + 1 >= nrv ? 0 : lane + 1;
-    const float ed[3] = {__shfl(A[0], ln) - A[0], __shfl(A[1], ln) - A[1], __shfl(A[2], ln) - A[2]};
-    cross(sn, ed, nr);
-  }
-  if (lane < ninc) {
-    float w[3];
-    vert_rel(m, s, gi, m->face_vert[fii.x + lane], c, w);
-    ps.polyw[0][lane][0] = w[0]; ps.polyw[0][lane][1] = w[1]; ps.polyw[0][lane][2] = w[2];
-  }
-  sync();
-  PSTAMP(m, 26);
-  int np = ninc, cur = 0;
-  for (int e = 0; e < nrv && np > 0; e++) {
-    const float Ae[3] = {__shfl(A[0], e), __shfl(A[1], e), __shfl(A[2], e)};
-    const float se[3] = {__shfl(sn[0], e), __shfl(sn[1], e), __shfl(sn[2], e)};
-    float P[3] = {0.f, 0.f, 0.f}, Q[3] = {0.f, 0.f, 0.f}, dp = 0.f, dq = 0.f;
-    int e0 = 0, e1 = 0;
-    if (lane < np) {
-      const int k2 = lane + 1 == np ? 0 : lane + 1;
-#pragma unroll
-      for (int k = 0; k < 3; k++) { P[k] = ps.polyw[cur][lane][k]; Q[k] = ps.polyw[cur][k2][k]; }
-      dp = se[0] * (P[0] - Ae[0]) + se[1] * (P[1] - Ae[1]) + se[2] * (P[2] - Ae[2]);
-      dq = se[0] * (Q[0] - Ae[0]) + se[1] * (Q[1] - Ae[1]) + se[2] * (Q[2] - Ae[2]);
-      e0 = dp <= 0.f;
-      e1 = (dp < 0.f && dq > 0.f) || (dp > 0.f && dq < 0.f);
-    }
-    int tot;
-    const int o = wscan_excl(e0 + e1, tot);
-    if (e0 && o < S::PMAXW) {
-#pragma unroll
-      for (int k = 0; k < 3; k++) ps.polyw[cur ^ 1][o][k] = P[k];
-    }
-    if (e1 && o + e0 < S::PMAXW) {
-      const float wgt = dp / (dp - dq);
-#pragma unroll
-      for (int k = 0; k < 3; k++) ps.polyw[cur ^ 1][o + e0][k] = P[k] + wgt * (Q[k] - P[k]);
-    }
-    np = min(tot, S::PMAXW);
-    cur ^= 1;
-    sync();
-  }
-  // the clipped points below the reference plane
-  float P[3] = {0.f, 0.f, 0.f}, dk = 3e38f;
-  bool keep = false;
-  if (lane < np) {
-#pragma unroll
-    for (int k = 0; k < 3; k++) P[k] = ps.polyw[cur][lane][k];
-    dk = nr[0] * P[0] + nr[1] * P[1] + nr[2] * P[2] - offr;
-    keep = dk < m->pair_margin[p];
-  }
-  const unsigned long long km = __ballot(keep);
-  const int nk = __popcll(km);
-  sync();  // the clip buffer is free for the next pair
-  PSTAMP(m, 27);
-  const float sg = rtwo ? -1.f : 1.f;  // contact normal g1 -> g2
-  if (nk == 0) {
-    // no clipped point below the reference plane (a small reference face
-    // over a deep penetration): the SAT axis still carries the contact, one
-    // point at gi's support vertex along -nr (the oracle's rule; MPR's own
-    // normal for a penetration this deep is path-dependent)
-    float w[3];
-    vert_rel(m, s, gi, si, c, w);
-    const float dk = nr[0] * w[0] + nr[1] * w[1] + nr[2] * w[2] - offr;
-    if (lane == q) {
-      if (dk < m->pair_margin[p]) {
-        dist[0] = dk;
-        dist[1] = dist[2] = dist[3] = 1e30f;
-#pragma unroll
-        for (int e = 0; e < 3; e++) { pos[0][e] = w[e] - 0.5f * dk * nr[e] + c[e]; nrm[0][e] = sg * nr[e]; }
-        nsl = 4;
-      } else {
-        nsl = 1;
-      }
-    }
-    return;
-  }
-  int idx[4] = {-1, -1, -1, -1};
-  if (nk <= 4) {
-    unsigned long long r = km;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      if (r) { idx[j] = __builtin_ctzll(r); r &= r - 1; }
-    }
-  } else {
-    // _manifold_points: a = the first, b = the farthest from a, c = the
-    // farthest from line ab, d = the farthest from edge bc or ac
-    auto pick = [&](float e, float& mxv) {
-      mxv = wmax(keep ? e : -1.f);
-      return __builtin_ctzll(__ballot(keep && near_max(e, mxv)));
-    };
-    const int ia = __builtin_ctzll(km);
-    const float a[3] = {__shfl(P[0], ia), __shfl(P[1], ia), __shfl(P[2], ia)};
-    float mxv;
-    const int ib = pick((a[0] - P[0]) * (a[0] - P[0]) + (a[1] - P[1]) * (a[1] - P[1]) + (a[2] - P[2]) * (a[2] - P[2]),
-                        mxv);
-    const float b[3] = {__shfl(P[0], ib), __shfl(P[1], ib), __shfl(P[2], ib)};
-    float ab[3];
-    {
-      const float amb[3] = {a[0] - b[0], a[1] - b[1], a[2] - b[2]};
-      cross(ab, nr, amb);
-    }
-    const int ic = pick(fabsf((a[0] - P[0]) * ab[0] + (a[1] - P[1]) * ab[1] + (a[2] - P[2]) * ab[2]), mxv);
-    const float cc[3] = {__shfl(P[0], ic), __shfl(P[1], ic), __shfl(P[2], ic)};
-    float ac[3], bc[3];
-    {
-      const float amc[3] = {a[0] - cc[0], a[1] - cc[1], a[2] - cc[2]}, bmc[3] = {b[0] - cc[0], b[1] - cc[1], b[2] - cc[2]};
-      cross(ac, nr, amc);
-      cross(bc, nr, bmc);
-    }
-    float bbp, bap;
-    const int ibp = pick(fabsf((b[0] - P[0]) * bc[0] + (b[1] - P[1]) * bc[1] + (b[2] - P[2]) * bc[2]), bbp);
-    const int iap = pick(fabsf((a[0] - P[0]) * ac[0] + (a[1] - P[1]) * ac[1] + (a[2] - P[2]) * ac[2]), bap);
-    idx[0] = ia; idx[1] = ib; idx[2] = ic; idx[3] = beats(bap, bbp) ? iap : ibp;
-  }
-#pragma unroll
-  for (int j = 0; j < 4; j++) {
-    bool dup = idx[j] < 0;
-#pragma unroll
-    for (int t = 0; t < j; t++) dup |= idx[t] == idx[j];
-    const int L = idx[j] < 0 ? 0 : idx[j];
-    const float Pj[3] = {__shfl(P[0], L), __shfl(P[1], L), __shfl(P[2], L)};
-    const float dj = __shfl(dk, L);
-    if (lane == q) {
-      dist[j] = dup ? 1e30f : dj;
-#pragma unroll
-      for (int e = 0; e < 3; e++) { pos[j][e] = Pj[e] - 0.5f * dj * nr[e] + c[e]; nrm[j][e] = sg * nr[e]; }
-    }
-  }
-  if (lane == q) nsl = 4;
-  PSTAMP(m, 28);
-}
-
-// per-lane narrow phase for plane/capsule/box-vs-capsule pairs (box-box is
-// wave-cooperative, below).  out: dist[4], pos[4][3], nrm[4][3]
-// Single-arm kernels: dist[] on every lane -- cost_c reads the distances --
-// and a capsule-box point's pos / nrm on demand: only where the point will be
-// emitted as a contact (its distance under the margin, contacts enabled); on
-// most steps no lane of the wave has one and the block is skipped.  With
-// DEV_NARROW_EAGER in the device model's flags (MPCR_NARROW_EAGER=1, tests)
-// every lane computes them.  rq: quads 0-1 of the pair's set-up record as the
-// chunk loop fetched them.
-template <class S>
-__device__ __forceinline__ int narrow_lane(const DevModel* __restrict__ m, const S& s, short* hints, int p, float dist[4],
-                            float pos[4][3], float nrm[4][3], float* dbg = nullptr,
-                            [[maybe_unused]] const float4* rq = nullptr) {
-  // single-arm kernels: function and geoms from the chunk loop's quads, both
-  // sizes from the record's other two (the model's arrays: pair -> geoms ->
-  // sizes; held from the chunk loop on they cost the one-wave kernel 6 VGPRs)
-  [[maybe_unused]] float4 q0 = {0.f, 0.f, 0.f, 0.f};
-  [[maybe_unused]] float sz1[3], sz2[3];
-  if constexpr (kStepLoad<S>) {
-    const StepPairSetup& ps = step_records(m)->pair[p];
-    q0 = rq[0];
-    const float4 q2 = recq(ps, 2), q3 = recq(ps, 3);
-    sz1[0] = q2.x; sz1[1] = q2.y; sz1[2] = q2.z;
-    sz2[0] = q3.x; sz2[1] = q3.y; sz2[2] = q3.z;
-  }
-  const int g1 = kStepLoad<S> ? __float_as_int(q0.z) : m->pair_g1[p], g2 = kStepLoad<S> ? __float_as_int(q0.w) : m->pair_g2[p];
-  const int func = kStepLoad<S> ? __float_as_int(q0.x) : m->pair_func[p];
-  const float* x1 = s.gxpos[g1];
-  const float* x2 = s.gxpos[g2];
-  const float* R1 = s.gxmat[g1];
-  const float* R2 = s.gxmat[g2];
-  const float* s1 = kStepLoad<S> ? sz1 : m->geom_size[g1];
-  const float* s2 = kStepLoad<S> ? sz2 : m->geom_size[g2];
-#pragma unroll
-  for (int k = 0; k < 4; k++) dist[k] = 1e30f;
-  if (func == 0) {  // plane - capsule
-    float n[3] = {R1[2], R1[5], R1[8]}, ax[3] = {R2[2], R2[5], R2[8]};
-    float r = s2[0], hl = s2[1];
-#pragma unroll
-    for (int k = 0; k < 2; k++) {
-      float sg = k == 0 ? 1.f : -1.f, e[3], dif[3];
-#pragma unroll
-      for (int c = 0; c < 3; c++) { e[c] = x2[c] + sg * hl * ax[c]; dif[c] = e[c] - x1[c]; }
-      float d = dot3(n, dif) - r;
-      dist[k] = d;
-#pragma unroll
-      for (int c = 0; c < 3; c++) { pos[k][c] = e[c] - n[c] * (r + 0.5f * d); nrm[k][c] = n[c]; }
-    }
-    return 2;
-  }
-  if (func == 1) {  // plane - box: the 4 deepest corners, ascending depth (ties: corner index)
-    // depth(c) = n.(x2 - x1) + sum_k +-w_k with w_k = h_k n.R2_k: the deepest
-    // corner takes the sign against each w_k, the next ones flip the axis of
-    // the smallest |w|, of the second smallest, and then the third axis or
-    // both of the first two -- 5 candidates instead of a 4 x 8 scan
-    const float n[3] = {R1[2], R1[5], R1[8]};
-    float w[3];
-#pragma unroll
-    for (int k = 0; k < 3; k++) w[k] = s2[k] * (n[0] * R2[k] + n[1] * R2[3 + k] + n[2] * R2[6 + k]);
-    const int c0 = (w[0] < 0.f ? 1 : 0) | (w[1] < 0.f ? 2 : 0) | (w[2] < 0.f ? 4 : 0);
-    int ax0 = 0, ax1 = 1, ax2 = 2;  // axes by |w| ascending, index order on ties
-    if (fabsf(w[ax1]) < fabsf(w[ax0])) { const int t = ax0; ax0 = ax1; ax1 = t; }
-    if (fabsf(w[ax2]) < fabsf(w[ax1])) { const int t = ax1; ax1 = ax2; ax2 = t; }
-    if (fabsf(w[ax1]) < fabsf(w[ax0])) { const int t = ax0; ax0 = ax1; ax1 = t; }
-    auto depth = [&](int c) {  // the same expression as the oracle's corner distance
-      const float l[3] = {(c & 1) ? s2[0] : -s2[0], (c & 2) ? s2[1] : -s2[1], (c & 4) ? s2[2] : -s2[2]};
-      float v[3];
-      mv(v, R2, l);
-      return n[0] * (x2[0] + v[0] - x1[0]) + n[1] * (x2[1] + v[1] - x1[1]) + n[2] * (x2[2] + v[2] - x1[2]);
-    };
-    int cs[4] = {c0, c0 ^ (1 << ax0), c0 ^ (1 << ax1), c0 ^ (1 << ax2)};
-    float ds[4] = {depth(cs[0]), depth(cs[1]), depth(cs[2]), depth(cs[3])};
-    {
-      const int c4 = c0 ^ (1 << ax0) ^ (1 << ax1);
-      const float d4 = depth(c4);
-      if (d4 < ds[3] || (d4 == ds[3] && c4 < cs[3])) { cs[3] = c4; ds[3] = d4; }
-    }
-    // order the four by (depth, index): sorting network (0,1) (2,3) (0,2) (1,3) (1,2)
-    auto cx = [&](int i, int j) {
-      if (ds[j] < ds[i] || (ds[j] == ds[i] && cs[j] < cs[i])) {
-        const float td = ds[i]; ds[i] = ds[j]; ds[j] = td;
-        const int tc = cs[i]; cs[i] = cs[j]; cs[j] = tc;
-      }
-    };
-    cx(0, 1); cx(2, 3); cx(0, 2); cx(1, 3); cx(1, 2);
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      const int c = cs[k];
-      const float l[3] = {(c & 1) ? s2[0] : -s2[0], (c & 2) ? s2[1] : -s2[1], (c & 4) ? s2[2] : -s2[2]};
-      float v[3];
-      mv(v, R2, l);
-      dist[k] = ds[k];
-#pragma unroll
-      for (int e = 0; e < 3; e++) { pos[k][e] = x2[e] + v[e] - n[e] * 0.5f * ds[k]; nrm[k][e] = n[e]; }
-    }
-    return 4;
-  }
-  if (func == 2) {  // capsule - capsule
-    float a1[3] = {R1[2], R1[5], R1[8]}, a2[3] = {R2[2], R2[5], R2[8]};
-    float p1[3], d1[3], p2[3], d2[3];
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-      p1[c] = x1[c] - s1[1] * a1[c]; d1[c] = 2 * s1[1] * a1[c];
-      p2[c] = x2[c] - s2[1] * a2[c]; d2[c] = 2 * s2[1] * a2[c];
-    }
-    float sc, tc, n[3], c1[3];
-    seg_seg(p1, d1, p2, d2, &sc, &tc);
-#pragma unroll
-    for (int c = 0; c < 3; c++) { c1[c] = p1[c] + sc * d1[c]; n[c] = p2[c] + tc * d2[c] - c1[c]; }
-    float len = sqrtf(dot3(n, n));
-    if (len < 1e-12f) {
-      float t[3] = {1, 0, 0};
-      if (fabsf(a1[0]) > 0.9f) { t[0] = 0; t[1] = 1; }
-      cross(n, a1, t);
-      float l = sqrtf(dot3(n, n));
-      n[0] /= l; n[1] /= l; n[2] /= l;
-    } else {
-      n[0] /= len; n[1] /= len; n[2] /= len;
-    }
-    float d = len - s1[0] - s2[0];
-    dist[0] = d;
-#pragma unroll
-    for (int c = 0; c < 3; c++) { pos[0][c] = c1[c] + n[c] * (s1[0] + 0.5f * d); nrm[0][c] = n[c]; }
-    return 1;
-  }
-  if (func == 3) {  // capsule - box
-    float ax[3] = {R1[2], R1[5], R1[8]}, r = s1[0], hl = s1[1];
-    const float* h = s2;
-    float A[3], B[3], a[3], dd[3];
-#pragma unroll
-    for (int c = 0; c < 3; c++) { A[c] = x1[c] - hl * ax[c] - x2[c]; B[c] = 2 * hl * ax[c]; }
-    mtv(a, R2, A);
-    mtv(dd, R2, B);
-    float tlo = -1.f, thi = 2.f, flo = 0.f, fhi = 0.f;
-    // knots: 0, 1, (+-h_k - a_k)/dd_k inside (0,1), where the squared
-    // distance's derivative fp (piecewise linear, non-decreasing: the
-    // distance is convex along the segment) is evaluated.  The interior knots
-    // only matter when fp changes sign inside (fp(0) < 0 <= fp(1)); when no
-    // lane's does, the minimum is an end on every lane (ts 0 or 1 below, as
-    // the full scan gives) and the six interior knots are skipped (C3: most
-    // steps of the 20 robot capsule / box pairs, MPCR_CB_SKIP)
-    auto knot = [&](int i) {
-      float t;
-      bool ok = true;
-      if (i == 0) t = 0.f;
-      else if (i == 1) t = 1.f;
-      else {
-        int k = (i - 2) >> 1;
-        float sg = ((i - 2) & 1) ? 1.f : -1.f;
-        ok = fabsf(dd[k]) > kMinVal;
-        t = ok ? (sg * h[k] - a[k]) / dd[k] : 0.f;
-        ok = ok && t > 0.f && t < 1.f;
-      }
-      if (ok) {
-        // x - clamp(x, -h, h) is +-(|x| - h) outside the slab, 0 inside --
-        // the same value as the sign-selected excess, one v_med3 instead
-        // of the compares and selects
-        float fp = 0.f;
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-          const float x = a[k] + t * dd[k];
-          fp += 2.f * dd[k] * (x - __builtin_amdgcn_fmed3f(x, -h[k], h[k]));
-        }
-        if (fp < 0) { if (t > tlo) { tlo = t; flo = fp; } }
-        else { if (t < thi) { thi = t; fhi = fp; } }
-      }
-    };
-    knot(0);
-    knot(1);
-    if (!MPCR_CB_SKIP || __ballot(tlo == 0.f && thi == 1.f) != 0ull) {
-#pragma unroll
-      for (int i = 2; i < 8; i++) knot(i);
-    }
-    float ts;
-    if (tlo < 0) ts = 0.f;
-    else if (thi > 1) ts = 1.f;
-    else ts = fhi - flo > 0 ? tlo - flo * (thi - tlo) / (fhi - flo) : tlo;
-    float pp[3], q[3], nl[3];
-#pragma unroll
-    for (int c = 0; c < 3; c++) pp[c] = a[c] + ts * dd[c];
-    float g = point_box(pp, h, nl, q);
-    if (g <= 1e-6f) {  // on or in the box (penetrating segments land on the surface): the oracle's band
-      // deepest point of g(t) = max_k |x_k(t)| - h_k over its kinks
-      float gbest = 1e30f, tbest = 0.f;
-#pragma unroll
-      for (int i = 0; i < 17; i++) {
-        float t;
-        bool ok = true;
-        if (i == 0) t = 0.f;
-        else if (i == 1) t = 1.f;
-        else if (i < 5) {
-          int k = i - 2;
-          ok = fabsf(dd[k]) > kMinVal;
-          t = ok ? -a[k] / dd[k] : 0.f;
-          ok = ok && t > 0.f && t < 1.f;
-        } else {
-          int q4 = i - 5;        // 0..11: pair (ii,jj) x signs
-          int pr = q4 >> 2;      // 0:(0,1) 1:(0,2) 2:(1,2)
-          int ii = pr == 2 ? 1 : 0, jj = pr == 0 ? 1 : 2;
-          float si = (q4 & 2) ? 1.f : -1.f, sj = (q4 & 1) ? 1.f : -1.f;
-          float den = si * dd[ii] - sj * dd[jj];
-          ok = fabsf(den) > kMinVal;
-          t = ok ? (h[ii] - h[jj] - si * a[ii] + sj * a[jj]) / den : 0.f;
-          ok = ok && t > 0.f && t < 1.f;
-        }
-        if (ok) {
-          float gm = -1e30f;
-#pragma unroll
-          for (int k = 0; k < 3; k++) gm = fmaxf(gm, fabsf(a[k] + t * dd[k]) - h[k]);
-          // a flat minimum (the segment parallel to a face: every kink as
-          // deep) keeps the first candidate -- a later one must be deeper by
-          // more than 1 um, so fp32 and fp64 pick the same point (the oracle's rule)
-          if (gm < gbest - 1e-6f) { gbest = gm; tbest = t; }
-        }
-      }
-      ts = tbest;
-#pragma unroll
-      for (int c = 0; c < 3; c++) pp[c] = a[c] + ts * dd[c];
-      g = point_box(pp, h, nl, q);
-    }
-    // which points get their pos / nrm (single-arm kernels; uniform parts first)
-    [[maybe_unused]] bool want_all = true, want_any = true;
-    [[maybe_unused]] float mg = 0.f;
-    if constexpr (!S::WIDE) {
-      want_all = (m->disableflags & DEV_NARROW_EAGER) != 0;
-      want_any = !(m->disableflags & 16);
-      mg = kStepLoad<S> ? rq[1].w : m->pair_margin[p];
-    }
-    // the far end: on or in the box, the first point's face, the segment
-    // clipped to the face's extent (the oracle's col_capsule_box, round 4);
-    // outside, its own point_box
-    int fk = -1;
-    float fsg = 0.f;
-    if (g <= 0.f) {
-#pragma unroll
-      for (int c = 0; c < 3; c++)
-        if (nl[c] != 0.f) { fk = c; fsg = -nl[c]; }
-    }
-#pragma unroll
-    for (int k = 0; k < 2; k++) {
-      if (k == 1) {
-        float t = ts < 0.5f ? 1.f : 0.f;
-        if (fk >= 0) {
-#pragma unroll
-          for (int j = 0; j < 3; j++) {
-            if (j == fk || !(fabsf(dd[j]) > kMinVal)) continue;
-            const float x = a[j] + t * dd[j];
-            if (fabsf(x) > h[j]) {
-              const float tb = ((x > 0.f ? h[j] : -h[j]) - a[j]) / dd[j];
-              t = ts < t ? fminf(t, fmaxf(tb, ts)) : fmaxf(t, fminf(tb, ts));
-            }
-          }
-          float gf = 0.f;
-#pragma unroll
-          for (int c = 0; c < 3; c++) {
-            pp[c] = a[c] + t * dd[c];
-            nl[c] = c == fk ? -fsg : 0.f;
-            q[c] = c == fk ? fsg * h[c] : pp[c];
-            gf = c == fk ? fsg * pp[c] - h[c] : gf;
-          }
-          g = gf;
-        } else {
-#pragma unroll
-          for (int c = 0; c < 3; c++) pp[c] = a[c] + t * dd[c];
-          g = point_box(pp, h, nl, q);
-        }
-      }
-      if constexpr (S::WIDE) {
-        float n[3], pl[3], tmp[3];
-        mv(n, R2, nl);
-#pragma unroll
-        for (int c = 0; c < 3; c++) pl[c] = 0.5f * (pp[c] + r * nl[c] + q[c]);
-        mv(tmp, R2, pl);
-        dist[k] = g - r;
-#pragma unroll
-        for (int c = 0; c < 3; c++) { pos[k][c] = tmp[c] + x2[c]; nrm[k][c] = n[c]; }
-      } else {
-        dist[k] = g - r;
-        if (want_all || (want_any && dist[k] < mg)) {
-          float n[3], pl[3], tmp[3];
-          mv(n, R2, nl);
-#pragma unroll
-          for (int c = 0; c < 3; c++) pl[c] = 0.5f * (pp[c] + r * nl[c] + q[c]);
-          mv(tmp, R2, pl);
-#pragma unroll
-          for (int c = 0; c < 3; c++) { pos[k][c] = tmp[c] + x2[c]; nrm[k][c] = n[c]; }
-        }
-      }
-    }
-    return 2;
-  }
-  if constexpr (S::WIDE) {
-    // hull hill climbs start where this pair's previous step ended (the
-    // oracle keeps the same per-pair cache)
-    int* hp = reinterpret_cast<int*>(hints) + (p - m->cvx_base);  // (side 0, side 1) as two shorts
-    const int hv = *hp;
-    int hint[2] = {(int)(short)(hv & 0xffff), hv >> 16};
-    if (func == 9) {  // general convex (MPR)
-      float depth, n[3], pp[3];
-      float* tr = (dbg && (int)dbg[DBG_MPR] == p) ? dbg + DBG_MPR : nullptr;
-      const bool hit = mpr_lane(m, s, g1, g2, depth, n, pp, hint, tr);
-      if (tr) {
-        tr[1] = hit ? 1.f : 0.f; tr[2] = depth;
-        tr[3] = n[0]; tr[4] = n[1]; tr[5] = n[2]; tr[6] = pp[0]; tr[7] = pp[1]; tr[8] = pp[2];
-      }
-      *hp = (hint[0] & 0xffff) | (hint[1] << 16);
-      if (hit) {
-        if (n[0] == 0.f && n[1] == 0.f && n[2] == 0.f) n[2] = 1.f;
-        dist[0] = -depth;
-#pragma unroll
-        for (int c = 0; c < 3; c++) { pos[0][c] = pp[c]; nrm[0][c] = n[c]; }
-        // a penetrating polyhedron pair: the caller runs the face-clipping manifold
-        if (m->pair_ncon[p] == 4 && depth > 0.f) return kPendingPoly;
-      }
-      return 1;
-    }
-    if (func == 10 && m->pair_ncon[p] == 4 && m->geom_type[g2] == 5) {
-      // plane - cylinder: MuJoCo's mjc_PlaneCylinder (the oracle's
-      // col_plane_cylinder): deepest rim point, the far cap's on that side,
-      // two near-cap rim points 120 degrees either side of the first
-      const float n[3] = {R1[2], R1[5], R1[8]};
-      float ax[3] = {R2[2], R2[5], R2[8]}, vec[3];
-      float prjaxis = dot3(n, ax);
-      if (prjaxis > 0.f) { ax[0] = -ax[0]; ax[1] = -ax[1]; ax[2] = -ax[2]; prjaxis = -prjaxis; }
-      const float dist0 = n[0] * (x2[0] - x1[0]) + n[1] * (x2[1] - x1[1]) + n[2] * (x2[2] - x1[2]);
-#pragma unroll
-      for (int c = 0; c < 3; c++) vec[c] = ax[c] * prjaxis - n[c];
-      const float len = sqrtf(dot3(vec, vec));
-      if (len < kMinVal) { vec[0] = R2[0]; vec[1] = R2[3]; vec[2] = R2[6]; }
-      else { const float il = 1.f / len; vec[0] *= il; vec[1] *= il; vec[2] *= il; }
-#pragma unroll
-      for (int c = 0; c < 3; c++) { vec[c] *= s2[0]; ax[c] *= s2[1]; }
-      const float prjvec = dot3(vec, n);
-      prjaxis *= s2[1];
-      const float margin = m->pair_margin[p];
-      float d = dist0 + prjaxis + prjvec;
-      dist[0] = d;
-#pragma unroll
-      for (int c = 0; c < 3; c++) { pos[0][c] = x2[c] + vec[c] + ax[c] - 0.5f * d * n[c]; nrm[0][c] = n[c]; }
-      if (d <= margin) {
-        d = dist0 - prjaxis + prjvec;
-        if (d <= margin) {
-          dist[1] = d;
-#pragma unroll
-          for (int c = 0; c < 3; c++) { pos[1][c] = x2[c] + vec[c] - ax[c] - 0.5f * d * n[c]; nrm[1][c] = n[c]; }
-        }
-        d = dist0 + prjaxis - 0.5f * prjvec;
-        if (d <= margin) {
-          float v1[3];
-          cross(v1, vec, ax);
-          const float l1 = sqrtf(dot3(v1, v1));
-          const float sc = l1 > 0.f ? s2[0] * 0.8660254037844386f / l1 : 0.f;
-#pragma unroll
-          for (int k = 0; k < 2; k++) {
-            const float sv = k ? -sc : sc;
-            dist[2 + k] = d;
-#pragma unroll
-            for (int c = 0; c < 3; c++) {
-              pos[2 + k][c] = x2[c] + sv * v1[c] + ax[c] - 0.5f * vec[c] - 0.5f * d * n[c];
-              nrm[2 + k][c] = n[c];
-            }
-          }
-        }
-      }
-      return 4;
-    }
-    if (func == 10) {  // plane - convex: deepest support point
-      float n[3] = {R1[2], R1[5], R1[8]}, nn[3] = {-R1[2], -R1[5], -R1[8]}, q[3];
-      support_geom(m, s, g2, nn, q, hint[1]);
-      *hp = (hint[0] & 0xffff) | (hint[1] << 16);
-      const float d = n[0] * (q[0] - x1[0]) + n[1] * (q[1] - x1[1]) + n[2] * (q[2] - x1[2]);
-      dist[0] = d;
-#pragma unroll
-      for (int c = 0; c < 3; c++) { pos[0][c] = q[c] - 0.5f * d * n[c]; nrm[0][c] = n[c]; }
-      // a penetrating mesh: the caller runs the wave-cooperative manifold
-      return (d < 0.f && m->geom_type[g2] == 7) ? kPendingManifold : 1;
-    }
-  }
-  return 0;
-}
-
-__device__ __forceinline__ void make_frame(float f[9], const float n[3]) {
-  f[0] = n[0]; f[1] = n[1]; f[2] = n[2];
-  float y[3] = {0.f, 1.f, 0.f};
-  if (fabsf(n[1]) >= 0.5f) { y[1] = 0.f; y[2] = 1.f; }
-  float dd = dot3(n, y);
-  y[0] -= dd * n[0]; y[1] -= dd * n[1]; y[2] -= dd * n[2];
-  float ny = sqrtf(dot3(y, y));
-  f[3] = y[0] / ny; f[4] = y[1] / ny; f[5] = y[2] / ny;
-  cross(f + 6, f, f + 3);
-}
-
-__device__ __forceinline__ float impedance(const float* si, float pos, float margin) {
-  float dmin = clampf(si[0], kMinImp, kMaxImp), dmax = clampf(si[1], kMinImp, kMaxImp);
-  float width = si[2], mid = si[3], power = si[4];
-  if (dmin == dmax || width <= kMinVal) return 0.5f * (dmin + dmax);
-  float x = fabsf((pos - margin) / width);
-  if (x >= 1.f) return dmax;
-  if (x <= 0.f) return dmin;
-  float y;
-  if (power == 1.f) y = x;
-  else if (power == 2.f) y = x <= mid ? x * x / mid : 1.f - (1.f - x) * (1.f - x) / (1.f - mid);  // default solimp
-  else if (x <= mid) y = powf(x, power) / powf(mid, power - 1.f);
-  else y = 1.f - powf(1.f - x, power) / powf(1.f - mid, power - 1.f);
-  return dmin + y * (dmax - dmin);
-}
-
-// Box-box, wave-cooperative (one pair, all 64 lanes, uniform control flow):
-// lanes 0..14 evaluate the 15 separating axes, the reference-face clipping
-// (Sutherland-Hodgman against the 4 side planes) runs with one lane per
-// polygon edge and ballot compaction, the >4 selection is done on uniform
-// values.  Same definitions and orders as the oracle's col_box_box.
-// Appends up to 4 contacts to the active list.  Must be called by all lanes.
-template <class S>
-__device__ __forceinline__ void box_box_wave(const DevModel* __restrict__ m, S& s, int p, int lane) {
-  const int g1 = m->pair_g1[p], g2 = m->pair_g2[p];
-  const float margin = m->pair_margin[p];
-  float x1[3], x2[3], axA[3][3], axB[3][3], t[3], ha[3], hb[3];
-#pragma unroll
-  for (int c = 0; c < 3; c++) {
-    x1[c] = s.gxpos[g1][c];
-    x2[c] = s.gxpos[g2][c];
-    t[c] = x2[c] - x1[c];
-    ha[c] = m->geom_size[g1][c];
-    hb[c] = m->geom_size[g2][c];
-  }
-#pragma unroll
-  for (int i = 0; i < 3; i++)
-#pragma unroll
-    for (int c = 0; c < 3; c++) { axA[i][c] = s.gxmat[g1][3 * c + i]; axB[i][c] = s.gxmat[g2][3 * c + i]; }
-  // ---- separating axes, one per lane
-  float L[3] = {0.f, 0.f, 1.f}, sep = -3e38f;
-  bool valid = false;
-  // (per-lane axes read from the LDS frames by index: no select chains)
-  if (lane < 6) {
-    const float* R = s.gxmat[lane < 3 ? g1 : g2];
-    const int ia = lane < 3 ? lane : lane - 3;
-#pragma unroll
-    for (int c = 0; c < 3; c++) L[c] = R[3 * c + ia];
-    valid = true;
-  } else if (lane < 15) {
-    const int i = (lane - 6) / 3, j = (lane - 6) % 3;
-    float ai[3], bj[3];
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-      ai[c] = s.gxmat[g1][3 * c + i];
-      bj[c] = s.gxmat[g2][3 * c + j];
-    }
-    cross(L, ai, bj);
-    const float l = sqrtf(dot3(L, L));
-    valid = l >= 1e-6f;
-    if (valid) { L[0] /= l; L[1] /= l; L[2] /= l; }
-  }
-  if (valid) {
-    float ra = 0.f, rb = 0.f;
-#pragma unroll
-    for (int k = 0; k < 3; k++) { ra += ha[k] * fabsf(dot3(axA[k], L)); rb += hb[k] * fabsf(dot3(axB[k], L)); }
-    sep = fabsf(dot3(t, L)) - ra - rb;
-  }
-  float best_face = -1e30f, best_edge = -1e30f;
-  int face_id = -1, edge_lane = -1;
-#pragma unroll
-  for (int a = 0; a < 6; a++) {
-    const float v = rdlane(sep, a);
-    if (v > best_face) { best_face = v; face_id = a; }
-  }
-#pragma unroll
-  for (int a = 6; a < 15; a++) {
-    const float v = rdlane(sep, a);
-    if (v > -1e30f && v > best_edge) { best_edge = v; edge_lane = a; }
-  }
-  const float best = fmaxf(best_face, best_edge);
-  if (!(best < margin)) return;
-  const bool use_edge = edge_lane >= 0 && best_edge > 0.95f * best_face + 1e-5f;
-  const int src = use_edge ? edge_lane : face_id;
-  float n[3] = {rdlane(L[0], src), rdlane(L[1], src), rdlane(L[2], src)};
-  const float sg = dot3(t, n) >= 0.f ? 1.f : -1.f;
-  n[0] *= sg; n[1] *= sg; n[2] *= sg;
-  const int base = s.ncon;
-  sync();
-  if (use_edge) {
-    const int ei = (edge_lane - 6) / 3, ej = (edge_lane - 6) % 3;
-    float pa[3], pb[3], da[3], db[3];
-#pragma unroll
-    for (int c = 0; c < 3; c++) { pa[c] = x1[c]; pb[c] = x2[c]; }
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-      if (k != ei) {
-        const float s_ = dot3(n, axA[k]) >= 0.f ? 1.f : -1.f;
-#pragma unroll
-        for (int c = 0; c < 3; c++) pa[c] += s_ * ha[k] * axA[k][c];
-      }
-      if (k != ej) {
-        const float s_ = dot3(n, axB[k]) >= 0.f ? -1.f : 1.f;
-#pragma unroll
-        for (int c = 0; c < 3; c++) pb[c] += s_ * hb[k] * axB[k][c];
-      }
-    }
-    const float hae = m->geom_size[g1][ei], hbe = m->geom_size[g2][ej];
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-      const float ae = s.gxmat[g1][3 * c + ei], be = s.gxmat[g2][3 * c + ej];
-      pa[c] -= hae * ae; da[c] = 2.f * hae * ae;
-      pb[c] -= hbe * be; db[c] = 2.f * hbe * be;
-    }
-    float sc, uc;
-    seg_seg(pa, da, pb, db, &sc, &uc);
-    if (lane == 0 && base < S::MAXACT) {
-      float f[9];
-      make_frame(f, n);
-#pragma unroll
-      for (int c = 0; c < 3; c++) s.con_pos[base][c] = 0.5f * (pa[c] + sc * da[c] + pb[c] + uc * db[c]);
-#pragma unroll
-      for (int e = 0; e < S::FRAMEW; e++) s.con_frame[base][e] = f[e];
-      s.con_dist[base] = best_edge;
-      s.con_pair[base] = p;
-    }
-    sync();
-    if (lane == 0) s.ncon = base + 1;
-    sync();
-    return;
-  }
-  // ---- face contact: reference box owns the face axis.  The run-time axis
-  // indices address the boxes' LDS frames and model sizes directly (no
-  // select chains, nothing in scratch); same values as the registers above.
-  const bool refA = face_id < 3;
-  const int fi = refA ? face_id : face_id - 3;
-  const int gr = refA ? g1 : g2, gn = refA ? g2 : g1;
-  const float* Rr = s.gxmat[gr];  // axis k of a box: (R[k], R[3 + k], R[6 + k])
-  const float* Ri = s.gxmat[gn];
-  const float* hr = m->geom_size[gr];
-  const float* hi = m->geom_size[gn];
-  float cr[3], ci[3], nf[3];
-#pragma unroll
-  for (int c = 0; c < 3; c++) {
-    cr[c] = s.gxpos[gr][c];
-    ci[c] = s.gxpos[gn][c];
-    nf[c] = refA ? n[c] : -n[c];
-  }
-  const float d0 = fabsf(Ri[0] * nf[0] + Ri[3] * nf[1] + Ri[6] * nf[2]);
-  const float d1 = fabsf(Ri[1] * nf[0] + Ri[4] * nf[1] + Ri[7] * nf[2]);
-  const float d2 = fabsf(Ri[2] * nf[0] + Ri[5] * nf[1] + Ri[8] * nf[2]);
-  int ki = 0;
-  float bestdot = d0;
-  if (d1 > bestdot) { bestdot = d1; ki = 1; }
-  if (d2 > bestdot) { bestdot = d2; ki = 2; }
-  const int u = ki == 0 ? 1 : (ki == 1 ? 2 : 0), v = ki == 0 ? 2 : (ki == 1 ? 0 : 1);
-  float Ik[3], Iu[3], Iv[3];
-#pragma unroll
-  for (int c = 0; c < 3; c++) {
-    Ik[c] = Ri[3 * c + ki];
-    Iu[c] = Ri[3 * c + u];
-    Iv[c] = Ri[3 * c + v];
-  }
-  const float hk = hi[ki], hu = hi[u], hv = hi[v];
-  const float si = dot3(Ik, nf) > 0.f ? -1.f : 1.f;
-  if (lane < 4) {
-    const float su = (lane == 0 || lane == 3) ? 1.f : -1.f, sv = lane < 2 ? 1.f : -1.f;
-#pragma unroll
-    for (int k = 0; k < 3; k++) s.poly[0][lane][k] = ci[k] + si * hk * Ik[k] + su * hu * Iu[k] + sv * hv * Iv[k];
-  }
-  int np = 4, cur = 0;
-  // fast path: an incident face wholly inside the reference face's 4 side
-  // planes (an object resting inside a table top) passes every clip unchanged
-  // -- Sutherland-Hodgman keeps each vertex and adds no crossing -- so the 4
-  // sequential clips are skipped for exactly the same polygon
-  bool inside = true;
-  sync();
-  if (lane < 4) {
-    const float P[3] = {s.poly[0][lane][0], s.poly[0][lane][1], s.poly[0][lane][2]};
-#pragma unroll
-    for (int pl = 0; pl < 4; pl++) {  // the clip loop's own dp expression
-      const int ax = (fi + 1 + (pl >> 1)) % 3;
-      const float sgn = (pl & 1) ? -1.f : 1.f;
-      const float Ra[3] = {Rr[ax], Rr[3 + ax], Rr[6 + ax]};
-      const float cra = dot3(cr, Ra);
-      inside = inside && sgn * (dot3(P, Ra) - cra) - hr[ax] <= 0.f;
-    }
-  }
-  if (__ballot(!inside) == 0ull) np = -np;  // marker: skip the clips
-  for (int pl = 0; pl < 4 && np > 0; pl++) {
-    sync();
-    const int ax = (fi + 1 + (pl >> 1)) % 3;
-    const float sgn = (pl & 1) ? -1.f : 1.f;
-    const float Ra[3] = {Rr[ax], Rr[3 + ax], Rr[6 + ax]};
-    const float hax = hr[ax];
-    const float cra = dot3(cr, Ra);
-    float P[3] = {0.f, 0.f, 0.f}, Q[3] = {0.f, 0.f, 0.f}, dp = 0.f, dq = 0.f;
-    int e0 = 0, e1 = 0;
-    if (lane < np) {
-      const int c2 = lane + 1 == np ? 0 : lane + 1;
-#pragma unroll
-      for (int k = 0; k < 3; k++) { P[k] = s.poly[cur][lane][k]; Q[k] = s.poly[cur][c2][k]; }
-      dp = sgn * (dot3(P, Ra) - cra) - hax;
-      dq = sgn * (dot3(Q, Ra) - cra) - hax;
-      e0 = dp <= 0.f;
-      e1 = (dp < 0.f && dq > 0.f) || (dp > 0.f && dq < 0.f);
-    }
-    int tot;
-    const int o = wscan_excl(e0 + e1, tot);
-    if (e0) {
-#pragma unroll
-      for (int k = 0; k < 3; k++) s.poly[cur ^ 1][o][k] = P[k];
-    }
-    if (e1) {
-      const float wgt = dp / (dp - dq);
-#pragma unroll
-      for (int k = 0; k < 3; k++) s.poly[cur ^ 1][o + e0][k] = P[k] + wgt * (Q[k] - P[k]);
-    }
-    np = tot;
-    cur ^= 1;
-  }
-  if (np < 0) np = -np;
-  sync();
-  if (np == 0) return;
-  const float hrf = hr[fi];
-  float depth = -3e38f;
-  bool keep = false;
-  if (lane < np) {
-    const float rel[3] = {s.poly[cur][lane][0] - cr[0], s.poly[cur][lane][1] - cr[1], s.poly[cur][lane][2] - cr[2]};
-    depth = hrf - dot3(rel, nf);
-    keep = -depth < margin;
-  }
-  const unsigned long long km = __ballot(keep);
-  const int nkeep = __popcll(km);
-  if (nkeep == 0) return;
-  const int rank = lanes_below(km);  // position of this lane among the kept points
-  int slot = keep ? rank : -1;
-  int npick = nkeep;
-  if (nkeep > 4) {
-    // deepest kept point (first maximum), then evenly spaced around the polygon
-    int d0 = 0;
-    float dbest = -3e38f;
-#pragma unroll
-    for (int c = 0; c < 8; c++) {
-      const float dc = rdlane(depth, c);
-      const bool kc = (km >> c) & 1ull;
-      const int rc = __popcll(km & ((1ull << c) - 1ull));
-      if (kc && dc > dbest) { dbest = dc; d0 = rc; }
-    }
-    slot = -1;
-#pragma unroll
-    for (int q = 0; q < 4; q++)
-      if (keep && rank == (d0 + q * nkeep / 4) % nkeep) slot = q;
-    npick = 4;
-  }
-  if (slot >= 0 && base + slot < S::MAXACT) {
-    const int o = base + slot;
-    float f[9];
-    make_frame(f, n);
-#pragma unroll
-    for (int k = 0; k < 3; k++) s.con_pos[o][k] = s.poly[cur][lane][k] + nf[k] * 0.5f * depth;
-#pragma unroll
-    for (int e = 0; e < S::FRAMEW; e++) s.con_frame[o][e] = f[e];
-    s.con_dist[o] = -depth;
-    s.con_pair[o] = p;
-  }
-  sync();
-  if (lane == 0) s.ncon = base + npick;
-  sync();
-}
-
-// Per-lane contact bookkeeping after a narrow-phase pass: cost_c on the
-// robot-masked slots (SBP/mjx_planner.py:284-296) and ballot-compacted append
-// of the active contacts.  Must be called by all lanes (two barriers).
-// Previous-step masked slot distances (cost_c's history term) of the lane's
-// own pairs, held in registers across the horizon (narrow variant): the lane
-// that owns pair p in 64-pair chunk k owns its <= 4 slots every step, so
-// chunk k < NC keeps them in v[k][0..3] (no per-step HBM slab round trip: the
-// slab's L2 evictions were ~8.6 MB of a C3 launch's 29.7 MB HBM traffic);
-// pairs of later chunks use the slab.  The dual-arm class keeps the slab.
-template <class S>
-struct SlotHist {
-  static constexpr int NC = S::WIDE ? 0 : 128 / WAVE;
-  float v[NC > 0 ? NC : 1][4];
-};
-
-// the active contacts (dist < margin) of pair p into the contact list from
-// position o on (those past MAXACT are dropped; the caller counts them)
-template <class S>
-__device__ __forceinline__ void put_contacts(const DevModel* __restrict__ m, S& s, int o, int p, int nsl,
-                                             const float dist[4], const float pos[4][3], const float nrm[4][3]) {
-  const float mg = m->pair_margin[p];
-#pragma unroll
-  for (int c = 0; c < 4; c++) {
-    if (c < nsl && dist[c] < mg) {
-      if (o < S::MAXACT) {
-        float f[9];
-        make_frame(f, nrm[c]);
-        s.con_pos[o][0] = pos[c][0]; s.con_pos[o][1] = pos[c][1]; s.con_pos[o][2] = pos[c][2];
-#pragma unroll
-        for (int e = 0; e < S::FRAMEW; e++) s.con_frame[o][e] = f[e];
-        s.con_dist[o] = dist[c];
-        s.con_pair[o] = p;
-      }
-      o++;
-    }
-  }
-}
-
-// How a kernel reads its RolloutArgs (KA->field).  The dual-arm kernels read
-// the by-value argument itself, as ever.  The single-arm kernels read each
-// field where it is used, from the kernarg segment (RolloutArgs is the first
-// kernel argument: offset 0), through a pointer laundered at every read: a
-// by-value field is loaded in the prologue and, when it is needed once a step
-// or only in the epilogue, held in scalar registers across the whole horizon
-// loop -- with the masks and model scalars the loop needs that was more than
-// the 106 SGPRs, and the register allocator kept the surplus in VGPR lanes
-// (v_writelane / v_readlane: VALU instructions, and a VALU -> SALU wait in
-// front of every use).  The segment stays in the constant address space, so
-// the reads are s_load from the scalar cache.
-typedef const __attribute__((address_space(4))) RolloutArgs* KernargArgs;
-// Which optional outputs a call asked for (ARGS_HAS): the single-arm kernels
-// keep the answers as bits of one scalar (aflags), taken from the by-value
-// argument in the prologue, and read a pointer only behind its bit.
-enum { AF_TRACE_SLOTS = 1, AF_TRACE_EEF = 2, AF_THETA = 4, AF_TDOUT = 8 };  // AF_TDOUT: thetadot, theta-dot input layout
-// KA->field: the by-value argument (dual-arm kernels) or the laundered kernarg
-// segment (single-arm kernels); `args` is the kernel's by-value parameter or,
-// in a device function, a reference to it
-// The choice is the translation unit's (rollout_wide.hip defines
-// MPCR_ARGS_BY_VALUE before it includes this file; each unit instantiates
-// its own class only): with it the macros below are the text the kernels
-// had, and the dual-arm unit compiles to the code it had.
-#ifdef MPCR_ARGS_BY_VALUE
-#define KA (&args)
-#define KSA (&sa)
-#define KSCEN scen_count(args)
-#define ARGS_HAS(f, expr) (expr)
-#define ARGS_LAST_STEP_FIRST(t, H) true
-#else
-__device__ __forceinline__ KernargArgs karg() {
-  KernargArgs p = (KernargArgs)__builtin_amdgcn_kernarg_segment_ptr();
-  asm volatile("" : "+s"(p));
-  return p;
-}
-#define KA karg()
-__device__ __forceinline__ unsigned args_flags(const RolloutArgs& a) {
-  return (a.trace_slots ? AF_TRACE_SLOTS : 0) | (a.trace_eef ? AF_TRACE_EEF : 0) | (a.theta ? AF_THETA : 0) |
-         (a.layout != 0 && a.thetadot ? AF_TDOUT : 0);
-}
-// ARGS_HAS(bit, the by-value units' own test): laundering the word at the
-// test, so that a bit's test is not hoisted out of the horizon loop as a lane
-// mask, does not compile (inside a divergent region the word may sit in a
-// vector register)
-#define ARGS_HAS(f, expr) ((aflags & (f)) != 0)
-// a test of an argument on the last step only: the step first, the read behind it
-#define ARGS_LAST_STEP_FIRST(t, H) ((t) == (H) - 1)
-// StateArgs the same way (KSA->field; the STATE kernels read it in the
-// kernarg segment, where it lives in RolloutArgs::par's bytes)
-static_assert(offsetof(RolloutArgs, par) % 8 == 0, "StateArgs' pointers aligned inside the kernarg segment");
-typedef const __attribute__((address_space(4))) StateArgs* KernargState;
-__device__ __forceinline__ KernargState ksarg() {
-  const __attribute__((address_space(4))) char* p =
-      (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr();
-  asm volatile("" : "+s"(p));
-  return (KernargState)(p + offsetof(RolloutArgs, par));
-}
-#define KSA ksarg()
-// the scenario count behind it (rollout.h, kScenOff)
-__device__ __forceinline__ int kscen() {
-  const __attribute__((address_space(4))) char* p =
-      (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr();
-  asm volatile("" : "+s"(p));
-  return *(const __attribute__((address_space(4))) int*)(p + offsetof(RolloutArgs, par) + kScenOff);
-}
-#define KSCEN kscen()
-#endif
-// The target schedule behind the scenario count (rollout.h, kTargetOff;
-// KTA->field): both units read it where they use it, once a step, from the
-// kernarg segment through a laundered pointer -- the dual-arm kernels too,
-// whose by-value copy of it held four more scalars across the horizon loop (a
-// fifth spilled VGPR and 32 bytes of scratch in the one-wave kernel)
-static_assert((offsetof(RolloutArgs, par) + kTargetOff) % 8 == 0, "TargetArgs' pointer aligned inside the kernarg segment");
-typedef const __attribute__((address_space(4))) TargetArgs* KernargTarget;
-__device__ __forceinline__ KernargTarget ktarg() {
-  const __attribute__((address_space(4))) char* p =
-      (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr();
-  asm volatile("" : "+s"(p));
-  return (KernargTarget)(p + offsetof(RolloutArgs, par) + kTargetOff);
-}
-#define KTA ktarg()
-
-template <class S>
-__device__ __forceinline__ void emit_contacts(const DevModel* __restrict__ m, S& s, const RolloutArgs& args,
-                                              [[maybe_unused]] unsigned aflags, int b,
-                                              int t, int H, bool valid, int p, int nsl, const float dist[4],
-                                              const float pos[4][3], const float nrm[4][3], float& cost_c,
-                                              SlotHist<S>& sh, int k,
-                                              [[maybe_unused]] const float4* rq = nullptr) {
-  int act = 0;
-  if (valid) {
-    // single-arm kernels: slot address, slot count and margin from the pair's
-    // set-up record, the two quads the chunk loop fetched (rq)
-    float4 q0 = {0.f, 0.f, 0.f, 0.f}, q1 = q0;
-    if constexpr (kStepLoad<S>) {
-      q0 = rq[0];
-      q1 = rq[1];
-    }
-    const int sa = kStepLoad<S> ? __float_as_int(q0.y) : m->pair_slotadr[p];
-    if (sa >= 0) {
-      const int ns = kStepLoad<S> ? __float_as_int(q1.x) >> 16 : m->pair_ncon[p];
-      if constexpr (SlotHist<S>::NC == 2) {
-        // single-arm kernels: the chunk index is the wave's, so a scalar branch
-        // names the chunk's history registers (hv; null: the slab) where
-        // per-slot selects over k read and wrote them
-        auto slots = [&](float* hv) {
-#pragma unroll
-          for (int c = 0; c < 4; c++) {
-            if (c < ns) {
-              const float d = dist[c];
-              if (d < 0.f) cost_c += 1.f;
-              if (hv) {
-                if (t > 0) cost_c += fmaxf(hv[c] * (1.f - 0.005f) - d, 0.f);
-                hv[c] = d;
-              } else {
-                float* cp = KA->slot_prev + (size_t)b * m->nslot;
-                if (t > 0) cost_c += fmaxf(cp[sa + c] * (1.f - 0.005f) - d, 0.f);
-                cp[sa + c] = d;
-              }
-              if (ARGS_HAS(AF_TRACE_SLOTS, KA->trace_slots && b < KA->n)) KA->trace_slots[((size_t)b * H + t) * m->nslot + sa + c] = d;
-            }
-          }
-        };
-        const int ku = __builtin_amdgcn_readfirstlane(k);
-        if (ku == 0) slots(sh.v[0]);
-        else if (ku == 1) slots(sh.v[1]);
-        else slots(nullptr);
-      } else {
-#pragma unroll
-      for (int c = 0; c < 4; c++) {
-        if (c < ns) {
-          const float d = dist[c];
-          if (d < 0.f) cost_c += 1.f;
-          if (SlotHist<S>::NC > 0 && k < SlotHist<S>::NC) {  // this lane's registers (chunk k, slot c)
-            float prev = 0.f;
-#pragma unroll
-            for (int j = 0; j < SlotHist<S>::NC; j++) prev = j == k ? sh.v[j][c] : prev;
-            if (t > 0) cost_c += fmaxf(prev * (1.f - 0.005f) - d, 0.f);
-#pragma unroll
-            for (int j = 0; j < SlotHist<S>::NC; j++) sh.v[j][c] = j == k ? d : sh.v[j][c];
-          } else {
-            float* cp = KA->slot_prev + (size_t)b * m->nslot;
-            if (t > 0) cost_c += fmaxf(cp[sa + c] * (1.f - 0.005f) - d, 0.f);
-            cp[sa + c] = d;
-          }
-          if (ARGS_HAS(AF_TRACE_SLOTS, KA->trace_slots && b < KA->n)) KA->trace_slots[((size_t)b * H + t) * m->nslot + sa + c] = d;
-        }
-      }
-      }
-    }
-    if (!(m->disableflags & 16)) {
-      const float mg = kStepLoad<S> ? q1.w : m->pair_margin[p];
-#pragma unroll
-      for (int c = 0; c < 4; c++) act += (c < nsl && dist[c] < mg) ? 1 : 0;
-    }
-  }
-  int tot;
-  const int pre = wscan_excl(act, tot);
-  const int base = s.ncon;
-  if (act) put_contacts(m, s, base + pre, p, nsl, dist, pos, nrm);
-  sync();
-  if ((threadIdx.x & (WAVE - 1)) == 0) s.ncon = base + tot;
-  sync();
-}
-
-// ---------------------------------------------------------------------------
-// line search point (MJX-style, see oracle)
-
-// cost: complete, or (narrow kernel, full == false) without its constant
-// part q0 (the active rows' 0.5 D jar^2 + the Gauss term), which the bracket
-// never reads: the line search adds it once for the final two points.
-// T: the precision of a point's step size, cost and derivatives and of the
-// bracket arithmetic -- fp64 in the dual-arm class (LsReal): the point's cost
-// alpha^2 q2 + alpha q1 + q0 cancels a ~1e4 constant to compare candidates
-// that differ in the last fp32 bits, and the bracket's Newton steps
-// alpha - d0 / d1 divide two such differences; in fp32 those decisions
-// halved the dual arm's parity (78 -> 37 well-conditioned
-// misses of the fp32 restatement against fp64).  The row sums stay fp32.
-template <class T>
-struct LsPtT { T alpha, cost, d0, d1; bool full; };
-template <class S>
-using LsReal = typename std::conditional<S::WIDE, double, float>::type;
-
-// elliptic rows: efc_src = (5 << 24) | (contact << 14) | (pair << 4) | side
-__device__ __forceinline__ bool ell_row(int src) { return (src >> 24) == 5; }
-__device__ __forceinline__ bool ell_head(int src) { return (src >> 24) == 5 && (src & 15) == 0; }
-__device__ __forceinline__ int ell_pair(int src) { return (src >> 4) & 1023; }
-
-
-// the row's side of its kink at the step size alpha (in alpha's precision)
-template <class T>
-__device__ __forceinline__ bool ls_neg(float jar, float jv, T alpha) {
-  return (T)jar + alpha * (T)jv < (T)0;
-}
-
-template <class S, class T>
-__device__ __forceinline__ void ls_rows(const S& s, int lane, T alpha, float& q0, float& q1, float& q2) {
-  q0 = q1 = q2 = 0.f;
-  for (int r = lane; r < s.nefc; r += WAVE) {
-    float jar = s.efc_jar[r], jv = s.efc_jv[r];
-    if constexpr (S::WIDE) {
-      if (ell_row(s.efc_src[r])) continue;
-    }
-    if (((s.efc_src[r] >> 24) == 1) || ls_neg(jar, jv, alpha)) {
-      float D = s.efc_D[r];
-      q0 += 0.5f * D * jar * jar;
-      q1 += D * jv * jar;
-      q2 += 0.5f * D * jv * jv;
-    }
-  }
-}
-
-template <class T>
-__device__ __forceinline__ LsPtT<T> ls_make(T alpha, T q0, T q1, T q2) {
-  LsPtT<T> p;
-  p.alpha = alpha;
-  p.cost = alpha * alpha * q2 + alpha * q1 + q0;
-  p.d0 = (T)2 * alpha * q2 + q1;
-  p.d1 = (T)2 * q2 + (q2 == (T)0 ? (T)kMinVal : (T)0);
-  p.full = true;
-  return p;
-}
-
-template <class S, bool Q0 = true, class T = LsReal<S>>
-__device__ __forceinline__ LsPtT<T> ls_eval(const S& s, int lane, const float qg[3], T alpha) {
-  float q0, q1, q2;
-  ls_rows(s, lane, alpha, q0, q1, q2);
-  if constexpr (Q0) wsum3(q0, q1, q2); else wsum2(q1, q2);
-  q0 = Q0 ? q0 + qg[0] : 0.f;
-  q1 = q1 + qg[1];
-  q2 = q2 + qg[2];
-  LsPtT<T> p = ls_make<T>(alpha, q0, q1, q2);
-  p.full = Q0;
-  return p;
-}
-// the deferred constant parts of two line-search points in one row pass
-template <class S, class T>
-__device__ __forceinline__ void ls_finish(const S& s, int lane, const float qg[3], LsPtT<T>& a, LsPtT<T>& b) {
-  float qa = 0.f, qb = 0.f;
-  for (int r = lane; r < s.nefc; r += WAVE) {
-    const float jar = s.efc_jar[r], jv = s.efc_jv[r];
-    const bool eq = (s.efc_src[r] >> 24) == 1;
-    const float c0 = 0.5f * s.efc_D[r] * jar * jar;
-    if (eq || ls_neg(jar, jv, a.alpha)) qa += c0;
-    if (eq || ls_neg(jar, jv, b.alpha)) qb += c0;
-  }
-  wsum2(qa, qb);
-  qa = qa + qg[0];
-  qb = qb + qg[0];
-  if (!a.full) { a.cost = a.cost + qa; a.full = true; }
-  if (!b.full) { b.cost = b.cost + qb; b.full = true; }
-}
-
-// three line-search points in one pass over the rows; the 9 reductions are
-// independent so their DPP chains interleave
-template <class S, bool Q0 = true, class T = LsReal<S>>
-__device__ __forceinline__ void ls_eval3(const S& s, int lane, const float qg[3], T a0, T a1, T a2,
-                                         LsPtT<T>& p0, LsPtT<T>& p1, LsPtT<T>& p2) {
-  float q[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  const T al[3] = {a0, a1, a2};
-  for (int r = lane; r < s.nefc; r += WAVE) {
-    const float jar = s.efc_jar[r], jv = s.efc_jv[r], D = s.efc_D[r];
-    const bool eq = (s.efc_src[r] >> 24) == 1;
-    if constexpr (S::WIDE) {
-      if (ell_row(s.efc_src[r])) continue;
-    }
-    const float c0 = 0.5f * D * jar * jar, c1 = D * jv * jar, c2 = 0.5f * D * jv * jv;
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-      if (eq || ls_neg(jar, jv, al[k])) { q[3 * k] += c0; q[3 * k + 1] += c1; q[3 * k + 2] += c2; }
-    }
-  }
-  if constexpr (Q0) {
-    wsum3(q[0], q[1], q[2]);
-    wsum3(q[3], q[4], q[5]);
-    wsum3(q[6], q[7], q[8]);
-  } else {
-    wsum3(q[1], q[2], q[4]);
-    wsum3(q[5], q[7], q[8]);
-  }
-#pragma unroll
-  for (int k = 0; k < 9; k++) q[k] = (Q0 || k % 3) ? q[k] + qg[k % 3] : 0.f;
-  p0 = ls_make<T>(a0, q[0], q[1], q[2]);
-  p1 = ls_make<T>(a1, q[3], q[4], q[5]);
-  p2 = ls_make<T>(a2, q[6], q[7], q[8]);
-  p0.full = p1.full = p2.full = Q0;
-}
-
-// ---------------------------------------------------------------------------
-// elliptic friction cone of one condim-3 contact (rows n, t1, t2; equal
-// sliding frictions), MuJoCo's primal three-zone cost (oracle: ell_update /
-// ell_line).  N = mu x_n, U = fri x_t, T = |U|:
-//   top    N >= mu T        no cost
-//   bottom mu N + T <= 0    0.5 sum D_k x_k^2
-//   middle                  0.5 Dm (N - mu T)^2, Dm = D_n / (mu^2 (1 + mu^2))
-
-// cost; f = -dcost/dx; h = Hessian (h00 h01 h02 h11 h12 h22)
-__device__ __forceinline__ float cone_update(const float x[3], float mu, float fri, const float D[3], float f[3],
-                                             float h[6]) {
-  const float N = mu * x[0], U0 = fri * x[1], U1 = fri * x[2], T = sqrtf(U0 * U0 + U1 * U1);
-  if (N >= mu * T || (T <= 0.f && N >= 0.f)) {
-    f[0] = f[1] = f[2] = 0.f;
-#pragma unroll
-    for (int k = 0; k < 6; k++) h[k] = 0.f;
-    return 0.f;
-  }
-  if (mu * N + T <= 0.f || (T <= 0.f && N < 0.f)) {
-    f[0] = -D[0] * x[0]; f[1] = -D[1] * x[1]; f[2] = -D[2] * x[2];
-    h[0] = D[0]; h[1] = 0.f; h[2] = 0.f; h[3] = D[1]; h[4] = 0.f; h[5] = D[2];
-    return 0.5f * (D[0] * x[0] * x[0] + D[1] * x[1] * x[1] + D[2] * x[2] * x[2]);
-  }
-  const float Dm = D[0] / (mu * mu * (1.f + mu * mu)), phi = N - mu * T, iT = 1.f / T;
-  const float g[3] = {mu, -mu * fri * U0 * iT, -mu * fri * U1 * iT};
-  f[0] = -Dm * phi * g[0]; f[1] = -Dm * phi * g[1]; f[2] = -Dm * phi * g[2];
-  const float c = -Dm * phi * mu * fri * fri * iT, u0 = U0 * iT, u1 = U1 * iT;
-  h[0] = Dm * g[0] * g[0];
-  h[1] = Dm * g[0] * g[1];
-  h[2] = Dm * g[0] * g[2];
-  h[3] = Dm * g[1] * g[1] + c * (1.f - u0 * u0);
-  h[4] = Dm * g[1] * g[2] - c * u0 * u1;
-  h[5] = Dm * g[2] * g[2] + c * (1.f - u1 * u1);
-  return 0.5f * Dm * phi * phi;
-}
-
-// cost and its first two derivatives along x + alpha v (zones at alpha)
-template <class A>
-__device__ __forceinline__ void cone_line(const float x0[3], const float v[3], A alpha, float mu, float fri,
-                                          const float D[3], float& c0, float& c1, float& c2) {
-  const float x[3] = {(float)((A)x0[0] + alpha * (A)v[0]), (float)((A)x0[1] + alpha * (A)v[1]),
-                      (float)((A)x0[2] + alpha * (A)v[2])};
-  const float N = mu * x[0], U0 = fri * x[1], U1 = fri * x[2], W0 = fri * v[1], W1 = fri * v[2];
-  const float T = sqrtf(U0 * U0 + U1 * U1);
-  if (N >= mu * T || (T <= 0.f && N >= 0.f)) { c0 = c1 = c2 = 0.f; return; }
-  if (mu * N + T <= 0.f || (T <= 0.f && N < 0.f)) {
-    c0 = 0.5f * (D[0] * x[0] * x[0] + D[1] * x[1] * x[1] + D[2] * x[2] * x[2]);
-    c1 = D[0] * x[0] * v[0] + D[1] * x[1] * v[1] + D[2] * x[2] * v[2];
-    c2 = D[0] * v[0] * v[0] + D[1] * v[1] * v[1] + D[2] * v[2] * v[2];
-    return;
-  }
-  const float Dm = D[0] / (mu * mu * (1.f + mu * mu));
-  const float T1 = (U0 * W0 + U1 * W1) / T, T2 = (W0 * W0 + W1 * W1 - T1 * T1) / T;
-  const float phi = N - mu * T, phi1 = mu * v[0] - mu * T1, phi2 = -mu * T2;
-  c0 = 0.5f * Dm * phi * phi;
-  c1 = Dm * phi * phi1;
-  c2 = Dm * (phi1 * phi1 + phi * phi2);
-}
-
-template <class S>
-__device__ __forceinline__ const float* jrow_ptr(const S& s, const float* gx, int r) {
-  return (S::JL == S::MAXEFC || r < S::JL) ? &s.J[r][0] : gx + (r - S::JL) * S::LDJ;
-}
-
-// line-search extra terms of the elliptic contacts at three step sizes
-template <class S, class T>
-__device__ __forceinline__ void ls_cones3(const S& s, const DevModel* __restrict__ m, int lane, const T al[3],
-                                          float e[9]) {
-#pragma unroll
-  for (int k = 0; k < 9; k++) e[k] = 0.f;
-  for (int r = lane; r < s.nefc; r += WAVE) {
-    const int src = s.efc_src[r];
-    if (!ell_head(src)) continue;
-    const int p = ell_pair(src);
-    const float x[3] = {s.efc_jar[r], s.efc_jar[r + 1], s.efc_jar[r + 2]};
-    const float v[3] = {s.efc_jv[r], s.efc_jv[r + 1], s.efc_jv[r + 2]};
-    const float D[3] = {s.efc_D[r], s.efc_D[r + 1], s.efc_D[r + 2]};
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-      float c0, c1, c2;
-      cone_line(x, v, al[k], m->pair_cmu[p], m->pair_friction[p], D, c0, c1, c2);
-      e[3 * k] += c0; e[3 * k + 1] += c1; e[3 * k + 2] += c2;
-    }
-  }
-  wsum3(e[0], e[1], e[2]);
-  wsum3(e[3], e[4], e[5]);
-  wsum3(e[6], e[7], e[8]);
-}
-
-template <class T>
-__device__ __forceinline__ void ls_add(LsPtT<T>& p, float c0, float c1, float c2) {
-  p.cost += (T)c0;
-  p.d0 += (T)c1;
-  p.d1 = p.d1 - (p.d1 == (T)kMinVal ? (T)kMinVal : (T)0) + (T)c2;
-  if (p.d1 == (T)0) p.d1 = (T)kMinVal;
-}
 
 // Re-derive the model pointer from the kernel argument through an opaque
 // zero offset.  The compiler then cannot hoist loop-invariant model loads out
@@ -2862,71 +60,14 @@ __device__ __forceinline__ void ls_add(LsPtT<T>& p, float c0, float c1, float c2
 // The dual-arm kernel too: 256 -> 241 VGPRs, scratch 304 -> 144 B, C4 49.7 -> 48.6 ms.
 // (Once per step only: launders at the phase boundaries as well were not kept.)
 #define LAUNDER_LANE() asm volatile("" : "+v"(lane))
-// The debug dump's test (candidate 0's last step, RolloutArgs::dbg given).  The
-// single-arm kernels test the step and the candidate first, values the loop
-// holds anyway, and read the pointer only behind them: no register and no
-// load for the dump in any other step.
-#ifdef MPCR_ARGS_BY_VALUE
-#define DBG_LAST() (KA->dbg && b == 0 && t == H - 1)
-#else
-#define DBG_LAST() (t == H - 1 && b == 0 && KA->dbg)
-#endif
-
-// ---------------------------------------------------------------------------
-// J row access: rows < JL in LDS, the rest in the block's HBM slab gx.  The
-// branches are per lane, and the HBM side is skipped (execz) unless a lane
-// has a row past JL.
-
-template <class S>
-__device__ __forceinline__ void jstore(S& s, float* gx, int r, int i, float v) {
-  if (S::JL == S::MAXEFC || r < S::JL) s.J[r][i] = v;
-  else gx[(r - S::JL) * S::LDJ + i] = v;
-}
-template <class S>
-__device__ __forceinline__ float jdot(const S& s, const float* gx, int r, const float* vec) {
-  if (S::JL == S::MAXEFC || r < S::JL) return dotN<S::NVW>(s.J[r], vec);
-  return dotN<S::NVW>(gx + (r - S::JL) * S::LDJ, vec);
-}
-// body(row pointer, r) over rows r = r0, r0 + step, ... < nefc: the LDS rows,
-// then the slab rows (two loops, no per-row address-space select)
-template <class S, class F>
-__device__ __forceinline__ void jrows(const S& s, const float* gx, int r0, int step, int nefc, F&& body) {
-  const int n1 = nefc < S::JL ? nefc : S::JL;
-  for (int r = r0; r < n1; r += step) body(&s.J[r][0], r);
-  if constexpr (S::JL < S::MAXEFC) {
-    for (int r = S::JL + r0; r < nefc; r += step) body(gx + (r - S::JL) * S::LDJ, r);
-  }
-}
+// The problem of the call's candidate gi (several problems in one call,
+// RolloutArgs::prob_n; 0: one problem).  A macro, so the single-arm kernels read
+// prob_n before they evaluate gi, in the order the expression is written.
+#define PROBLEM_OF(gi) (KA->prob_n ? (gi) / KA->prob_n : 0)
 
 // ---------------------------------------------------------------------------
 // the kernel
 
-// narrow variant: the Newton gradient J^T f and Hessian J^T D J on the matrix
-// core (v_mfma_f32_16x16x4_f32) instead of per-row VALU loops
-typedef float mfx4 __attribute__((ext_vector_type(4)));
-typedef float mfx16 __attribute__((ext_vector_type(16)));
-// narrow variant: the chain / subtree sums of the dynamics (CRB, body
-// velocities, cdof_dot, RNE accelerations, bias forces) and the mass matrix as
-// 16 x 16 (x 16) products on the matrix core: a 0/1 (or qvel-weighted) chain
-// mask times per-dof / per-body rows.  v_mfma_f32_16x16x4_f32 is a k-ordered
-// fmaf chain, and the products are the loops' own (qvel x cdof, fvec x cdof),
-// so the results are bitwise the per-lane loops'
-// acc + A B over k < 16 (4 instructions): lane l supplies A[l & 15][k] =
-// af(l & 15, k) and B[k][l & 15] = bf(k, l & 15) for its k = 4 s + (l >> 4);
-// register v of lane l then holds row 4 (l >> 4) + v, column l & 15
-template <int KB, class AF, class BF>
-__device__ __forceinline__ mfx4 mm16(AF&& af, BF&& bf, mfx4 acc, int lane) {
-  const int i = lane & 15, kq = lane >> 4;
-#pragma unroll
-  for (int s4 = 0; s4 < KB; s4++) {
-    const int k = 4 * s4 + kq;
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(af(i, k), bf(k, i), acc, 0, 0, 0);
-  }
-  return acc;
-}
-// the same for the 32-wide (dual-arm) Newton on v_mfma_f32_32x32x2_f32
-// (neutral while the 32-wide readlane Cholesky dominated; with the blocked
-// per-tree solve C4 66.2 -> 65.2 ms)
 // Two waves per candidate, dual-arm class: wave 1 builds each Newton
 // iteration's Hessian while wave 0 forms J^T f, the gradient and the stop
 // test, and the implicit solve's blocked factor of M + dt D during Newton
@@ -2938,42 +79,6 @@ __device__ __forceinline__ mfx4 mm16(AF&& af, BF&& bf, mfx4 acc, int lane) {
 // AGPRs; uncapped it took 274 and ran 1 wave/SIMD): with its 21.6 KB image,
 // 7 blocks per CU instead of 4 (dual arm 4096 x 50: 47.5 -> 35.8 ms).
 constexpr int kWideWavesPerSimd = 2, kNarrowWavesPerSimd = 4;
-
-// 32-wide: acc += sum over constraint rows, two per v_mfma_f32_32x32x2_f32
-// (lane (gi, gq) supplies A = J[r0 + gq][gi] and B = bf(r, A)).  Rows < JL
-// come from LDS; the HBM-slab rows (heavily constrained candidates: 100+
-// rows) are read four row pairs at a time with the loads issued together,
-// instead of one dependent flat load per instruction.  Same MFMAs in the same
-// row order (pairs wholly past nefc skipped): bitwise the single loop.
-template <class S, class BF>
-__device__ __forceinline__ mfx16 mfma_rows32(const S& s, const float* gx, int nefc, int gi, int gq, BF&& bf,
-                                             mfx16 acc) {
-  static_assert(S::JL % 2 == 0, "a row group never straddles the LDS / slab boundary");
-  const int n1 = nefc < S::JL ? nefc : S::JL;
-  for (int r0 = 0; r0 < n1; r0 += 2) {
-    const int r = r0 + gq;
-    const bool ok = r < nefc;
-    const float a = ok ? s.J[r][gi] : 0.f;
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, ok ? bf(r, a) : 0.f, acc, 0, 0, 0);
-  }
-  if constexpr (S::JL < S::MAXEFC) {
-    for (int r0 = S::JL; r0 < nefc; r0 += 8) {
-      float a[4];
-#pragma unroll
-      for (int u = 0; u < 4; u++) {
-        const int r = r0 + 2 * u + gq;
-        a[u] = r < nefc ? gx[(r - S::JL) * S::LDJ + gi] : 0.f;
-      }
-#pragma unroll
-      for (int u = 0; u < 4; u++) {
-        const int r = r0 + 2 * u + gq;
-        if (r0 + 2 * u < nefc)
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u], r < nefc ? bf(r, a[u]) : 0.f, acc, 0, 0, 0);
-      }
-    }
-  }
-  return acc;
-}
 
 // WPC = waves per candidate.  WPC = 2 (narrow variant, small batches: one
 // candidate per SIMD or fewer): wave 1 runs the collision
@@ -2994,7 +99,7 @@ __device__ __forceinline__ mfx16 mfma_rows32(const S& s, const float* gx, int ne
 // 1.542 ms).  In the other instantiations the STATE terms below fold away at
 // compile time.  Never the plant (plant = 0).
 // SCEN: a STATE batch whose problems come in groups of scenarios that share
-// their input rows (rollout.h, scen_count > 1; mpcr_rollout_cost_scenarios).
+// their input rows (rollout.h, CallBlocks::nscen > 1; mpcr_rollout_cost_scenarios).
 // Its own instantiation once more, on top of the STATE one, so the twelve
 // others compile to the code they had, spill counts included -- and under
 // the names they had: the flag rides on the waves-per-candidate argument
@@ -3011,7 +116,7 @@ __global__ void __launch_bounds__(WAVE * (WPCS & 3), WIDE ? kWideWavesPerSimd : 
   static_assert(STATE || !SCEN, "scenarios are problems of a STATE launch");
 #ifdef MPCR_ARGS_BY_VALUE
   StateArgs sa = {nullptr, nullptr, 0, 0, 0, nullptr, nullptr, 0, 0};
-  if constexpr (STATE) sa = state_args(args);
+  if constexpr (STATE) sa = args.blk.st;
   constexpr unsigned aflags = 0;
 #else
   // (this unit reads the arguments where it uses them: KA, KSA, ARGS_HAS)
@@ -3178,15 +283,15 @@ __global__ void __launch_bounds__(WAVE * (WPCS & 3), WIDE ? kWideWavesPerSimd : 
   const float* st_in = nullptr;  // STATE: the problem's start block (null: the template)
   if constexpr (MULTI) {
     // the candidate's problem (mpcr_rollout_cost_multi): wave-uniform, scalar
-    const int pr = KA->prob_n ? (KA->prob_off + b) / KA->prob_n : 0;
+    const int pr = PROBLEM_OF(KA->prob_off + b);
     const float* dp = KA->dpar + (size_t)pr * PAR_N;
     if (lane < PAR_N) s.par[lane] = dp[lane];
     if constexpr (STATE) {
       if (KSA->start) st_in = KSA->start + (size_t)pr * KSA->start_stride;
       // the problem's target schedule (TargetArgs), its offset in rows' quads
       // (strides are multiples of 4 floats; the host bounds it, rollout_call),
-      // parked in the image's spare word: no scalar lives across the step for it
-      if (lane == 0) s.cprev_pad_ = __uint_as_float((unsigned)(((size_t)pr * (unsigned)KTA->stride) >> 2));
+      // kept in the image: no scalar lives across the step for it
+      if (lane == 0) s.tgt_quad0 = (unsigned)(((size_t)pr * (unsigned)KTA->stride) >> 2);
     }
   } else {
     if (lane < PAR_N) s.par[lane] = KA->dpar ? KA->dpar[lane] : KA->par[lane];
@@ -3290,7 +395,7 @@ __global__ void __launch_bounds__(WAVE * (WPCS & 3), WIDE ? kWideWavesPerSimd : 
   // pair; the values themselves are loaded again every step.
   const float* ctrl_p = nullptr;
   if constexpr (STATE && S::WIDE) {
-    if (KSA->ctrl) ctrl_p = KSA->ctrl + (size_t)(KA->prob_n ? (KA->prob_off + b) / KA->prob_n : 0) * KSA->ctrl_stride;
+    if (KSA->ctrl) ctrl_p = KSA->ctrl + (size_t)PROBLEM_OF(KA->prob_off + b) * KSA->ctrl_stride;
   }
   // STATE: the problem's geom-pose block (StateArgs::geom_pose; null: the
   // model's own static poses, geom_pos / geom_quat).  Wave-uniform, a scalar
@@ -3298,7 +403,7 @@ __global__ void __launch_bounds__(WAVE * (WPCS & 3), WIDE ? kWideWavesPerSimd : 
   const float* gpose_p = nullptr;
   if constexpr (STATE) {
     if (KSA->geom_pose)
-      gpose_p = KSA->geom_pose + (size_t)(KA->prob_n ? (KA->prob_off + b) / KA->prob_n : 0) * KSA->geom_stride;
+      gpose_p = KSA->geom_pose + (size_t)PROBLEM_OF(KA->prob_off + b) * KSA->geom_stride;
   }
   PROF_DECL
   unsigned* pace = nullptr;
@@ -3460,7 +565,7 @@ __global__ void __launch_bounds__(WAVE * (WPCS & 3), WIDE ? kWideWavesPerSimd : 
     [[maybe_unused]] auto target_load = [&](float4& p, float4& q) -> bool {
       const float* tg = KTA->target;
       if (!tg || lane != 0) return false;
-      const float4* row = reinterpret_cast<const float4*>(tg) + __float_as_uint(s.cprev_pad_) +
+      const float4* row = reinterpret_cast<const float4*>(tg) + s.tgt_quad0 +
                           (((size_t)t * (unsigned)KTA->step_stride) >> 2);
       p = row[0];
       q = row[1];
@@ -5546,7 +2651,7 @@ __global__ void __launch_bounds__(WAVE * (WPCS & 3), WIDE ? kWideWavesPerSimd : 
       const uint32_t u = __float_as_uint(cost);
       uint32_t key = isnan(cost) ? 0u : ((u & 0x80000000u) ? ~u : (u | 0x80000000u));
       if constexpr (MULTI) {  // problem pr's key, the index within the problem
-        const int gi = KA->prob_off + b, pr = KA->prob_n ? gi / KA->prob_n : 0;
+        const int gi = KA->prob_off + b, pr = PROBLEM_OF(gi);
         const int li = KA->prob_n ? gi - pr * KA->prob_n : gi;
         const unsigned long long k64 = ((unsigned long long)key << 32) | (uint32_t)(KA->index_base + li);
         atomicMin(KA->best_key + pr, k64);

@@ -5,7 +5,7 @@
 // scalar fp32 restatement's drift (C4 shard well-conditioned misses 22 -> 8,
 // worst 4.8e-3 -> 7.8e-4).
 // the dual-arm kernels read their arguments from the by-value parameter, as
-// ever (rollout.hip, KA / KSA): this unit's device code stays what it was
+// ever (kernarg.h, KA / KSA): this unit's device code stays what it was
 #define MPCR_ARGS_BY_VALUE 1
 #include "rollout.hip"
 
@@ -27,7 +27,7 @@ void rollout_wide_launch(int wpc, unsigned grid, hipStream_t st, const RolloutAr
     hipLaunchKernelGGL((rollout_kernel<32, 32, 72, true, 2, true, true>), dim3(grid), dim3(2 * WAVE), 0, st, a, dm);
   else if (!scenarios(a))
     hipLaunchKernelGGL((rollout_kernel<32, 32, 72, true, 1, true, true>), dim3(grid), dim3(WAVE), 0, st, a, dm);
-  // scenarios (scen_count > 1): the SCEN instantiations, named after every other
+  // scenarios (CallBlocks::nscen > 1): the SCEN instantiations, named after every other
   else if (wpc == 2)
     hipLaunchKernelGGL((rollout_kernel<32, 32, 72, true, 2 + WPCS_SCEN, true, true>), dim3(grid), dim3(2 * WAVE), 0, st, a,
                        dm);

@@ -162,13 +162,13 @@ int main(int argc, char** argv) {
     RolloutArgs a;
     memset(&a, 0, sizeof(a));
     a.dpar = dummy;
-    set_state_args(a, StateArgs{nullptr, nullptr, 0, 0, 0, nullptr, nullptr, 0, 0});
+    a.blk.st = StateArgs{nullptr, nullptr, 0, 0, 0, nullptr, nullptr, 0, 0};
     if (has_state(a)) { printf("FAIL has_state: true without any block\n"); return 1; }
-    set_state_args(a, StateArgs{nullptr, nullptr, 0, 0, 0, nullptr, dummy, 16, 8});
+    a.blk.st = StateArgs{nullptr, nullptr, 0, 0, 0, nullptr, dummy, 16, 8};
     if (!has_state(a)) { printf("FAIL has_state: false for geom_pose alone\n"); return 1; }
-    const StateArgs s = state_args(a);
+    const StateArgs s = a.blk.st;
     if (s.geom_pose != dummy || s.geom_stride != 16 || s.geom_step_stride != 8 || s.ctrl || s.start || s.final_state) {
-      printf("FAIL state_args: round trip\n");
+      printf("FAIL StateArgs: round trip\n");
       return 1;
     }
     a.dpar = nullptr;

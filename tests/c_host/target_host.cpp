@@ -1,7 +1,7 @@
 // A stand-alone host of what csrc/rollout.h holds for the target schedule as
 // a call input (no libmpcr, nothing launched, no GPU opened): the bytes of
 // RolloutArgs::par a call with a device parameter block carries its blocks
-// in.  It checks
+// in (CallBlocks, RolloutArgs::blk).  It checks
 //   - sizeof(StateArgs) == 56 with the field offsets it had;
 //   - the scenario count round-trips at byte 56;
 //   - the target arguments round-trip at bytes 64..80, and neither the
@@ -29,7 +29,8 @@ static_assert(offsetof(StateArgs, start) == 0 && offsetof(StateArgs, final_state
                   offsetof(StateArgs, geom_pose) == 40 && offsetof(StateArgs, geom_stride) == 48 &&
                   offsetof(StateArgs, geom_step_stride) == 52,
               "StateArgs keeps its field order");
-static_assert(kScenOff == 56 && kTargetOff == 64 && sizeof(TargetArgs) == 16 && sizeof(float) * PAR_N == 80,
+static_assert(offsetof(CallBlocks, nscen) == 56 && offsetof(CallBlocks, tg) == 64 && sizeof(TargetArgs) == 16 &&
+                  sizeof(float) * PAR_N == 80 && sizeof(CallBlocks) == 80 && offsetof(CallBlocks, st) == 0,
               "the count at 56, the target schedule at 64..80");
 static_assert(offsetof(TargetArgs, target) == 0 && offsetof(TargetArgs, stride) == 8 &&
                   offsetof(TargetArgs, step_stride) == 12,
@@ -57,26 +58,26 @@ int main() {
     RolloutArgs a;
     memset(&a, 0, sizeof(a));
     a.dpar = dummy;
-    set_scen_count(a, 5);
+    a.blk.nscen = 5;
     int n = 0;
     memcpy(&n, reinterpret_cast<const char*>(a.par) + 56, sizeof(n));
-    if (n != 5 || scen_count(a) != 5) return fail("scenario count at offset 56");
-    set_target_args(a, tg);
+    if (n != 5 || a.blk.nscen != 5) return fail("scenario count at offset 56");
+    a.blk.tg = tg;
     const float* p = nullptr;
     int st[2] = {0, 0};
     memcpy(&p, reinterpret_cast<const char*>(a.par) + 64, sizeof(p));
     memcpy(st, reinterpret_cast<const char*>(a.par) + 72, sizeof(st));
     if (p != tg.target || st[0] != 96 || st[1] != 8) return fail("target arguments at offsets 64, 72, 76");
-    if (scen_count(a) != 5) return fail("the target arguments disturbed the scenario count");
-    set_state_args(a, full);
-    if (!same_state(state_args(a), full)) return fail("state_args round trip");
-    TargetArgs t = target_args(a);
-    if (t.target != tg.target || t.stride != 96 || t.step_stride != 8 || scen_count(a) != 5)
+    if (a.blk.nscen != 5) return fail("the target arguments disturbed the scenario count");
+    a.blk.st = full;
+    if (!same_state(a.blk.st, full)) return fail("StateArgs round trip");
+    TargetArgs t = a.blk.tg;
+    if (t.target != tg.target || t.stride != 96 || t.step_stride != 8 || a.blk.nscen != 5)
       return fail("the StateArgs disturbed the count or the target arguments");
-    set_scen_count(a, 3);
-    set_target_args(a, TargetArgs{nullptr, 0, 0});
-    if (!same_state(state_args(a), full) || scen_count(a) != 3) return fail("clearing the target disturbed the rest");
-    t = target_args(a);
+    a.blk.nscen = 3;
+    a.blk.tg = TargetArgs{nullptr, 0, 0};
+    if (!same_state(a.blk.st, full) || a.blk.nscen != 3) return fail("clearing the target disturbed the rest");
+    t = a.blk.tg;
     if (t.target || t.stride || t.step_stride) return fail("cleared target arguments");
     // bytes 60..64 stay what they were (zero)
     int pad = 1;
@@ -93,9 +94,9 @@ int main() {
           a.dpar = with_dpar ? dummy : nullptr;
           StateArgs s = none;
           if (with_state) s.geom_pose = dummy;
-          set_state_args(a, s);
-          set_scen_count(a, nscen);
-          set_target_args(a, with_target ? tg : TargetArgs{nullptr, 0, 0});
+          a.blk.st = s;
+          a.blk.nscen = nscen;
+          a.blk.tg = with_target ? tg : TargetArgs{nullptr, 0, 0};
           const bool want_state = with_dpar && (with_state || nscen > 1 || with_target);
           const int want_scen = with_dpar && nscen > 1 ? nscen : 0;
           if (has_state(a) != want_state || scenarios(a) != want_scen) {

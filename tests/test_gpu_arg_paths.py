@@ -1,5 +1,5 @@
 """The single-arm kernels read their launch arguments where they use them
-(csrc/rollout.hip, KA / KSA: the kernarg segment, not registers held
+(csrc/kernarg.h, KA / KSA: the kernarg segment, not registers held
 across the horizon loop).  Such a read can go wrong only where an argument is
 optional or offset, so every optional output is left out in turn, the best
 key's index base is moved, and the same trajectories go in through the other

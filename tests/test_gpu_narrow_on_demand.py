@@ -1,6 +1,6 @@
 """The single-arm kernels compute a pair's distances on every lane and a
 capsule-box point's contact position and normal only where the point is
-emitted as a contact (csrc/rollout.hip, narrow_lane).  An engine created with
+emitted as a contact (csrc/narrow_lane.h, narrow_lane).  An engine created with
 MPCR_NARROW_EAGER=1 computes them on every lane; both must give the same bits
 -- costs, theta, thetadot, status and final states -- on every single-arm
 scene and kernel variant.

@@ -249,7 +249,7 @@ def test_plant_hande_scene_free_running(torch_cuda):
 
 
 def test_dual_arm_large_hull_plane_manifold_matches_oracle(torch_cuda):
-    """The wave-cooperative plane-mesh manifold (csrc/rollout.hip
+    """The wave-cooperative plane-mesh manifold (csrc/manifold.h
     plane_mesh_manifold_wave) on the hulls of >= 600 vertices: a C4 candidate
     whose gripper and wrist meshes land on the table (tools/diag_manifold.py,
     candidate 2989 of the seed-20250632 batch: 36 steps with 4-point mesh

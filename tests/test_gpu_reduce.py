@@ -1,4 +1,4 @@
-"""The rollout kernels' wave reductions (csrc/rollout.hip: wsum, wsum2, wsum3,
+"""The rollout kernels' wave reductions (csrc/wave.h: wsum, wsum2, wsum3,
 wsum_lo<16>, wsum_lo<32>) against the reference form they replaced, through
 mpcr_selftest_reduce: every production form returns the reference's bits
 (NaN included: compared as bit patterns), also at the row boundaries and for

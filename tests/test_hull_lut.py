@@ -1,7 +1,7 @@
 """The hull support start table the engine builds (model format v9 dropped it
 from the blob; dev_model.h hull_start_table, read back through
 mpcr_model_hull_starts) and the cube-map cell mapping the oracle and the
-kernel share (oracle lut_cell / rollout.hip lut_cell): every cell names a
+kernel share (oracle lut_cell / convex_mpr.h lut_cell): every cell names a
 vertex of its own hull that is extreme along the cell centre.  Host only --
 the table is built on the CPU at engine creation (tests/test_oracle.py
 covers the rollouts, tests/test_hull_ties.py the start independence)."""

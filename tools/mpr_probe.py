@@ -1,7 +1,7 @@
 """MPR on one pair in fp64 and emulated fp32 (diagnostic, test infrastructure).
 
 A numpy statement of the oracle's / kernel's Minkowski portal refinement
-(oracle/mpcr_oracle.c mpr(), csrc/rollout.hip mpr_lane()) run with every
+(oracle/mpcr_oracle.c mpr(), csrc/convex_mpr.h mpr_lane()) run with every
 operation rounded to the chosen dtype, on the geom poses the oracle computes
 at a given qpos.  Shows whether fp32 arithmetic alone moves MPR's answer.
 
