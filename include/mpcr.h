@@ -124,6 +124,13 @@ int mpcr_model_actuators(const mpcr_model* m, int* nu, double* ctrlrange, int* l
    geom's row is 0 0 0 0 | 1 0 0 0 and is never read), model_geom_id[ngeom]
    (row -> geom index in the model) and is_static[ngeom]. */
 int mpcr_model_geom_poses(const mpcr_model* m, int* ngeom, float* block, int* model_geom_id, int* is_static);
+/* The model's robot-masked contact slots, the ones cost_c is summed over and
+   a slot-weight block prices (mpcr_rollout_cost_slotw): their number and, each
+   nullable, per slot in slot order geom1[nslot] and geom2[nslot] (the slot's
+   two geoms in the device model's geom order: rows of mpcr_model_geom_poses)
+   and pair[nslot] (the collision pair that owns the slot).  Host only: needs
+   no device. */
+int mpcr_model_slots(const mpcr_model* m, int* nslot, int* geom1, int* geom2, int* pair);
 void mpcr_model_free(mpcr_model* m);
 /* The support start table an engine builds for m's convex hulls (model
    format v9 dropped it from the blob; dev_model.h hull_start_table): R x R
@@ -341,6 +348,33 @@ int mpcr_rollout_cost_target(mpcr_engine* e, const float* input, int layout, int
                              int target_step_stride, float* cost4, float* theta, float* thetadot,
                              uint64_t* best_keys, int index_base, int* status, int flags, void* stream);
 
+/* mpcr_rollout_cost_target with the price of each robot-masked contact slot
+   as an input of the call (a backward-compatible addition;
+   mpcr_rollout_cost_target is this call with slot_w = NULL).  slot_w
+   (nullable): device memory, 16-byte aligned, nslot floats in slot order
+   (mpcr_model_slots).  With a block
+     cost_c = sum_s sum_t w[s] ([d_t,s < 0] + [t > 0] relu(0.995 d_t-1,s - d_t,s))
+   and cost = w_pos cost_g + w_rot cost_r + w_col cost_c as ever; the best key
+   follows the total.  The values are used as they are (0 permits a contact,
+   2 charges it double).  Problem p reads the block at slot_w + p
+   slot_w_stride (floats, a multiple of 4): 0 is one block for every problem,
+   otherwise at least nslot.  There is no per-step stride.  Cost only: a block
+   of all ones is bitwise the call without one in every output; any block
+   leaves cost4's goal and rotation columns, theta, thetadot, final_state and
+   status bitwise unchanged; which contacts act on the dynamics does not
+   depend on it.  Doubling every weight and doubling w_col scale cost_c alike
+   to fp32 rounding, not bitwise.  Read when the kernel runs (graph-capturable;
+   a replay sees new contents), never written.  MPCR_EINVAL: host memory, a
+   misaligned pointer, a stride that is no multiple of 4 or below nslot, a
+   model without slots (nslot = 0: the dual-arm scene), host parameters. */
+int mpcr_rollout_cost_slotw(mpcr_engine* e, const float* input, int layout, int nprob, int n_per,
+                            const float* params, const float* start, int start_stride, float* final_state,
+                            const float* ctrl, int ctrl_stride, int ctrl_step_stride, const float* geom_pose,
+                            int geom_stride, int geom_step_stride, const float* target, int target_stride,
+                            int target_step_stride, const float* slot_w, int slot_w_stride, float* cost4,
+                            float* theta, float* thetadot, uint64_t* best_keys, int index_base, int* status,
+                            int flags, void* stream);
+
 /* Fold the costs of candidates that were rolled out in several scenarios
    (world hypotheses) into one row each.  cost4_scen holds nprob nscen n_per
    rows of 4 (a rollout's cost4: total | goal | rotation | collision):
@@ -403,6 +437,23 @@ int mpcr_rollout_cost_scenarios_target(mpcr_engine* e, const float* input, int l
                                        int target_step_stride, float* cost4_scen, float* cost4, float* theta,
                                        float* thetadot, uint64_t* best_keys, int index_base, int* status, int flags,
                                        void* stream);
+
+/* mpcr_rollout_cost_scenarios_target with slot weights (a backward-compatible
+   addition; mpcr_rollout_cost_scenarios_target is this call with slot_w =
+   NULL): slot_w and slot_w_stride as in mpcr_rollout_cost_slotw, the stride
+   per rollout problem r = p nscen + s, so each hypothesis may price its own
+   contacts.  The same invariants hold: ones are bitwise the call without a
+   block, any block moves only the collision column, the total, the fold and
+   the keys.  Each scenario's slice is bitwise what mpcr_rollout_cost_slotw
+   computes for that scenario's blocks alone. */
+int mpcr_rollout_cost_scenarios_slotw(mpcr_engine* e, const float* input, int layout, int nprob, int nscen,
+                                      int worst, int n_per, const float* params, const float* start,
+                                      int start_stride, float* final_state, const float* ctrl, int ctrl_stride,
+                                      int ctrl_step_stride, const float* geom_pose, int geom_stride,
+                                      int geom_step_stride, const float* target, int target_stride,
+                                      int target_step_stride, const float* slot_w, int slot_w_stride,
+                                      float* cost4_scen, float* cost4, float* theta, float* thetadot,
+                                      uint64_t* best_keys, int index_base, int* status, int flags, void* stream);
 
 /* Closed-loop plant: one environment of the model, stepped by the rollout
    kernel (fp32 state resident on the device).  Created at the template

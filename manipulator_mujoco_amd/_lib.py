@@ -94,6 +94,12 @@ _ARGTYPES = {
                                  _vp, _vp, _vp, _i, _vp, _i, _vp],
     "mpcr_rollout_cost_scenarios_target": [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _i,
                                            _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp],
+    # collision-cost weights per contact slot as a call input
+    "mpcr_rollout_cost_slotw": [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _i, _i, _vp,
+                                _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp],
+    "mpcr_rollout_cost_scenarios_slotw": [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _i,
+                                          _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp],
+    "mpcr_model_slots": [_vp, _P(_i), _P(_i), _P(_i), _P(_i)],
 }
 # every symbol include/mpcr.h declares (tests check the exports)
 EXPORTS = tuple(_ARGTYPES)

@@ -46,7 +46,14 @@ __device__ __forceinline__ void put_contacts(const DevModel* __restrict__ m, S& 
   }
 }
 
-template <class S>
+// SW (the STATE / SCEN kernels): the call's slot weights (rollout.h SlotWArgs)
+// price the lane's slots -- cost_c += w[slot] * term where it was cost_c +=
+// term -- read here, at the use, from the problem's L2-resident block: the
+// pointer and the stride from the kernarg segment, the problem from the
+// candidate, so no register holds anything of them across the step (a resumed
+// horizon segment looks the same block up again).  A null block is w = 1, which
+// leaves every sum bitwise what it was.  Without SW the terms fold away.
+template <class S, bool SW = false>
 __device__ __forceinline__ void emit_contacts(const DevModel* __restrict__ m, S& s, const RolloutArgs& args,
                                               [[maybe_unused]] unsigned aflags, int b,
                                               int t, int H, bool valid, int p, int nsl, const float dist[4],
@@ -65,6 +72,20 @@ __device__ __forceinline__ void emit_contacts(const DevModel* __restrict__ m, S&
     const int sa = kStepLoad<S> ? __float_as_int(q0.y) : m->pair_slotadr[p];
     if (sa >= 0) {
       const int ns = kStepLoad<S> ? __float_as_int(q1.x) >> 16 : m->pair_ncon[p];
+      float w[4] = {1.f, 1.f, 1.f, 1.f};
+      if constexpr (SW) {
+        const float* wp = KSW->slot_w;
+        if (wp) {
+          // (the problem fields from the segment too, in both units: no by-value copy of them held across
+          //  the horizon loop for this one use)
+          const int pn = *kernarg_at<int>(offsetof(RolloutArgs, prob_n));
+          const int po = *kernarg_at<int>(offsetof(RolloutArgs, prob_off));
+          wp += (size_t)(pn ? (po + b) / pn : 0) * (unsigned)KSW->stride + sa;
+#pragma unroll
+          for (int c = 0; c < 4; c++)
+            if (c < ns) w[c] = wp[c];
+        }
+      }
       if constexpr (SlotHist<S>::NC == 2) {
         // single-arm kernels: the chunk index is the wave's, so a scalar branch
         // names the chunk's history registers (hv; null: the slab) where
@@ -74,13 +95,13 @@ __device__ __forceinline__ void emit_contacts(const DevModel* __restrict__ m, S&
           for (int c = 0; c < 4; c++) {
             if (c < ns) {
               const float d = dist[c];
-              if (d < 0.f) cost_c += 1.f;
+              if (d < 0.f) cost_c += w[c] * 1.f;
               if (hv) {
-                if (t > 0) cost_c += fmaxf(hv[c] * (1.f - 0.005f) - d, 0.f);
+                if (t > 0) cost_c += w[c] * fmaxf(hv[c] * (1.f - 0.005f) - d, 0.f);
                 hv[c] = d;
               } else {
                 float* cp = KA->slot_prev + (size_t)b * m->nslot;
-                if (t > 0) cost_c += fmaxf(cp[sa + c] * (1.f - 0.005f) - d, 0.f);
+                if (t > 0) cost_c += w[c] * fmaxf(cp[sa + c] * (1.f - 0.005f) - d, 0.f);
                 cp[sa + c] = d;
               }
               if (ARGS_HAS(AF_TRACE_SLOTS, KA->trace_slots && b < KA->n)) KA->trace_slots[((size_t)b * H + t) * m->nslot + sa + c] = d;
@@ -96,17 +117,17 @@ __device__ __forceinline__ void emit_contacts(const DevModel* __restrict__ m, S&
       for (int c = 0; c < 4; c++) {
         if (c < ns) {
           const float d = dist[c];
-          if (d < 0.f) cost_c += 1.f;
+          if (d < 0.f) cost_c += w[c] * 1.f;
           if (SlotHist<S>::NC > 0 && k < SlotHist<S>::NC) {  // this lane's registers (chunk k, slot c)
             float prev = 0.f;
 #pragma unroll
             for (int j = 0; j < SlotHist<S>::NC; j++) prev = j == k ? sh.v[j][c] : prev;
-            if (t > 0) cost_c += fmaxf(prev * (1.f - 0.005f) - d, 0.f);
+            if (t > 0) cost_c += w[c] * fmaxf(prev * (1.f - 0.005f) - d, 0.f);
 #pragma unroll
             for (int j = 0; j < SlotHist<S>::NC; j++) sh.v[j][c] = j == k ? d : sh.v[j][c];
           } else {
             float* cp = KA->slot_prev + (size_t)b * m->nslot;
-            if (t > 0) cost_c += fmaxf(cp[sa + c] * (1.f - 0.005f) - d, 0.f);
+            if (t > 0) cost_c += w[c] * fmaxf(cp[sa + c] * (1.f - 0.005f) - d, 0.f);
             cp[sa + c] = d;
           }
           if (ARGS_HAS(AF_TRACE_SLOTS, KA->trace_slots && b < KA->n)) KA->trace_slots[((size_t)b * H + t) * m->nslot + sa + c] = d;

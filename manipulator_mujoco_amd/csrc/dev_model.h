@@ -295,6 +295,27 @@ inline int model_geom_poses(const mpcr_model_t& m, float* block, int* model_geom
   return ng;
 }
 
+// The robot-masked contact slots (cost_c's, a call's slot-weight block): slot
+// pair_slotadr[p] + c, c < pair_ncon[p], belongs to pair p; its two geoms in
+// the device model's geom order (model_geom_poses' rows).  geom1[nslot],
+// geom2[nslot], pair[nslot], each nullable; returns nslot, or -1 when a masked
+// pair's slots fall outside it.  Host only.
+inline int model_slots(const mpcr_model_t& m, int* geom1, int* geom2, int* pair) {
+  int gmap[MPCR_MAX_GEOM];
+  pair_geom_map(m, gmap);
+  for (int p = 0; p < m.npair; p++) {
+    const int sa = m.pair_slotadr[p];
+    if (sa < 0) continue;
+    if (sa + m.pair_ncon[p] > m.nslot) return -1;
+    for (int c = 0; c < m.pair_ncon[p]; c++) {
+      if (geom1) geom1[sa + c] = gmap[m.pair_geom1[p]];
+      if (geom2) geom2[sa + c] = gmap[m.pair_geom2[p]];
+      if (pair) pair[sa + c] = p;
+    }
+  }
+  return m.nslot;
+}
+
 // Fills d (its table pointers stay null: mpcr_engine_create sets them to the
 // uploaded DevTables) or returns the refusal's code with its message in err.
 // lutadr[ngeom]: hull_start_table's geom_adr.

@@ -332,6 +332,14 @@ extern "C" int mpcr_model_geom_poses(const mpcr_model* m, int* ngeom, float* blo
   return MPCR_OK;
 }
 
+extern "C" int mpcr_model_slots(const mpcr_model* m, int* nslot, int* geom1, int* geom2, int* pair) {
+  if (!m) return fail(MPCR_EINVAL, "null model");
+  const int ns = model_slots(m->m, geom1, geom2, pair);
+  if (ns < 0) return fail(MPCR_EMODEL, "model exceeds blob capacity");
+  if (nslot) *nslot = ns;
+  return MPCR_OK;
+}
+
 extern "C" void mpcr_model_free(mpcr_model* m) { delete m; }
 
 // the support start table's scramble seed (dev_model.h hull_start_table; the
@@ -513,6 +521,7 @@ struct Launch {
   // the call's blocks (rollout.h: start / final_state, ctrl, geom_pose, strides in floats; the scenarios per
   // planning problem that share its input rows, 0: none; the target schedule, null: the parameter block's target)
   CallBlocks blk = {};
+  SlotWArgs sw = {};  // the contact slots' weights (rollout.h; null: every slot at 1)
 };
 
 // the kernel's arguments for launch l of engine e (the one place they are filled)
@@ -555,10 +564,11 @@ static int rollout_args(const mpcr_engine* e, const Launch& l, RolloutArgs& a) {
   // parameter values, so has_state() cannot read those as pointers
   if (l.dpar) {
     a.blk = l.blk;
+    a.sw = l.sw;
   } else {
     const StateArgs& s = l.blk.st;
-    if (s.start || s.final_state || s.ctrl || s.geom_pose || l.blk.nscen || l.blk.tg.target)
-      return fail(MPCR_EINVAL, "state, control and geom-pose blocks need a device parameter block");
+    if (s.start || s.final_state || s.ctrl || s.geom_pose || l.blk.nscen || l.blk.tg.target || l.sw.slot_w)
+      return fail(MPCR_EINVAL, "state, control, geom-pose and slot-weight blocks need a device parameter block");
     std::memcpy(a.par, l.par, sizeof(a.par));
   }
   return MPCR_OK;
@@ -704,7 +714,7 @@ static bool device_memory(const void* p, int d) {
 // p, addressed by `stem`_stride and `stem`_step_stride in floats, one unit of
 // `unit` floats (named `unit_name`) per step.  align: bytes its rows are
 // aligned to (0: no demand).  ctrl: nu floats; geom_pose: 8 ngeom, 16 bytes;
-// target: a row of 8, 16 bytes.
+// target: a row of 8, 16 bytes; slot_w: nslot floats, 16 bytes, no step stride.
 static int check_block(const mpcr_engine* e, const char* name, const char* stem, const float* p, int stride,
                        int step_stride, const char* unit_name, int unit, int align) {
   if (align && ((reinterpret_cast<uintptr_t>(p) & (align - 1)) || (stride & (align / 4 - 1)) ||
@@ -763,6 +773,15 @@ static int rollout_call(mpcr_engine* e, Launch& l, int flags, void* stream) {
   } else {
     tg.stride = tg.step_stride = 0;
   }
+  SlotWArgs& sw = l.sw;
+  if (sw.slot_w) {
+    if (e->host.nslot == 0) return fail(MPCR_EINVAL, "slot_w: the model has no robot-masked contact slot (nslot = 0)");
+    if (sw.stride < 0) return fail(MPCR_EINVAL, "slot_w_stride=%d: 0 or at least nslot=%d", sw.stride, e->host.nslot);
+    if (int rc = check_block(e, "slot_w", "slot_w", sw.slot_w, sw.stride, 0, "nslot", e->host.nslot, 16)) return rc;
+  } else {
+    sw.stride = 0;
+  }
+  sw.pad_ = 0;
   if (int rc = check_layout(l.layout)) return rc;
   if (!l.in || !l.dpar || !l.cost4) return fail(MPCR_EINVAL, "null argument");
   HIPCHK(hipSetDevice(e->device));
@@ -800,12 +819,12 @@ extern "C" int mpcr_rollout_cost_multi(mpcr_engine* e, const float* input, int l
   return rollout_call(e, l, flags, stream);
 }
 
-extern "C" int mpcr_rollout_cost_target(mpcr_engine* e, const float* input, int layout, int nprob, int n_per,
+extern "C" int mpcr_rollout_cost_slotw(mpcr_engine* e, const float* input, int layout, int nprob, int n_per,
                                         const float* params, const float* start, int start_stride, float* final_state,
                                         const float* ctrl, int ctrl_stride, int ctrl_step_stride,
                                         const float* geom_pose, int geom_stride, int geom_step_stride,
-                                        const float* target, int target_stride, int target_step_stride, float* cost4,
-                                        float* theta, float* thetadot, uint64_t* best_keys, int index_base,
+                                        const float* target, int target_stride, int target_step_stride,
+                                        const float* slot_w, int slot_w_stride, float* cost4, float* theta, float* thetadot, uint64_t* best_keys, int index_base,
                                         int* status, int flags, void* stream) {
   if (!e) return fail(MPCR_EINVAL, "null argument");
   if (!(flags & MPCR_F_DEVICE_PTRS)) return fail(MPCR_EINVAL, "mpcr_rollout_cost_state takes device pointers");
@@ -818,7 +837,21 @@ extern "C" int mpcr_rollout_cost_target(mpcr_engine* e, const float* input, int 
   l.blk.st.ctrl = ctrl; l.blk.st.ctrl_stride = ctrl_stride; l.blk.st.ctrl_step_stride = ctrl_step_stride;
   l.blk.st.geom_pose = geom_pose; l.blk.st.geom_stride = geom_stride; l.blk.st.geom_step_stride = geom_step_stride;
   l.blk.tg.target = target; l.blk.tg.stride = target_stride; l.blk.tg.step_stride = target_step_stride;
+  l.sw.slot_w = slot_w; l.sw.stride = slot_w_stride;
   return rollout_call(e, l, flags, stream);
+}
+
+extern "C" int mpcr_rollout_cost_target(mpcr_engine* e, const float* input, int layout, int nprob, int n_per,
+                                        const float* params, const float* start, int start_stride, float* final_state,
+                                        const float* ctrl, int ctrl_stride, int ctrl_step_stride,
+                                        const float* geom_pose, int geom_stride, int geom_step_stride,
+                                        const float* target, int target_stride, int target_step_stride, float* cost4,
+                                        float* theta, float* thetadot, uint64_t* best_keys, int index_base,
+                                        int* status, int flags, void* stream) {
+  return mpcr_rollout_cost_slotw(e, input, layout, nprob, n_per, params, start, start_stride, final_state, ctrl,
+                                 ctrl_stride, ctrl_step_stride, geom_pose, geom_stride, geom_step_stride, target,
+                                 target_stride, target_step_stride, nullptr, 0, cost4, theta, thetadot, best_keys,
+                                 index_base, status, flags, stream);
 }
 
 extern "C" int mpcr_rollout_cost_world(mpcr_engine* e, const float* input, int layout, int nprob, int n_per,
@@ -871,12 +904,13 @@ extern "C" int mpcr_scenario_reduce(mpcr_engine* e, const float* cost4_scen, int
   return MPCR_OK;
 }
 
-extern "C" int mpcr_rollout_cost_scenarios_target(mpcr_engine* e, const float* input, int layout, int nprob, int nscen,
+extern "C" int mpcr_rollout_cost_scenarios_slotw(mpcr_engine* e, const float* input, int layout, int nprob, int nscen,
                                                   int worst, int n_per, const float* params, const float* start,
                                                   int start_stride, float* final_state, const float* ctrl,
                                                   int ctrl_stride, int ctrl_step_stride, const float* geom_pose,
                                                   int geom_stride, int geom_step_stride, const float* target,
-                                                  int target_stride, int target_step_stride, float* cost4_scen,
+                                                  int target_stride, int target_step_stride, const float* slot_w,
+                                                  int slot_w_stride, float* cost4_scen,
                                                   float* cost4, float* theta, float* thetadot, uint64_t* best_keys,
                                                   int index_base, int* status, int flags, void* stream) {
   if (!e) return fail(MPCR_EINVAL, "null argument");
@@ -897,12 +931,28 @@ extern "C" int mpcr_rollout_cost_scenarios_target(mpcr_engine* e, const float* i
   l.blk.st.ctrl = ctrl; l.blk.st.ctrl_stride = ctrl_stride; l.blk.st.ctrl_step_stride = ctrl_step_stride;
   l.blk.st.geom_pose = geom_pose; l.blk.st.geom_stride = geom_stride; l.blk.st.geom_step_stride = geom_step_stride;
   l.blk.tg.target = target; l.blk.tg.stride = target_stride; l.blk.tg.step_stride = target_step_stride;
+  l.sw.slot_w = slot_w; l.sw.stride = slot_w_stride;
   if (int rc = rollout_call(e, l, flags & ~(MPCR_F_SYNC | MPCR_F_RESET_BEST), stream)) return rc;
   if (cost4)
     return mpcr_scenario_reduce(e, cost4_scen, nprob, nscen, n_per, worst, cost4, best_keys, index_base, flags,
                                 stream);
   if (flags & MPCR_F_SYNC) HIPCHK(hipStreamSynchronize((hipStream_t)stream));
   return MPCR_OK;
+}
+
+extern "C" int mpcr_rollout_cost_scenarios_target(mpcr_engine* e, const float* input, int layout, int nprob, int nscen,
+                                                  int worst, int n_per, const float* params, const float* start,
+                                                  int start_stride, float* final_state, const float* ctrl,
+                                                  int ctrl_stride, int ctrl_step_stride, const float* geom_pose,
+                                                  int geom_stride, int geom_step_stride, const float* target,
+                                                  int target_stride, int target_step_stride, float* cost4_scen,
+                                                  float* cost4, float* theta, float* thetadot, uint64_t* best_keys,
+                                                  int index_base, int* status, int flags, void* stream) {
+  return mpcr_rollout_cost_scenarios_slotw(e, input, layout, nprob, nscen, worst, n_per, params, start, start_stride,
+                                           final_state, ctrl, ctrl_stride, ctrl_step_stride, geom_pose, geom_stride,
+                                           geom_step_stride, target, target_stride, target_step_stride, nullptr, 0,
+                                           cost4_scen, cost4, theta, thetadot, best_keys, index_base, status, flags,
+                                           stream);
 }
 
 extern "C" int mpcr_rollout_cost_scenarios(mpcr_engine* e, const float* input, int layout, int nprob, int nscen,

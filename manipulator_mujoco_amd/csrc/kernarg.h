@@ -1,5 +1,5 @@
 // kernarg.h -- how the rollout kernels read their launch arguments (KA, KSA, KSCEN,
-// KTA, ARGS_HAS, DBG_LAST).
+// KTA, KSW, ARGS_HAS, DBG_LAST).
 #pragma once
 #include "rollout.h"
 
@@ -66,6 +66,9 @@ __device__ __forceinline__ unsigned args_flags(const RolloutArgs& a) {
 // horizon loop (a fifth spilled VGPR and 32 bytes of scratch in the one-wave
 // kernel)
 #define KTA kernarg_at<TargetArgs>(offsetof(RolloutArgs, blk) + offsetof(CallBlocks, tg))
+// The slot weights (KSW->field) likewise, in both units: read at the use, in
+// emit_contacts, so nothing of them lives across the step loop
+#define KSW kernarg_at<SlotWArgs>(offsetof(RolloutArgs, sw))
 
 // The debug dump's test (candidate 0's last step, RolloutArgs::dbg given).  The
 // single-arm kernels test the step and the candidate first, values the loop

@@ -117,6 +117,27 @@ struct CallBlocks {
   int pad_;
   TargetArgs tg;
 };
+// sw: what each robot-masked contact slot costs (mpcr_rollout_cost_slotw): a
+// block of DevModel::nslot floats in slot order, 16-byte aligned, read when
+// the kernel runs and never written; slot s enters cost_c as w[s] ([d < 0] +
+// relu(0.995 d_prev - d)), the values used as they are.  Problem p (with
+// scenarios: rollout problem r = p nscen + s) reads the block at slot_w + p
+// stride (floats, a multiple of 4; 0: one block for every problem).  No step
+// stride: what a task permits holds for a horizon.  Null prices every slot at
+// 1.  Cost only: the slot history records every distance and the active
+// contacts are chosen whatever the weights.  CallBlocks fills par's bytes, so
+// the block sits behind the union: everything up to it keeps its offset, and
+// the problem fields move 16 bytes with the model pointer that follows the
+// arguments, so the kernels that read those keep the loads they had (the
+// three share one).  Like CallBlocks it is set only with dpar, and read only
+// by the STATE / SCEN instantiations.
+struct SlotWArgs {
+  const float* slot_w;
+  int stride;
+  int pad_;
+};
+static_assert(sizeof(SlotWArgs) == 16 && offsetof(SlotWArgs, slot_w) == 0 && offsetof(SlotWArgs, stride) == 8,
+              "SlotWArgs: one pointer and one int");
 static_assert(sizeof(StateArgs) == 56 && offsetof(StateArgs, start) == 0 && offsetof(StateArgs, final_state) == 8 &&
                   offsetof(StateArgs, start_stride) == 16 && offsetof(StateArgs, ctrl_stride) == 20 &&
                   offsetof(StateArgs, ctrl_step_stride) == 24 && offsetof(StateArgs, ctrl) == 32 &&
@@ -176,6 +197,8 @@ struct RolloutArgs {
     float par[PAR_N];
     CallBlocks blk;
   };
+  // the contact slots' weights (SlotWArgs above; set only with dpar)
+  SlotWArgs sw;
   // several independent problems in one call (mpcr_rollout_cost_multi):
   // problem p owns candidates [p prob_n, (p + 1) prob_n) of the call, reads
   // its parameter block from dpar + p PAR_N and reduces into best_key[p] with
@@ -185,6 +208,10 @@ struct RolloutArgs {
   // instantiations of rollout_kernel, which the launchers pick for prob_n > 0.
   int prob_n, prob_off;
 };
+static_assert(offsetof(RolloutArgs, blk) == 216 && offsetof(RolloutArgs, sw) == 296 &&
+                  offsetof(RolloutArgs, prob_n) == 312 && offsetof(RolloutArgs, prob_off) == 316 &&
+                  sizeof(RolloutArgs) == 320,
+              "the slot weights behind the union; the problem fields end the arguments as they did");
 // the unit quaternion of a target's (parameter block or schedule row): the one
 // expression both go through
 __host__ __device__ inline void target_quat_unit(const float q[4], float out[4]) {
@@ -192,12 +219,12 @@ __host__ __device__ inline void target_quat_unit(const float q[4], float out[4])
   out[0] = q[0] / qn; out[1] = q[1] / qn; out[2] = q[2] / qn; out[3] = q[3] / qn;
 }
 // whether a launch starts from, or returns, state blocks, reads a control,
-// geom-pose or target block, or shares its input rows among scenarios (whose
-// kernels are STATE ones, block pointers or not)
+// geom-pose, target or slot-weight block, or shares its input rows among
+// scenarios (whose kernels are STATE ones, block pointers or not)
 inline bool has_state(const RolloutArgs& a) {
   if (!a.dpar) return false;
   const StateArgs& s = a.blk.st;
-  return s.start || s.final_state || s.ctrl || s.geom_pose || a.blk.nscen > 1 || a.blk.tg.target;
+  return s.start || s.final_state || s.ctrl || s.geom_pose || a.blk.nscen > 1 || a.blk.tg.target || a.sw.slot_w;
 }
 // the scenarios of a launch (0: none)
 inline int scenarios(const RolloutArgs& a) { return a.dpar && a.blk.nscen > 1 ? a.blk.nscen : 0; }

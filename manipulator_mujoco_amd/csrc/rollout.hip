@@ -1407,7 +1407,7 @@ __global__ void __launch_bounds__(WAVE * (WPCS & 3), WIDE ? kWideWavesPerSimd : 
       if (run && func != 4 && !defer) nsl = narrow_lane(m, s, hx, p, dist, pos, nrm, nullptr, rq);
       STAMP(11);
       const unsigned long long bbm = __ballot(run && func == 4);
-      emit_contacts(m, s, args, aflags, b, t, H, valid && func != 4 && !defer, p, nsl, dist, pos, nrm, cost_c, shist, k, rq);
+      emit_contacts<S, STATE>(m, s, args, aflags, b, t, H, valid && func != 4 && !defer, p, nsl, dist, pos, nrm, cost_c, shist, k, rq);
       STAMP(12);
       if (bbm && !(m->disableflags & 16)) {
         unsigned long long mm = bbm;
@@ -1540,7 +1540,7 @@ __global__ void __launch_bounds__(WAVE * (WPCS & 3), WIDE ? kWideWavesPerSimd : 
             }
             lsl = __float_as_int(o[28]);
           }
-          emit_contacts(m, s, args, aflags, b, t, H, lane < ncv, lpc, lsl, ld, lp, ln, cost_c, shist, -1);
+          emit_contacts<S, STATE>(m, s, args, aflags, b, t, H, lane < ncv, lpc, lsl, ld, lp, ln, cost_c, shist, -1);
         }
         STAMP(18);
       }
@@ -1592,7 +1592,7 @@ __global__ void __launch_bounds__(WAVE * (WPCS & 3), WIDE ? kWideWavesPerSimd : 
           ncon_w += tot;
           block_sync();  // jcnt is the next round's
         } else if (mine) {
-          emit_contacts(m, s, args, aflags, b, t, H, v, pc, cn_sl, cd, cp, cn, cost_c, shist, -1);
+          emit_contacts<S, STATE>(m, s, args, aflags, b, t, H, v, pc, cn_sl, cd, cp, cn, cost_c, shist, -1);
         }
         STAMP(18);
       }

@@ -146,6 +146,46 @@ class Model:
             out[..., r, 4:8] = q / np.sqrt(np.sum(q * q))
         return out
 
+    def slots(self):
+        """``mpcr_model_slots``: (geom1, geom2, pair), each (nslot,) int32 --
+        per robot-masked contact slot, in slot order, its two geoms as rows of
+        ``geom_poses`` (the device model's geom order) and the collision pair
+        that owns it.  Needs the library, no GPU."""
+        lib = _lib.load()
+        ns = ctypes.c_int()
+        check(lib.mpcr_model_slots(self.handle, ctypes.byref(ns), None, None, None))
+        out = [np.zeros(max(ns.value, 1), dtype=np.int32) for _ in range(3)]
+        ip = ctypes.POINTER(ctypes.c_int)
+        check(lib.mpcr_model_slots(self.handle, None, *(a.ctypes.data_as(ip) for a in out)))
+        return tuple(a[:ns.value] for a in out)
+
+    def slot_weights(self, geoms=None, bodies=None, default=1.0):
+        """A slot-weight block (``Engine.rollout_cost_state(slot_w=)``), float32
+        (nslot,): a slot's weight is the product of its two geoms' weights.
+        ``geoms`` maps a geom name or model geom id to a weight, ``bodies`` a
+        body name to the weight of all its collision geoms (a geom named in
+        ``geoms`` keeps that weight); every other geom weighs ``default``.
+        Unknown names raise ``ValueError``."""
+        g1, g2, _ = self.slots()
+        _, ids, _ = self.geom_poses()
+        gw = np.full(max(ids.size, 1), float(default), dtype=np.float64)
+        names = self.compiled.names["body"]
+        names = list(names.values()) if isinstance(names, dict) else list(names)
+        bodyid = np.asarray(self.compiled.geom_bodyid).reshape(-1)
+        for key, w in (bodies or {}).items():
+            if key not in names:
+                raise ValueError(f"no body named {key!r}")
+            rows = np.nonzero(bodyid[ids] == names.index(key))[0]
+            if rows.size == 0:
+                raise ValueError(f"body {key!r} has no collision geom")
+            gw[rows] = float(w)
+        for key, w in (geoms or {}).items():
+            try:
+                gw[self.geom_row(key)] = float(w)
+            except KeyError as e:
+                raise ValueError(str(e.args[0])) from None
+        return (gw[g1] * gw[g2]).astype(np.float32)
+
     def __del__(self):
         try:
             if getattr(self, "handle", None):
@@ -313,7 +353,7 @@ class Engine:
 
     def _rollout_dp(self, nprob, inp, layout, params, cost4, theta, thetadot, best_keys, index_base, status,
                     reset_best, stream, state=None, ctrl=None, ctrl_per_step=False, geom_pose=None,
-                    geom_pose_per_step=False, target=None, target_per_step=False):
+                    geom_pose_per_step=False, target=None, target_per_step=False, slot_w=None):
         """nprob None: ``rollout_cost_dp`` (its own C entry, which takes an
         empty batch); else ``rollout_cost_multi`` or, with state = (start,
         final_state), ``rollout_cost_state`` (``mpcr_rollout_cost_world``,
@@ -333,9 +373,13 @@ class Engine:
         if state is not None:
             fn = lib.mpcr_rollout_cost_world
             args += self._state_args(nprob, n, inp, *state, ctrl, ctrl_per_step, geom_pose, geom_pose_per_step)
-            if target is not None:
+            if target is not None or slot_w is not None:
                 fn = lib.mpcr_rollout_cost_target
                 args += self._block_args("target", target, (8,), nprob, inp.device, target_per_step)
+            if slot_w is not None:
+                fn = lib.mpcr_rollout_cost_slotw
+                slot_w, sw_args = self._slot_w_args(slot_w, nprob, inp.device)
+                args += sw_args
         check(fn(self.handle, _ptr(inp), layout, *shape, *args, _ptr(cost4), _ptr(theta), _ptr(thetadot),
                  _ptr(best_keys), int(index_base), _ptr(status), *_call_tail(inp, reset_best, stream)))
         return cost4
@@ -385,6 +429,22 @@ class Engine:
             return _ptr(t), self.H * size, size
         return _ptr(t), size if nprob > 1 and t.numel() == nprob * size else 0, 0
 
+    def _slot_w_args(self, t, nprob, device):
+        """(the tensor the call reads, (pointer, problem stride)) of a
+        slot-weight tensor: ``(nslot,)`` for every rollout problem or ``(nprob,
+        nslot)`` with one block each.  Rows of nslot floats are padded (a copy,
+        with ones) to the next multiple of 4, the block's alignment; rows
+        already that long -- a planner's own buffer -- are passed as they are."""
+        import torch
+        _check_tensor("slot_w", t, device)
+        ns4 = (self.nslot + 3) & ~3
+        if t.dim() not in (1, 2) or t.shape[-1] not in (self.nslot, ns4):
+            raise ValueError(f"slot_w must be ({self.nslot},) or ({nprob}, {self.nslot}) (rows may be padded to "
+                             f"{ns4}); got {tuple(t.shape)}")
+        if t.shape[-1] != ns4:
+            t = torch.nn.functional.pad(t, (0, ns4 - t.shape[-1]), value=1.0).contiguous()
+        return t, self._block_args("slot_w", t, (ns4,), nprob, device)[:2]
+
     @property
     def ngeom(self):
         """The device model's collision geoms: the rows of a geom-pose block."""
@@ -415,7 +475,7 @@ class Engine:
                            theta=None, thetadot=None, best_keys=None, index_base: int = 0, status=None,
                            reset_best: bool = True, stream=None, ctrl=None, ctrl_per_step: bool = False,
                            geom_pose=None, geom_pose_per_step: bool = False, target=None,
-                           target_per_step: bool = False):
+                           target_per_step: bool = False, slot_w=None):
         """``rollout_cost_multi`` from a given full state and / or returning
         the final states (``mpcr_rollout_cost_state``).  ``start``: a device
         tensor of one state block (``pack_state``, ``Plant.copy_state``) shared
@@ -442,12 +502,19 @@ class Engine:
         per problem, or with ``target_per_step`` (nprob, H, 8), one row per
         step; the quaternion may have any norm.  It replaces the parameter
         block's ptgt / qtgt and is read when the kernel runs.  None keeps the
-        parameter block's target."""
+        parameter block's target.
+        ``slot_w`` (``mpcr_rollout_cost_slotw``): what each robot-masked
+        contact slot costs, a device tensor of slot-weight blocks
+        (``Model.slot_weights``), (nslot,) for every problem or (nprob, nslot)
+        with one per problem: cost_c sums w[slot] times the slot's terms, the
+        values used as they are.  Cost only -- every other output is bitwise
+        the call without it, and ones are that call exactly -- and read when
+        the kernel runs.  None prices every slot at 1."""
         return self._rollout_dp(int(nprob), inp, layout, params, cost4, theta, thetadot, best_keys, index_base,
                                 status, reset_best, stream, state=(start, final_state), ctrl=ctrl,
                                 ctrl_per_step=ctrl_per_step, geom_pose=geom_pose,
                                 geom_pose_per_step=geom_pose_per_step, target=target,
-                                target_per_step=target_per_step)
+                                target_per_step=target_per_step, slot_w=slot_w)
 
     @staticmethod
     def _cost_rows(name, t, rows, device=None):
@@ -490,7 +557,7 @@ class Engine:
                                cost4=None, start=None, final_state=None, theta=None, thetadot=None, best_keys=None,
                                index_base: int = 0, status=None, reset_best: bool = True, stream=None, ctrl=None,
                                ctrl_per_step: bool = False, geom_pose=None, geom_pose_per_step: bool = False,
-                               target=None, target_per_step: bool = False):
+                               target=None, target_per_step: bool = False, slot_w=None):
         """One set of candidates priced in ``nscen`` scenarios per problem
         (``mpcr_rollout_cost_scenarios``).  ``inp`` holds nprob * n_per rows;
         rollout problem r = p nscen + s is scenario s of problem p and is
@@ -504,7 +571,10 @@ class Engine:
         ``best_keys`` (needs ``cost4``) its keys.  Each scenario's slice is
         bitwise the ``rollout_cost_state`` call on that scenario's blocks.
         ``target`` / ``target_per_step`` as there, per rollout problem
-        (``mpcr_rollout_cost_scenarios_target``).
+        (``mpcr_rollout_cost_scenarios_target``).  ``slot_w``
+        (``mpcr_rollout_cost_scenarios_slotw``): (nslot,), (nprob, nslot) -- a
+        problem's block for all its scenarios -- or (nprob, nscen, nslot), one
+        per hypothesis.
         Returns ``cost4`` (or ``cost4_scen`` without one).  Graph-capturable."""
         nprob, nscen = int(nprob), int(nscen)
         worst = nscen if worst is None else int(worst)
@@ -524,9 +594,18 @@ class Engine:
         args = self._state_args(R, R * n_per, inp, start, final_state, ctrl, ctrl_per_step, geom_pose,
                                 geom_pose_per_step)
         fn = _lib.load().mpcr_rollout_cost_scenarios
-        if target is not None:
+        if target is not None or slot_w is not None:
             fn = _lib.load().mpcr_rollout_cost_scenarios_target
             args += self._block_args("target", target, (8,), R, inp.device, target_per_step)
+        if slot_w is not None:
+            fn = _lib.load().mpcr_rollout_cost_scenarios_slotw
+            _check_tensor("slot_w", slot_w, inp.device)
+            if slot_w.dim() == 2 and nscen > 1 and slot_w.shape[0] == nprob:  # a problem's block for its scenarios
+                slot_w = slot_w.unsqueeze(1).expand(nprob, nscen, slot_w.shape[-1]).contiguous()
+            if slot_w.dim() == 3 and tuple(slot_w.shape[:2]) == (nprob, nscen):
+                slot_w = slot_w.reshape(R, slot_w.shape[-1])
+            slot_w, sw_args = self._slot_w_args(slot_w, R, inp.device)
+            args += sw_args
         check(fn(
             self.handle, _ptr(inp), layout, nprob, nscen, worst, n_per, self._params_arg(params, R), *args,
             _ptr(cost4_scen), _ptr(cost4), _ptr(theta), _ptr(thetadot), _ptr(best_keys), int(index_base),

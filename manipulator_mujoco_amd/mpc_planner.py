@@ -130,7 +130,7 @@ def run_cem_planner(num_dof=None, num_batch=None, num_steps=None, maxiter_cem=No
                     position_threshold=None, rotation_threshold=None, save_data=None, data_dir=None,
                     stop_at_final_target=None, *, max_ticks=100, model_path=None, device=None, graph=True,
                     verbose=True, planner_kwargs=None, plan_from_state=False, ctrl=None, geom_poses=None,
-                    hypotheses=None, scenario_worst=None, target_velocity=None):
+                    hypotheses=None, scenario_worst=None, target_velocity=None, touch_target=False):
     """Run the CEM planner in closed loop for ``max_ticks`` ticks (headless).
     plan_from_state: every tick's rollouts start from the plant's full state
     (a device copy of its block) instead of the template state with the arm
@@ -156,7 +156,12 @@ def run_cem_planner(num_dof=None, num_batch=None, num_steps=None, maxiter_cem=No
     per tick (``moving_target``): the planner gets the num_steps predicted
     poses of its horizon (``cem_planner(target_schedule=)``), the reached-test
     and the logged cost_g use the pose at the tick's time.  "home" does not
-    move.  None: the targets stand still, and nothing changes."""
+    move.  None: the targets stand still, and nothing changes.
+    touch_target: while a named target body is current, the contact slots of
+    its collision geoms cost nothing (``cem_planner(collision_weights=)``,
+    weight 0): the plan may near and touch the body it is sent to, and every
+    other contact costs what it did.  The weights are restored when the target
+    switches; "home" exempts nothing.  False: the loop makes the calls it made."""
     hypotheses = list(hypotheses or [])
     if initial_qpos is None:
         initial_qpos = [1.5, -1.8, 1.75, -1.25, -1.6, 0]
@@ -183,7 +188,8 @@ def run_cem_planner(num_dof=None, num_batch=None, num_steps=None, maxiter_cem=No
                                              else {})
                                           | ({"num_scenarios": 1 + len(hypotheses), "scenario_worst": scenario_worst}
                                              if hypotheses else {})
-                                          | ({"target_schedule": True} if target_velocity is not None else {})))
+                                          | ({"target_schedule": True} if target_velocity is not None else {})
+                                          | ({"collision_weights": True} if touch_target else {})))
     log(f"Initialized CEM Planner: {round(time.time() - start_time, 2)}s")
 
     model = cem.model
@@ -245,8 +251,20 @@ def run_cem_planner(num_dof=None, num_batch=None, num_steps=None, maxiter_cem=No
             scen[s, :, row, :3] += d
         return {"geom_pose": scen}
 
+    def touch_weights(name):
+        """The planner's slot weights while ``name`` is the current target: 0
+        on the slots of that body's geoms, 1 elsewhere ("home", or a target
+        that is no body with collision geoms: all ones)."""
+        if not touch_target:
+            return {}
+        m = cem.engine.model
+        try:
+            return {"slot_w": m.slot_weights(bodies={name: 0.0}) if name != "home" else m.slot_weights()}
+        except ValueError:
+            return {"slot_w": m.slot_weights()}
+
     _ = cem.compute_cem(xi_mean, data.qpos[ctrl_q], data.qvel[ctrl_v], data.qacc[ctrl_v], target_pos, target_rot,
-                        **from_plant, **apply_ctrl(0), **apply_geom_poses(0))
+                        **from_plant, **apply_ctrl(0), **apply_geom_poses(0), **touch_weights(target_names[0]))
     log(f"Compute CEM: {round(time.time() - start_time, 2)}s")
 
     thetadot = np.zeros(num_dof)
@@ -276,7 +294,7 @@ def run_cem_planner(num_dof=None, num_batch=None, num_steps=None, maxiter_cem=No
 
         cost, best_cost_g, best_cost_r, best_cost_c, best_vels, best_traj, xi_mean, _, _ = cem.compute_cem(
             xi_mean, data.qpos[ctrl_q], data.qvel[ctrl_v], data.qacc[ctrl_v], target_pos, target_rot, **from_plant,
-            **apply_ctrl(_tick), **apply_geom_poses(_tick), **to_target)
+            **apply_ctrl(_tick), **apply_geom_poses(_tick), **to_target, **touch_weights(current_target))
 
         thetadot = np.mean(best_vels[1:num_steps - 2], axis=0)
         data.step(thetadot)
@@ -374,6 +392,9 @@ def main(argv=None):  # SBP/mpc_planner.py:256-314
     parser.add_argument("--target_velocity", nargs=3, type=float, default=None, metavar=("VX", "VY", "VZ"),
                         help="a target body, once current, translates at this constant world velocity (m/s): the "
                              "planner gets the predicted poses of its horizon")
+    parser.add_argument("--touch_target", action="store_true",
+                        help="while a target body is current, contacts with its geoms cost nothing: the plan may touch "
+                             "the body it is sent to")
     a = parser.parse_args(argv)
     geom_poses = None
     if a.obstacle is not None:
@@ -395,7 +416,8 @@ def main(argv=None):  # SBP/mpc_planner.py:256-314
                            model_path=a.model, graph=not a.no_graph, plan_from_state=a.plan_from_state,
                            ctrl=ctrl, geom_poses=geom_poses,
                            hypotheses=[(h[0], [float(x) for x in h[1:]]) for h in a.hypothesis or []],
-                           scenario_worst=a.scenario_worst, target_velocity=a.target_velocity)
+                           scenario_worst=a.scenario_worst, target_velocity=a.target_velocity,
+                           touch_target=a.touch_target)
 
 
 if __name__ == "__main__":

@@ -128,6 +128,14 @@ class cem_planner:  # noqa: N801 (reference name)
                         tick without a trajectory holds ``target_pos`` /
                         ``target_rot`` over the horizon and plans what a
                         planner without the flag plans, bit for bit
+    collision_weights   the rollouts price each robot-masked contact slot with
+                        a weight read per problem (and scenario) from a static
+                        device buffer of slot-weight blocks
+                        (``compute_cem(slot_w=...)``, ``Model.slot_weights``),
+                        initialised to ones, instead of charging every contact
+                        alike: 0 permits a contact, 2 charges it double.  A
+                        planner with the flag and nothing staged plans what a
+                        planner without it plans, bit for bit
     num_scenarios       world hypotheses per problem (default 1: none).  With
                         S > 1 the state, control and geom-pose buffers hold
                         one block per problem and scenario -- ``compute_cem``'s
@@ -147,7 +155,7 @@ class cem_planner:  # noqa: N801 (reference name)
                  model_path=None, device=None, seed=0, elite_from_filtered=False, graph=False, group=None,
                  gather_rollouts=False, return_rollouts=True, capture_exchange=True, verbose=True,
                  num_problems=1, seed_step=0, plan_from_state=False, actuator_ctrl=False, geom_poses=False,
-                 num_scenarios=1, scenario_worst=None, target_schedule=False):
+                 num_scenarios=1, scenario_worst=None, target_schedule=False, collision_weights=False):
         import torch
         import torch.distributed as tdist
 
@@ -267,6 +275,14 @@ class cem_planner:  # noqa: N801 (reference name)
         # one target row per problem (and scenario) and step: every tick stages it (_stage_targets)
         self.target_schedule = bool(target_schedule)
         self._target = torch.zeros((B,) + sb + (H, 8), **f32) if self.target_schedule else None
+        # one slot-weight block per problem (and scenario), rows padded to a multiple of 4 floats: ones until
+        # a tick stages another
+        self.collision_weights = bool(collision_weights)
+        self._slot_w = None
+        if self.collision_weights:
+            if self.engine.nslot == 0:
+                raise ValueError("collision_weights: the model has no robot-masked contact slot")
+            self._slot_w = torch.ones((B,) + sb + ((self.engine.nslot + 3) & ~3,), **f32)
         self._graphs = None
         if verbose and self.rank == 0:
             self.print_info()
@@ -316,14 +332,15 @@ class cem_planner:  # noqa: N801 (reference name)
                                                geom_pose=flat(self._gpose),
                                                geom_pose_per_step=self.geom_poses == "per_step",
                                                target=flat(self._target), target_per_step=self.target_schedule,
-                                               **out)
+                                               slot_w=self._slot_w, **out)
         else:
             # one launch over the problems, reading each one's start / control /
             # geom-pose block where the planner stages one (None: the model's own)
             self.engine.rollout_cost_state(self._xf.view(B * n, self.nvar), MPCR_LAYOUT_XI, self._par, B,
                                            self._costs[it], start=self._state, ctrl=self._ctrl,
                                            geom_pose=self._gpose, geom_pose_per_step=self.geom_poses == "per_step",
-                                           target=self._target, target_per_step=self.target_schedule, **out)
+                                           target=self._target, target_per_step=self.target_schedule,
+                                           slot_w=self._slot_w, **out)
 
     def _seg_local_update(self, it):
         """compute_ellite_samples + compute_mean_cov on one rank (:355-360)."""
@@ -500,6 +517,29 @@ class cem_planner:  # noqa: N801 (reference name)
                                  + (f" or {whole}, one per scenario" if whole != full else "") + f", got {g.shape}")
             self._gpose[p].copy_(torch.as_tensor(np.broadcast_to(g, whole).copy()))
 
+    def _stage_slot_weights(self, blocks):
+        """Each problem's slot-weight block into the static buffer: (nslot,)
+        (``Model.slot_weights``) or, with scenarios, also (S, nslot), one per
+        scenario.  None keeps what is staged (at first ones).  Every rank of a
+        sharded planner stages the same block."""
+        import torch
+        if blocks is None:
+            return
+        if not self.collision_weights:
+            raise ValueError("slot weights need a planner built with collision_weights=True")
+        if len(blocks) != self.num_problems:
+            raise ValueError(f"{len(blocks)} slot-weight blocks for {self.num_problems} problem(s)")
+        ns, S = self.engine.nslot, self.num_scenarios
+        for p, w in enumerate(blocks):
+            if w is None:
+                continue
+            w = np.asarray(w.cpu() if hasattr(w, "cpu") else w, dtype=np.float32)
+            if w.shape != (ns,) and not (S > 1 and w.shape == (S, ns)):
+                raise ValueError(f"a slot-weight block is ({ns},)" + (f" or ({S}, {ns}), one per scenario" if S > 1 else "")
+                                 + f"; got {w.shape}")
+            self._slot_w[p][..., :ns].copy_(torch.as_tensor(np.broadcast_to(w, tuple(self._slot_w.shape[1:-1]) + (ns,))
+                                                            .copy()))
+
     def _stage_targets(self, trajs, target_pos, target_rot):
         """Each problem's target schedule into the static buffer: (H, 8) target
         rows (``Engine.target_rows``) or a (pos (H, 3), rot (H, 4)) pair; with
@@ -536,7 +576,8 @@ class cem_planner:  # noqa: N801 (reference name)
         self._target.copy_(torch.as_tensor(out))
 
     def compute_cem(self, xi_mean, init_pos=(1.5, -1.8, 1.75, -1.25, -1.6, 0.0), init_vel=None, init_acc=None,
-                    target_pos=None, target_rot=None, state=None, ctrl=None, geom_pose=None, target_traj=None):
+                    target_pos=None, target_rot=None, state=None, ctrl=None, geom_pose=None, target_traj=None,
+                    slot_w=None):
         """One MPC tick of CEM (SBP/mjx_planner.py:364-406). Returns the reference 9-tuple (numpy).
         state (planners built with plan_from_state): the full state the
         rollouts start from, a ``Plant`` or ``(qpos, qvel[, qacc_warmstart])``;
@@ -550,7 +591,10 @@ class cem_planner:  # noqa: N801 (reference name)
         built with target_schedule): the target pose of every step of the
         horizon, (H, 8) target rows or a (pos (H, 3), rot (H, 4)) pair, with
         scenarios also (S, H, 8); None holds target_pos / target_rot over
-        the horizon."""
+        the horizon.  slot_w (planners built with collision_weights): what
+        each contact slot costs, (nslot,) (``Model.slot_weights``) or, with
+        scenarios, also (S, nslot); None keeps the block staged last (at
+        first ones)."""
         import torch
 
         from . import dist as mdist
@@ -575,6 +619,7 @@ class cem_planner:  # noqa: N801 (reference name)
         self._stage_ctrls(None if ctrl is None else [ctrl])
         self._stage_geom_poses(None if geom_pose is None else [geom_pose])
         self._stage_targets(None if target_traj is None else [target_traj], target_pos[None], target_rot[None])
+        self._stage_slot_weights(None if slot_w is None else [slot_w])
         self._run_iterations()
 
         costs, theta, thetadot = self._costs, self._theta, self._thetadot
@@ -601,7 +646,8 @@ class cem_planner:  # noqa: N801 (reference name)
         return tuple(o.cpu().numpy() if isinstance(o, torch.Tensor) else o for o in out)
 
     def compute_cem_batch(self, xi_mean, init_pos, init_vel=None, init_acc=None, target_pos=None, target_rot=None,
-                          weights=None, states=None, ctrls=None, geom_poses=None, target_trajs=None):
+                          weights=None, states=None, ctrls=None, geom_poses=None, target_trajs=None,
+                          slot_ws=None):
         """One MPC tick of ``num_problems`` independent CEM problems in one
         batched sequence of launches (each kernel of ``compute_cem`` once,
         over every problem): xi_mean (B, nvar), init_pos / init_vel /
@@ -618,7 +664,9 @@ class cem_planner:  # noqa: N801 (reference name)
         problem, likewise.  target_trajs (planners built with
         target_schedule): one target trajectory per problem as
         ``compute_cem``'s ``target_traj``; a None entry holds that problem's
-        target_pos / target_rot over the horizon."""
+        target_pos / target_rot over the horizon.  slot_ws (planners built
+        with collision_weights): one slot-weight block per problem as
+        ``compute_cem``'s ``slot_w``; a None entry keeps that problem's."""
         import torch
 
         B, d, H, n, it_n = self.num_problems, self.num_dof, self.num, self.n_local, self.maxiter_cem
@@ -646,6 +694,7 @@ class cem_planner:  # noqa: N801 (reference name)
         self._stage_ctrls(ctrls)
         self._stage_geom_poses(geom_poses)
         self._stage_targets(target_trajs, target_pos, target_rot)
+        self._stage_slot_weights(slot_ws)
         self._run_iterations()
 
         # each problem's best candidate of the last iteration: the low word of

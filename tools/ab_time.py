@@ -8,7 +8,9 @@ or sched (one row per step), and GEOM=none, const (one block of the model's
 own static geom poses) or sched (one block per step); START=1 starts from a
 block holding the template state, which alone selects the STATE kernels;
 TARGET=none, const (one target row, the parameter block's) or sched (one row
-per step, the target translating and yawing over the horizon)."""
+per step, the target translating and yawing over the horizon); SLOTW=none,
+ones (one slot-weight block of ones) or mixed (one block of weights 0, 0.25,
+1 and 2 in turn)."""
 import os
 import sys
 
@@ -44,6 +46,7 @@ key = torch.empty(1, dtype=torch.int64, device="cuda")
 args = (xi, MPCR_LAYOUT_XI, q0, (20., 3., 80.), (-0.3, -0.3, 0.5), (0., 1., 0., 0.))
 entry, ctrl_mode = os.environ.get("ENTRY", "cost"), os.environ.get("CTRL", "none")
 geom_mode, target_mode = os.environ.get("GEOM", "none"), os.environ.get("TARGET", "none")
+slotw_mode = os.environ.get("SLOTW", "none")
 if entry == "state":
     par = torch.as_tensor(Engine.params(*args[2:])).cuda()
     ckw = {}
@@ -63,6 +66,10 @@ if entry == "state":
         rows = torch.as_tensor(Engine.target_rows(pos, 1.7 * rot)).cuda()
         ckw |= dict(target=rows[0].contiguous()) if target_mode == "const" else dict(target=rows[None].contiguous(),
                                                                                      target_per_step=True)
+    if slotw_mode != "none":
+        ns4 = (e.nslot + 3) & ~3
+        w = np.ones(ns4, np.float32) if slotw_mode == "ones" else np.tile(np.float32([0, 0.25, 1, 2]), ns4 // 4)
+        ckw["slot_w"] = torch.as_tensor(w).cuda()
 
     def run(theta=None, thetadot=None, best_key=None, status=None):
         e.rollout_cost_state(xi, MPCR_LAYOUT_XI, par, 1, c4, theta=theta, thetadot=thetadot, best_keys=best_key,
@@ -95,7 +102,7 @@ sv = st.cpu().numpy()
 rows = f" rows/step {float((sv >> 11).mean()) / H:.1f} max-rows p50/p90/p99 " + "/".join(
     str(int(np.percentile((sv >> 2) & 255, q))) for q in (50, 90, 99))
 tag = (f" {entry}/ctrl={ctrl_mode}/geom={geom_mode}/start={os.environ.get('START', '0')}/target={target_mode}"
-       if entry == "state" else "")
+       + (f"/slotw={slotw_mode}" if slotw_mode != "none" else "") if entry == "state" else "")
 print(f"{os.path.basename(sys.argv[1])}{tag}{occ}{rows} {name} {n}x{H} median {np.median(ts):.3f} ms min {np.min(ts):.3f} "
       f"-> {n / np.median(ts) * 1e3:.0f} rollouts/s  cost0 {float(c4[:, 0].sum()):.6e}")
 if os.environ.get("SAVE"):  # outputs of the last launch, for bitwise comparisons between variants
