@@ -375,6 +375,40 @@ int mpcr_rollout_cost_slotw(mpcr_engine* e, const float* input, int layout, int 
                             float* theta, float* thetadot, uint64_t* best_keys, int index_base, int* status,
                             int flags, void* stream);
 
+/* mpcr_rollout_cost_slotw with the weight of each step's cost terms as an
+   input of the call (a backward-compatible addition; mpcr_rollout_cost_slotw
+   is this call with step_w = NULL): running against terminal cost, a
+   discount, a term that counts only on arrival.  step_w (nullable): device
+   memory, 16-byte aligned, H contiguous rows of 4 floats, a_pos a_rot a_col 0
+   (float 3 is reserved and never read).  With a schedule
+     cost_g = sum_t a_pos[t] |p_t - ptgt_t|
+     cost_r = sum_t a_rot[t] 2 acos(clamp(|q_t . qtgt_t| / |q_t|))
+     cost_c = sum_t sum_s (a_col[t] w[s]) ([d_t,s < 0] + [t > 0] relu(0.995 d_t-1,s - d_t,s))
+   and cost = w_pos cost_g + w_rot cost_r + w_col cost_c as ever; the best key
+   follows the total.  t is the absolute step of the horizon; the approach
+   term of step t is priced by row t; w[s] is the slot-weight block, or 1.  The
+   values are used as they are (0 switches a step off, values may exceed 1).
+   Problem p reads rows step_w + p step_w_stride + 4 t: the stride is in
+   floats, a multiple of 4, and 0 (one schedule for every problem) or at least
+   4 H.  There is no step stride.  Cost only: a schedule of all ones is
+   bitwise the call without one in every output (one multiply per term, the
+   sums in the order they had); any schedule leaves theta, thetadot,
+   final_state and status bitwise unchanged; a schedule that differs from ones
+   in one column leaves the other two cost columns bitwise unchanged; the slot
+   history records every distance, and which contacts act on the dynamics
+   does not depend on it.  Read when the kernel runs (graph-capturable; a
+   replay sees new contents), never written.  A model without slots takes a
+   schedule (a_pos and a_rot).  MPCR_EINVAL: host memory, a misaligned
+   pointer, a stride that is no multiple of 4 or lies in (0, 4 H), host
+   parameters. */
+int mpcr_rollout_cost_stepw(mpcr_engine* e, const float* input, int layout, int nprob, int n_per,
+                            const float* params, const float* start, int start_stride, float* final_state,
+                            const float* ctrl, int ctrl_stride, int ctrl_step_stride, const float* geom_pose,
+                            int geom_stride, int geom_step_stride, const float* target, int target_stride,
+                            int target_step_stride, const float* slot_w, int slot_w_stride, const float* step_w,
+                            int step_w_stride, float* cost4, float* theta, float* thetadot, uint64_t* best_keys,
+                            int index_base, int* status, int flags, void* stream);
+
 /* Fold the costs of candidates that were rolled out in several scenarios
    (world hypotheses) into one row each.  cost4_scen holds nprob nscen n_per
    rows of 4 (a rollout's cost4: total | goal | rotation | collision):
@@ -454,6 +488,22 @@ int mpcr_rollout_cost_scenarios_slotw(mpcr_engine* e, const float* input, int la
                                       int target_step_stride, const float* slot_w, int slot_w_stride,
                                       float* cost4_scen, float* cost4, float* theta, float* thetadot,
                                       uint64_t* best_keys, int index_base, int* status, int flags, void* stream);
+
+/* mpcr_rollout_cost_scenarios_slotw with step weights (a backward-compatible
+   addition; mpcr_rollout_cost_scenarios_slotw is this call with step_w =
+   NULL): step_w and step_w_stride as in mpcr_rollout_cost_stepw, the stride
+   per rollout problem r = p nscen + s, so each hypothesis may have its own
+   schedule.  The same invariants hold.  Each scenario's slice is bitwise what
+   mpcr_rollout_cost_stepw computes for that scenario's blocks alone. */
+int mpcr_rollout_cost_scenarios_stepw(mpcr_engine* e, const float* input, int layout, int nprob, int nscen,
+                                      int worst, int n_per, const float* params, const float* start,
+                                      int start_stride, float* final_state, const float* ctrl, int ctrl_stride,
+                                      int ctrl_step_stride, const float* geom_pose, int geom_stride,
+                                      int geom_step_stride, const float* target, int target_stride,
+                                      int target_step_stride, const float* slot_w, int slot_w_stride,
+                                      const float* step_w, int step_w_stride, float* cost4_scen, float* cost4,
+                                      float* theta, float* thetadot, uint64_t* best_keys, int index_base, int* status,
+                                      int flags, void* stream);
 
 /* Closed-loop plant: one environment of the model, stepped by the rollout
    kernel (fp32 state resident on the device).  Created at the template

@@ -100,6 +100,11 @@ _ARGTYPES = {
     "mpcr_rollout_cost_scenarios_slotw": [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _i,
                                           _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp],
     "mpcr_model_slots": [_vp, _P(_i), _P(_i), _P(_i), _P(_i)],
+    # cost weights per step as a call input
+    "mpcr_rollout_cost_stepw": [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _i, _i, _vp,
+                                _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp],
+    "mpcr_rollout_cost_scenarios_stepw": [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _i,
+                                          _vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp],
 }
 # every symbol include/mpcr.h declares (tests check the exports)
 EXPORTS = tuple(_ARGTYPES)

@@ -59,7 +59,8 @@ __device__ __forceinline__ void emit_contacts(const DevModel* __restrict__ m, S&
                                               int t, int H, bool valid, int p, int nsl, const float dist[4],
                                               const float pos[4][3], const float nrm[4][3], float& cost_c,
                                               SlotHist<S>& sh, int k,
-                                              [[maybe_unused]] const float4* rq = nullptr) {
+                                              [[maybe_unused]] const float4* rq = nullptr,
+                                              [[maybe_unused]] float a_col = 1.f) {
   int act = 0;
   if (valid) {
     // single-arm kernels: slot address, slot count and margin from the pair's
@@ -85,6 +86,16 @@ __device__ __forceinline__ void emit_contacts(const DevModel* __restrict__ m, S&
           for (int c = 0; c < 4; c++)
             if (c < ns) w[c] = wp[c];
         }
+        // the call's step weights (StepWArgs): this step's a_col -- the
+        // caller's, read once ahead of the phase (single-arm kernels), or read
+        // here like the slot weights (dual-arm kernels) -- folds into the slot
+        // weights: cost_c += (a_col[t] w[slot]) * term, the approach term of
+        // step t included.  1 (no schedule, or ones) leaves w what it was.
+        if constexpr (S::WIDE) {
+          if (const float* row = step_w_row(b, t)) a_col = row[2];
+        }
+#pragma unroll
+        for (int c = 0; c < 4; c++) w[c] *= a_col;
       }
       if constexpr (SlotHist<S>::NC == 2) {
         // single-arm kernels: the chunk index is the wave's, so a scalar branch

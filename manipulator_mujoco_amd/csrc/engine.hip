@@ -522,6 +522,7 @@ struct Launch {
   // planning problem that share its input rows, 0: none; the target schedule, null: the parameter block's target)
   CallBlocks blk = {};
   SlotWArgs sw = {};  // the contact slots' weights (rollout.h; null: every slot at 1)
+  StepWArgs stw = {};  // the cost weights per step (rollout.h; null: every step at 1)
 };
 
 // the kernel's arguments for launch l of engine e (the one place they are filled)
@@ -567,8 +568,10 @@ static int rollout_args(const mpcr_engine* e, const Launch& l, RolloutArgs& a) {
     a.sw = l.sw;
   } else {
     const StateArgs& s = l.blk.st;
-    if (s.start || s.final_state || s.ctrl || s.geom_pose || l.blk.nscen || l.blk.tg.target || l.sw.slot_w)
-      return fail(MPCR_EINVAL, "state, control, geom-pose and slot-weight blocks need a device parameter block");
+    if (s.start || s.final_state || s.ctrl || s.geom_pose || l.blk.nscen || l.blk.tg.target || l.sw.slot_w ||
+        l.stw.step_w)
+      return fail(MPCR_EINVAL, "state, control, geom-pose, slot-weight and step-weight blocks need a device "
+                               "parameter block");
     std::memcpy(a.par, l.par, sizeof(a.par));
   }
   return MPCR_OK;
@@ -578,8 +581,9 @@ static int launch_rollout(mpcr_engine* e, const Launch& l, hipStream_t st) {
   RolloutArgs a;
   if (int rc = rollout_args(e, l, a)) return rc;
   if (l.key && l.reset_key) hipLaunchKernelGGL(fill_u64, dim3(l.nprob), dim3(1), 0, st, l.key, ~0ull);
+  // (the step weights ride beside the arguments, as the kernels' third: rollout.h StepWArgs)
   rollout_launch(e->wide, a, (const DevModel*)e->d_model, l.n, st, e->seg_groups, e->seg_stream,
-                 e->seg_event);
+                 e->seg_event, l.stw);
   HIPCHK(hipGetLastError());
   return MPCR_OK;
 }
@@ -714,7 +718,8 @@ static bool device_memory(const void* p, int d) {
 // p, addressed by `stem`_stride and `stem`_step_stride in floats, one unit of
 // `unit` floats (named `unit_name`) per step.  align: bytes its rows are
 // aligned to (0: no demand).  ctrl: nu floats; geom_pose: 8 ngeom, 16 bytes;
-// target: a row of 8, 16 bytes; slot_w: nslot floats, 16 bytes, no step stride.
+// target: a row of 8, 16 bytes; slot_w: nslot floats, 16 bytes, no step stride;
+// step_w: 4 H floats (H contiguous rows of 4), 16 bytes, no step stride.
 static int check_block(const mpcr_engine* e, const char* name, const char* stem, const float* p, int stride,
                        int step_stride, const char* unit_name, int unit, int align) {
   if (align && ((reinterpret_cast<uintptr_t>(p) & (align - 1)) || (stride & (align / 4 - 1)) ||
@@ -782,6 +787,16 @@ static int rollout_call(mpcr_engine* e, Launch& l, int flags, void* stream) {
     sw.stride = 0;
   }
   sw.pad_ = 0;
+  // (a model without slots is fine: the pose columns price the dual arm too)
+  StepWArgs& stw = l.stw;
+  if (stw.step_w) {
+    if (int rc = check_block(e, "step_w", "step_w", stw.step_w, stw.stride, 0, "4 H", 4 * e->H, 16)) return rc;
+    if (!step_w_stride_ok(stw.stride, e->H))  // (check_block's rules, restated where a host program can test them)
+      return fail(MPCR_EINVAL, "step_w_stride=%d: 0 or a multiple of 4 floats at least 4 H=%d", stw.stride, 4 * e->H);
+  } else {
+    stw.stride = 0;
+  }
+  stw.pad_ = 0;
   if (int rc = check_layout(l.layout)) return rc;
   if (!l.in || !l.dpar || !l.cost4) return fail(MPCR_EINVAL, "null argument");
   HIPCHK(hipSetDevice(e->device));
@@ -819,13 +834,14 @@ extern "C" int mpcr_rollout_cost_multi(mpcr_engine* e, const float* input, int l
   return rollout_call(e, l, flags, stream);
 }
 
-extern "C" int mpcr_rollout_cost_slotw(mpcr_engine* e, const float* input, int layout, int nprob, int n_per,
-                                        const float* params, const float* start, int start_stride, float* final_state,
-                                        const float* ctrl, int ctrl_stride, int ctrl_step_stride,
-                                        const float* geom_pose, int geom_stride, int geom_step_stride,
-                                        const float* target, int target_stride, int target_step_stride,
-                                        const float* slot_w, int slot_w_stride, float* cost4, float* theta, float* thetadot, uint64_t* best_keys, int index_base,
-                                        int* status, int flags, void* stream) {
+extern "C" int mpcr_rollout_cost_stepw(mpcr_engine* e, const float* input, int layout, int nprob, int n_per,
+                                       const float* params, const float* start, int start_stride, float* final_state,
+                                       const float* ctrl, int ctrl_stride, int ctrl_step_stride,
+                                       const float* geom_pose, int geom_stride, int geom_step_stride,
+                                       const float* target, int target_stride, int target_step_stride,
+                                       const float* slot_w, int slot_w_stride, const float* step_w, int step_w_stride,
+                                       float* cost4, float* theta, float* thetadot, uint64_t* best_keys,
+                                       int index_base, int* status, int flags, void* stream) {
   if (!e) return fail(MPCR_EINVAL, "null argument");
   if (!(flags & MPCR_F_DEVICE_PTRS)) return fail(MPCR_EINVAL, "mpcr_rollout_cost_state takes device pointers");
   if (int rc = check_multi(nprob, n_per, e->max_n)) return rc;
@@ -838,7 +854,22 @@ extern "C" int mpcr_rollout_cost_slotw(mpcr_engine* e, const float* input, int l
   l.blk.st.geom_pose = geom_pose; l.blk.st.geom_stride = geom_stride; l.blk.st.geom_step_stride = geom_step_stride;
   l.blk.tg.target = target; l.blk.tg.stride = target_stride; l.blk.tg.step_stride = target_step_stride;
   l.sw.slot_w = slot_w; l.sw.stride = slot_w_stride;
+  l.stw.step_w = step_w; l.stw.stride = step_w_stride;
   return rollout_call(e, l, flags, stream);
+}
+
+extern "C" int mpcr_rollout_cost_slotw(mpcr_engine* e, const float* input, int layout, int nprob, int n_per,
+                                       const float* params, const float* start, int start_stride, float* final_state,
+                                       const float* ctrl, int ctrl_stride, int ctrl_step_stride,
+                                       const float* geom_pose, int geom_stride, int geom_step_stride,
+                                       const float* target, int target_stride, int target_step_stride,
+                                       const float* slot_w, int slot_w_stride, float* cost4, float* theta,
+                                       float* thetadot, uint64_t* best_keys, int index_base, int* status, int flags,
+                                       void* stream) {
+  return mpcr_rollout_cost_stepw(e, input, layout, nprob, n_per, params, start, start_stride, final_state, ctrl,
+                                 ctrl_stride, ctrl_step_stride, geom_pose, geom_stride, geom_step_stride, target,
+                                 target_stride, target_step_stride, slot_w, slot_w_stride, nullptr, 0, cost4, theta,
+                                 thetadot, best_keys, index_base, status, flags, stream);
 }
 
 extern "C" int mpcr_rollout_cost_target(mpcr_engine* e, const float* input, int layout, int nprob, int n_per,
@@ -904,15 +935,16 @@ extern "C" int mpcr_scenario_reduce(mpcr_engine* e, const float* cost4_scen, int
   return MPCR_OK;
 }
 
-extern "C" int mpcr_rollout_cost_scenarios_slotw(mpcr_engine* e, const float* input, int layout, int nprob, int nscen,
-                                                  int worst, int n_per, const float* params, const float* start,
-                                                  int start_stride, float* final_state, const float* ctrl,
-                                                  int ctrl_stride, int ctrl_step_stride, const float* geom_pose,
-                                                  int geom_stride, int geom_step_stride, const float* target,
-                                                  int target_stride, int target_step_stride, const float* slot_w,
-                                                  int slot_w_stride, float* cost4_scen,
-                                                  float* cost4, float* theta, float* thetadot, uint64_t* best_keys,
-                                                  int index_base, int* status, int flags, void* stream) {
+extern "C" int mpcr_rollout_cost_scenarios_stepw(mpcr_engine* e, const float* input, int layout, int nprob, int nscen,
+                                                 int worst, int n_per, const float* params, const float* start,
+                                                 int start_stride, float* final_state, const float* ctrl,
+                                                 int ctrl_stride, int ctrl_step_stride, const float* geom_pose,
+                                                 int geom_stride, int geom_step_stride, const float* target,
+                                                 int target_stride, int target_step_stride, const float* slot_w,
+                                                 int slot_w_stride, const float* step_w, int step_w_stride,
+                                                 float* cost4_scen, float* cost4, float* theta, float* thetadot,
+                                                 uint64_t* best_keys, int index_base, int* status, int flags,
+                                                 void* stream) {
   if (!e) return fail(MPCR_EINVAL, "null argument");
   if (!(flags & MPCR_F_DEVICE_PTRS)) return fail(MPCR_EINVAL, "mpcr_rollout_cost_scenarios takes device pointers");
   if (int rc = check_scenarios(nprob, nscen, n_per, worst, e->max_n)) return rc;
@@ -932,12 +964,29 @@ extern "C" int mpcr_rollout_cost_scenarios_slotw(mpcr_engine* e, const float* in
   l.blk.st.geom_pose = geom_pose; l.blk.st.geom_stride = geom_stride; l.blk.st.geom_step_stride = geom_step_stride;
   l.blk.tg.target = target; l.blk.tg.stride = target_stride; l.blk.tg.step_stride = target_step_stride;
   l.sw.slot_w = slot_w; l.sw.stride = slot_w_stride;
+  l.stw.step_w = step_w; l.stw.stride = step_w_stride;
   if (int rc = rollout_call(e, l, flags & ~(MPCR_F_SYNC | MPCR_F_RESET_BEST), stream)) return rc;
   if (cost4)
     return mpcr_scenario_reduce(e, cost4_scen, nprob, nscen, n_per, worst, cost4, best_keys, index_base, flags,
                                 stream);
   if (flags & MPCR_F_SYNC) HIPCHK(hipStreamSynchronize((hipStream_t)stream));
   return MPCR_OK;
+}
+
+extern "C" int mpcr_rollout_cost_scenarios_slotw(mpcr_engine* e, const float* input, int layout, int nprob, int nscen,
+                                                 int worst, int n_per, const float* params, const float* start,
+                                                 int start_stride, float* final_state, const float* ctrl,
+                                                 int ctrl_stride, int ctrl_step_stride, const float* geom_pose,
+                                                 int geom_stride, int geom_step_stride, const float* target,
+                                                 int target_stride, int target_step_stride, const float* slot_w,
+                                                 int slot_w_stride, float* cost4_scen, float* cost4, float* theta,
+                                                 float* thetadot, uint64_t* best_keys, int index_base, int* status,
+                                                 int flags, void* stream) {
+  return mpcr_rollout_cost_scenarios_stepw(e, input, layout, nprob, nscen, worst, n_per, params, start, start_stride,
+                                           final_state, ctrl, ctrl_stride, ctrl_step_stride, geom_pose, geom_stride,
+                                           geom_step_stride, target, target_stride, target_step_stride, slot_w,
+                                           slot_w_stride, nullptr, 0, cost4_scen, cost4, theta, thetadot, best_keys,
+                                           index_base, status, flags, stream);
 }
 
 extern "C" int mpcr_rollout_cost_scenarios_target(mpcr_engine* e, const float* input, int layout, int nprob, int nscen,

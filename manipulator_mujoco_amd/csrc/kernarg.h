@@ -1,5 +1,5 @@
 // kernarg.h -- how the rollout kernels read their launch arguments (KA, KSA, KSCEN,
-// KTA, KSW, ARGS_HAS, DBG_LAST).
+// KTA, KSW, KSTW, ARGS_HAS, DBG_LAST).
 #pragma once
 #include "rollout.h"
 
@@ -69,6 +69,22 @@ __device__ __forceinline__ unsigned args_flags(const RolloutArgs& a) {
 // The slot weights (KSW->field) likewise, in both units: read at the use, in
 // emit_contacts, so nothing of them lives across the step loop
 #define KSW kernarg_at<SlotWArgs>(offsetof(RolloutArgs, sw))
+// The step weights (KSTW->field) likewise -- the kernels' third argument, at
+// STW_KERNARG of the segment: read at the two uses, the pose cost and the head
+// of the collision phase, once a step each
+#define KSTW kernarg_at<StepWArgs>(STW_KERNARG)
+// the schedule row (a_pos a_rot a_col 0) of absolute step t for candidate b's
+// problem, null without a schedule: the pointer, the stride and the problem
+// fields from the segment at the use (as emit_contacts reads the slot weights),
+// so no register holds anything of the schedule across the step loop and a
+// resumed horizon segment finds the same row
+__device__ __forceinline__ const float* step_w_row(int b, int t) {
+  const float* sp = KSTW->step_w;
+  if (!sp) return nullptr;
+  const int pn = *kernarg_at<int>(offsetof(RolloutArgs, prob_n));
+  const int po = *kernarg_at<int>(offsetof(RolloutArgs, prob_off));
+  return sp + (size_t)(pn ? (po + b) / pn : 0) * (unsigned)KSTW->stride + 4 * (size_t)t;
+}
 
 // The debug dump's test (candidate 0's last step, RolloutArgs::dbg given).  The
 // single-arm kernels test the step and the candidate first, values the loop

@@ -138,6 +138,30 @@ struct SlotWArgs {
 };
 static_assert(sizeof(SlotWArgs) == 16 && offsetof(SlotWArgs, slot_w) == 0 && offsetof(SlotWArgs, stride) == 8,
               "SlotWArgs: one pointer and one int");
+// stw: when the cost's terms matter (mpcr_rollout_cost_stepw): a schedule of H
+// rows of 4 floats, a_pos a_rot a_col 0, 16-byte aligned, rows contiguous, read
+// when the kernel runs and never written; float 3 is never read.  Step t
+// (absolute, so horizon segments agree) enters cost_g as a_pos[t] |p - ptgt|,
+// cost_r as a_rot[t] times the angle and cost_c as (a_col[t] w[s]) times slot
+// s's penetration and approach terms of that step: one multiply per term, the
+// sums in the order they had, the values used as they are.  Problem p (with
+// scenarios: rollout problem r = p nscen + s) reads the rows at step_w + p
+// stride + 4 t (floats; stride a multiple of 4, 0: one schedule for every
+// problem, otherwise at least 4 H).  Null prices every step at 1.  Cost only,
+// like the slot weights.  It is not a member of RolloutArgs, whose layout
+// stays what it was: it is the kernels' third argument, behind the model
+// pointer (STW_KERNARG below), so no other argument moves.  Set only with
+// dpar, read only by the STATE / SCEN instantiations.
+struct StepWArgs {
+  const float* step_w;
+  int stride;
+  int pad_;
+};
+static_assert(sizeof(StepWArgs) == 16 && offsetof(StepWArgs, step_w) == 0 && offsetof(StepWArgs, stride) == 8,
+              "StepWArgs: one pointer and one int");
+// the stride rule of a schedule over H steps: floats, a multiple of 4, and 0 or
+// at least the 4 H floats a problem reads (rollout_call refuses the others)
+inline bool step_w_stride_ok(int stride, int H) { return (stride & 3) == 0 && (stride == 0 || stride >= 4 * H); }
 static_assert(sizeof(StateArgs) == 56 && offsetof(StateArgs, start) == 0 && offsetof(StateArgs, final_state) == 8 &&
                   offsetof(StateArgs, start_stride) == 16 && offsetof(StateArgs, ctrl_stride) == 20 &&
                   offsetof(StateArgs, ctrl_step_stride) == 24 && offsetof(StateArgs, ctrl) == 32 &&
@@ -212,6 +236,10 @@ static_assert(offsetof(RolloutArgs, blk) == 216 && offsetof(RolloutArgs, sw) == 
                   offsetof(RolloutArgs, prob_n) == 312 && offsetof(RolloutArgs, prob_off) == 316 &&
                   sizeof(RolloutArgs) == 320,
               "the slot weights behind the union; the problem fields end the arguments as they did");
+// where the kernels' third argument, the step weights, sits in the kernarg
+// segment: behind RolloutArgs (offset 0) and the model pointer
+constexpr size_t STW_KERNARG = sizeof(RolloutArgs) + sizeof(const DevModel*);
+static_assert(STW_KERNARG == 328 && STW_KERNARG % alignof(StepWArgs) == 0, "the step weights at byte 328 of the segment");
 // the unit quaternion of a target's (parameter block or schedule row): the one
 // expression both go through
 __host__ __device__ inline void target_quat_unit(const float q[4], float out[4]) {
@@ -225,6 +253,10 @@ inline bool has_state(const RolloutArgs& a) {
   if (!a.dpar) return false;
   const StateArgs& s = a.blk.st;
   return s.start || s.final_state || s.ctrl || s.geom_pose || a.blk.nscen > 1 || a.blk.tg.target || a.sw.slot_w;
+}
+// ... or reads a step-weight schedule (the launch's StepWArgs, set only with dpar)
+inline bool has_state(const RolloutArgs& a, const StepWArgs& stw) {
+  return has_state(a) || (a.dpar && stw.step_w);
 }
 // the scenarios of a launch (0: none)
 inline int scenarios(const RolloutArgs& a) { return a.dpar && a.blk.nscen > 1 ? a.blk.nscen : 0; }
@@ -455,10 +487,12 @@ static_assert(sizeof(SmemW) <= 20448, "dual-arm LDS image must fit 8 blocks per 
 // waves (1: one wave per candidate, 2: two), each class in its own translation
 // unit; rollout_plan.h decides wpc, horizon segments and candidate groups
 // the single-arm kernels' (rollout_narrow.hip)
-void rollout_narrow_launch(int wpc, unsigned grid, hipStream_t st, const RolloutArgs& a, const DevModel* dm);
+void rollout_narrow_launch(int wpc, unsigned grid, hipStream_t st, const RolloutArgs& a, const DevModel* dm,
+                           const StepWArgs& stw);
 // the dual-arm kernels' launches and occupancy (rollout_wide.hip); info[0..2]
 // blocks per CU, LDS, VGPRs
-void rollout_wide_launch(int wpc, unsigned grid, hipStream_t st, const RolloutArgs& a, const DevModel* dm);
+void rollout_wide_launch(int wpc, unsigned grid, hipStream_t st, const RolloutArgs& a, const DevModel* dm,
+                         const StepWArgs& stw);
 hipError_t rollout_wide_occupancy(int* info);
 // resident blocks per CU, static LDS bytes, VGPRs: narrow (0..2), wide (3..5)
 hipError_t rollout_occupancy(int* info);

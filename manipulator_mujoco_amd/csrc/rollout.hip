@@ -108,7 +108,7 @@ constexpr int kWideWavesPerSimd = 2, kNarrowWavesPerSimd = 4;
 constexpr int WPCS_SCEN = 4;
 template <int NVW, int NBW, int NGW, bool WIDE, int WPCS = 1, bool MULTI = false, bool STATE = false>
 __global__ void __launch_bounds__(WAVE * (WPCS & 3), WIDE ? kWideWavesPerSimd : kNarrowWavesPerSimd)
-    rollout_kernel(RolloutArgs args, const DevModel* __restrict__ mptr) {
+    rollout_kernel(RolloutArgs args, const DevModel* __restrict__ mptr, StepWArgs) {  // (the third: read through KSTW)
   constexpr int WPC = WPCS & 3;
   constexpr bool SCEN = (WPCS & WPCS_SCEN) != 0;
   static_assert(WPC == 1 || WPC == 2, "waves per candidate");
@@ -905,10 +905,17 @@ __global__ void __launch_bounds__(WAVE * (WPCS & 3), WIDE ? kWideWavesPerSimd : 
       const float* pt = &s.par[PAR_PT];
       const float* qt = &s.par[PAR_QT];
       float dx = ep[0] - pt[0], dy = ep[1] - pt[1], dz = ep[2] - pt[2];
-      cost_g += sqrtf(dx * dx + dy * dy + dz * dz);
+      // the call's step weights (STATE, StepWArgs): this step's a_pos and a_rot
+      // price the two terms, one multiply each and the sums in step order (1,
+      // without a schedule or in it, leaves them bitwise what they were)
+      float a_pos = 1.f, a_rot = 1.f;
+      if constexpr (STATE) {
+        if (const float* row = step_w_row(b, t)) { a_pos = row[0]; a_rot = row[1]; }
+      }
+      cost_g += a_pos * sqrtf(dx * dx + dy * dy + dz * dz);
       float qn = sqrtf(eq[0] * eq[0] + eq[1] * eq[1] + eq[2] * eq[2] + eq[3] * eq[3]);
       float dq = fabsf((eq[0] * qt[0] + eq[1] * qt[1] + eq[2] * qt[2] + eq[3] * qt[3]) / qn);
-      cost_r += 2.f * acosf(clampf(dq, -1.f, 1.f));
+      cost_r += a_rot * (2.f * acosf(clampf(dq, -1.f, 1.f)));
       if (ARGS_HAS(AF_TRACE_EEF, KA->trace_eef)) {
         float* e = KA->trace_eef + ((size_t)b * H + t) * 7;
         e[0] = ep[0]; e[1] = ep[1]; e[2] = ep[2]; e[3] = eq[0]; e[4] = eq[1]; e[5] = eq[2]; e[6] = eq[3];
@@ -1304,6 +1311,20 @@ __global__ void __launch_bounds__(WAVE * (WPCS & 3), WIDE ? kWideWavesPerSimd : 
     // then the convex ones).  With more convex pairs than the lead flush
     // takes, the collision wave runs that narrow phase itself, as before.
     const bool swapm = WPC == 2 && S::WIDE && m->cvx_joint && m->nslot == 0;
+    // the call's step weights (STATE, StepWArgs), single-arm kernels: this
+    // step's a_col, read once ahead of the collision phase on the wave that
+    // prices the contacts and held in one vector register over it -- uniform,
+    // but a scalar would sit on top of the phase's masks, and a read at each
+    // use in emit_contacts cost the one-wave kernel two more spilled scalars.
+    // emit_contacts folds it into the slot weights.  The dual-arm kernels,
+    // with no vector register to spare, read it there, at the use.
+    [[maybe_unused]] float a_col = 1.f;
+    if constexpr (STATE && !S::WIDE) {
+      if (run_coll) {
+        if (const float* row = step_w_row(b, t)) a_col = row[2];
+        asm volatile("" : "+v"(a_col));
+      }
+    }
     for (int pass = 0; pass < 2 && (run_coll || swapm); pass++) {
     bool do_list = false, do_narrow = false;
     if (run_coll) {
@@ -1407,7 +1428,7 @@ __global__ void __launch_bounds__(WAVE * (WPCS & 3), WIDE ? kWideWavesPerSimd : 
       if (run && func != 4 && !defer) nsl = narrow_lane(m, s, hx, p, dist, pos, nrm, nullptr, rq);
       STAMP(11);
       const unsigned long long bbm = __ballot(run && func == 4);
-      emit_contacts<S, STATE>(m, s, args, aflags, b, t, H, valid && func != 4 && !defer, p, nsl, dist, pos, nrm, cost_c, shist, k, rq);
+      emit_contacts<S, STATE>(m, s, args, aflags, b, t, H, valid && func != 4 && !defer, p, nsl, dist, pos, nrm, cost_c, shist, k, rq, a_col);
       STAMP(12);
       if (bbm && !(m->disableflags & 16)) {
         unsigned long long mm = bbm;
@@ -1540,7 +1561,7 @@ __global__ void __launch_bounds__(WAVE * (WPCS & 3), WIDE ? kWideWavesPerSimd : 
             }
             lsl = __float_as_int(o[28]);
           }
-          emit_contacts<S, STATE>(m, s, args, aflags, b, t, H, lane < ncv, lpc, lsl, ld, lp, ln, cost_c, shist, -1);
+          emit_contacts<S, STATE>(m, s, args, aflags, b, t, H, lane < ncv, lpc, lsl, ld, lp, ln, cost_c, shist, -1, nullptr, a_col);
         }
         STAMP(18);
       }
@@ -1592,7 +1613,7 @@ __global__ void __launch_bounds__(WAVE * (WPCS & 3), WIDE ? kWideWavesPerSimd : 
           ncon_w += tot;
           block_sync();  // jcnt is the next round's
         } else if (mine) {
-          emit_contacts<S, STATE>(m, s, args, aflags, b, t, H, v, pc, cn_sl, cd, cp, cn, cost_c, shist, -1);
+          emit_contacts<S, STATE>(m, s, args, aflags, b, t, H, v, pc, cn_sl, cd, cp, cn, cost_c, shist, -1, nullptr, a_col);
         }
         STAMP(18);
       }

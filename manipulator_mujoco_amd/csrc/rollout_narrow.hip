@@ -8,29 +8,30 @@
 namespace mpcr {
 
 // the single-arm kernels' launches (rollout_launch's single-arm branch calls these)
-void rollout_narrow_launch(int wpc, unsigned grid, hipStream_t st, const RolloutArgs& a, const DevModel* dm) {
+void rollout_narrow_launch(int wpc, unsigned grid, hipStream_t st, const RolloutArgs& a, const DevModel* dm,
+                           const StepWArgs& stw) {
   const bool multi = a.prob_n > 0;  // several problems: the MULTI instantiations
   // (the STATE instantiations last: the code object lays the kernels out
   // in the order this chain names them, and the others keep their places)
-  const bool state = has_state(a);  // state blocks: the STATE instantiations (one problem or several)
+  const bool state = has_state(a, stw);  // state blocks: the STATE instantiations (one problem or several)
   if (!state && wpc == 2 && multi)
-    hipLaunchKernelGGL((rollout_kernel<16, 16, 24, false, 2, true>), dim3(grid), dim3(2 * WAVE), 0, st, a, dm);
+    hipLaunchKernelGGL((rollout_kernel<16, 16, 24, false, 2, true>), dim3(grid), dim3(2 * WAVE), 0, st, a, dm, stw);
   else if (!state && wpc == 2)
-    hipLaunchKernelGGL((rollout_kernel<16, 16, 24, false, 2>), dim3(grid), dim3(2 * WAVE), 0, st, a, dm);
+    hipLaunchKernelGGL((rollout_kernel<16, 16, 24, false, 2>), dim3(grid), dim3(2 * WAVE), 0, st, a, dm, stw);
   else if (!state && multi)
-    hipLaunchKernelGGL((rollout_kernel<16, 16, 24, false, 1, true>), dim3(grid), dim3(WAVE), 0, st, a, dm);
+    hipLaunchKernelGGL((rollout_kernel<16, 16, 24, false, 1, true>), dim3(grid), dim3(WAVE), 0, st, a, dm, stw);
   else if (!state)
-    hipLaunchKernelGGL((rollout_kernel<16, 16, 24, false>), dim3(grid), dim3(WAVE), 0, st, a, dm);
+    hipLaunchKernelGGL((rollout_kernel<16, 16, 24, false>), dim3(grid), dim3(WAVE), 0, st, a, dm, stw);
   else if (!scenarios(a) && wpc == 2)
-    hipLaunchKernelGGL((rollout_kernel<16, 16, 24, false, 2, true, true>), dim3(grid), dim3(2 * WAVE), 0, st, a, dm);
+    hipLaunchKernelGGL((rollout_kernel<16, 16, 24, false, 2, true, true>), dim3(grid), dim3(2 * WAVE), 0, st, a, dm, stw);
   else if (!scenarios(a))
-    hipLaunchKernelGGL((rollout_kernel<16, 16, 24, false, 1, true, true>), dim3(grid), dim3(WAVE), 0, st, a, dm);
+    hipLaunchKernelGGL((rollout_kernel<16, 16, 24, false, 1, true, true>), dim3(grid), dim3(WAVE), 0, st, a, dm, stw);
   // (scenarios: the SCEN instantiations, after every other for the same reason)
   else if (wpc == 2)
     hipLaunchKernelGGL((rollout_kernel<16, 16, 24, false, 2 + WPCS_SCEN, true, true>), dim3(grid), dim3(2 * WAVE), 0, st, a,
-                       dm);
+                       dm, stw);
   else
-    hipLaunchKernelGGL((rollout_kernel<16, 16, 24, false, 1 + WPCS_SCEN, true, true>), dim3(grid), dim3(WAVE), 0, st, a, dm);
+    hipLaunchKernelGGL((rollout_kernel<16, 16, 24, false, 1 + WPCS_SCEN, true, true>), dim3(grid), dim3(WAVE), 0, st, a, dm, stw);
 }
 
 hipError_t rollout_occupancy(int* info) {

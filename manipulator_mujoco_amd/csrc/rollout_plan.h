@@ -119,16 +119,17 @@ inline int rollout_dispatches(bool wide, const RolloutArgs& a, unsigned grid, in
 // group's segments in stream order.  The launches of different groups overlap,
 // so one segment's tail is filled by the other groups' work.
 inline void rollout_launch(bool wide, const RolloutArgs& a0, const DevModel* dm, unsigned grid, hipStream_t st,
-                           int groups = 0, hipStream_t* gstream = nullptr, hipEvent_t* gev = nullptr) {
+                           int groups = 0, hipStream_t* gstream = nullptr, hipEvent_t* gev = nullptr,
+                           const StepWArgs& stw = StepWArgs{nullptr, 0, 0}) {
   RolloutArgs a = a0;
   a.t0 = 0;
   a.t1 = a.H;
   const PlanThresholds th = plan_thresholds();
   int G = 1;
   if (!wide) {
-    rollout_narrow_launch(plan_wpc(wide, grid, th), grid, st, a, dm);
+    rollout_narrow_launch(plan_wpc(wide, grid, th), grid, st, a, dm, stw);
   } else if (!seg_plan(wide, a, grid, groups, gstream && gev, th, &G)) {
-    rollout_wide_launch(plan_wpc(wide, grid, th), grid, st, a, dm);
+    rollout_wide_launch(plan_wpc(wide, grid, th), grid, st, a, dm, stw);
   } else {
     // horizon segments over candidate groups on their own streams: each
     // group's segments in its stream's order, the groups overlapping
@@ -145,7 +146,7 @@ inline void rollout_launch(bool wide, const RolloutArgs& a0, const DevModel* dm,
       for (int t0 = 0; t0 < a.H; t0 += a.seg) {
         ga.t0 = t0;
         ga.t1 = std::min(a.H, t0 + a.seg);
-        rollout_wide_launch(1, ng, gs, ga, dm);
+        rollout_wide_launch(1, ng, gs, ga, dm, stw);  // (the schedule is per problem, which prob_off locates)
       }
     }
     if (G > 1)

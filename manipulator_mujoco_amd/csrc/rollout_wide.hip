@@ -12,27 +12,28 @@
 namespace mpcr {
 
 // the dual-arm kernels' launches (rollout_launch's wide branch calls these)
-void rollout_wide_launch(int wpc, unsigned grid, hipStream_t st, const RolloutArgs& a, const DevModel* dm) {
+void rollout_wide_launch(int wpc, unsigned grid, hipStream_t st, const RolloutArgs& a, const DevModel* dm,
+                         const StepWArgs& stw) {
   const bool multi = a.prob_n > 0;  // several problems: the MULTI instantiations
-  const bool state = has_state(a);  // state blocks: the STATE instantiations (one problem or several), named last
+  const bool state = has_state(a, stw);  // state blocks: the STATE instantiations (one problem or several), named last
   if (!state && wpc == 2 && multi)
-    hipLaunchKernelGGL((rollout_kernel<32, 32, 72, true, 2, true>), dim3(grid), dim3(2 * WAVE), 0, st, a, dm);
+    hipLaunchKernelGGL((rollout_kernel<32, 32, 72, true, 2, true>), dim3(grid), dim3(2 * WAVE), 0, st, a, dm, stw);
   else if (!state && wpc == 2)
-    hipLaunchKernelGGL((rollout_kernel<32, 32, 72, true, 2>), dim3(grid), dim3(2 * WAVE), 0, st, a, dm);
+    hipLaunchKernelGGL((rollout_kernel<32, 32, 72, true, 2>), dim3(grid), dim3(2 * WAVE), 0, st, a, dm, stw);
   else if (!state && multi)
-    hipLaunchKernelGGL((rollout_kernel<32, 32, 72, true, 1, true>), dim3(grid), dim3(WAVE), 0, st, a, dm);
+    hipLaunchKernelGGL((rollout_kernel<32, 32, 72, true, 1, true>), dim3(grid), dim3(WAVE), 0, st, a, dm, stw);
   else if (!state)
-    hipLaunchKernelGGL((rollout_kernel<32, 32, 72, true>), dim3(grid), dim3(WAVE), 0, st, a, dm);
+    hipLaunchKernelGGL((rollout_kernel<32, 32, 72, true>), dim3(grid), dim3(WAVE), 0, st, a, dm, stw);
   else if (!scenarios(a) && wpc == 2)
-    hipLaunchKernelGGL((rollout_kernel<32, 32, 72, true, 2, true, true>), dim3(grid), dim3(2 * WAVE), 0, st, a, dm);
+    hipLaunchKernelGGL((rollout_kernel<32, 32, 72, true, 2, true, true>), dim3(grid), dim3(2 * WAVE), 0, st, a, dm, stw);
   else if (!scenarios(a))
-    hipLaunchKernelGGL((rollout_kernel<32, 32, 72, true, 1, true, true>), dim3(grid), dim3(WAVE), 0, st, a, dm);
+    hipLaunchKernelGGL((rollout_kernel<32, 32, 72, true, 1, true, true>), dim3(grid), dim3(WAVE), 0, st, a, dm, stw);
   // scenarios (CallBlocks::nscen > 1): the SCEN instantiations, named after every other
   else if (wpc == 2)
     hipLaunchKernelGGL((rollout_kernel<32, 32, 72, true, 2 + WPCS_SCEN, true, true>), dim3(grid), dim3(2 * WAVE), 0, st, a,
-                       dm);
+                       dm, stw);
   else
-    hipLaunchKernelGGL((rollout_kernel<32, 32, 72, true, 1 + WPCS_SCEN, true, true>), dim3(grid), dim3(WAVE), 0, st, a, dm);
+    hipLaunchKernelGGL((rollout_kernel<32, 32, 72, true, 1 + WPCS_SCEN, true, true>), dim3(grid), dim3(WAVE), 0, st, a, dm, stw);
 }
 hipError_t rollout_wide_occupancy(int* info) {
   const void* k = reinterpret_cast<const void*>(&rollout_kernel<32, 32, 72, true>);

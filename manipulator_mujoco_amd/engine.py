@@ -340,6 +340,25 @@ class Engine:
         return rows
 
     @staticmethod
+    def step_weights(H, discount=1.0, terminal=1.0, running=(1.0, 1.0, 1.0)):
+        """A step-weight schedule (``Engine.rollout_cost_state(step_w=)``),
+        float32 ``(H, 4)``: row t is a_pos a_rot a_col 0 with ``a[t, k] =
+        float32(running[k] * discount**t)``, computed in fp64, and the last
+        row's a_pos and a_rot multiplied by ``terminal`` -- a terminal weight
+        on the pose terms, a discount over the horizon, a running weight per
+        term (``running=(0, 0, 1), terminal=...`` with ``discount=1`` would
+        zero the pose terms of every row, the last included: give the
+        terminal row by hand then).  Column 3 is zero."""
+        H = int(H)
+        run = np.asarray(running, dtype=np.float64).reshape(-1)
+        if H < 1 or run.shape != (3,):
+            raise ValueError(f"step_weights takes H >= 1 and three running weights; got H={H}, running={running!r}")
+        a = np.zeros((H, 4), dtype=np.float64)
+        a[:, :3] = run[None, :] * (float(discount) ** np.arange(H, dtype=np.float64))[:, None]
+        a[H - 1, :2] *= float(terminal)
+        return a.astype(np.float32)
+
+    @staticmethod
     def state_layout():
         """``mpcr_state_layout``: the offsets of a state block's parts and its
         size in floats (no GPU needed)."""
@@ -353,7 +372,7 @@ class Engine:
 
     def _rollout_dp(self, nprob, inp, layout, params, cost4, theta, thetadot, best_keys, index_base, status,
                     reset_best, stream, state=None, ctrl=None, ctrl_per_step=False, geom_pose=None,
-                    geom_pose_per_step=False, target=None, target_per_step=False, slot_w=None):
+                    geom_pose_per_step=False, target=None, target_per_step=False, slot_w=None, step_w=None):
         """nprob None: ``rollout_cost_dp`` (its own C entry, which takes an
         empty batch); else ``rollout_cost_multi`` or, with state = (start,
         final_state), ``rollout_cost_state`` (``mpcr_rollout_cost_world``,
@@ -373,13 +392,16 @@ class Engine:
         if state is not None:
             fn = lib.mpcr_rollout_cost_world
             args += self._state_args(nprob, n, inp, *state, ctrl, ctrl_per_step, geom_pose, geom_pose_per_step)
-            if target is not None or slot_w is not None:
+            if target is not None or slot_w is not None or step_w is not None:
                 fn = lib.mpcr_rollout_cost_target
                 args += self._block_args("target", target, (8,), nprob, inp.device, target_per_step)
-            if slot_w is not None:
+            if slot_w is not None or step_w is not None:
                 fn = lib.mpcr_rollout_cost_slotw
                 slot_w, sw_args = self._slot_w_args(slot_w, nprob, inp.device)
                 args += sw_args
+            if step_w is not None:
+                fn = lib.mpcr_rollout_cost_stepw
+                args += self._block_args("step_w", step_w, (self.H, 4), nprob, inp.device)[:2]
         check(fn(self.handle, _ptr(inp), layout, *shape, *args, _ptr(cost4), _ptr(theta), _ptr(thetadot),
                  _ptr(best_keys), int(index_base), _ptr(status), *_call_tail(inp, reset_best, stream)))
         return cost4
@@ -436,6 +458,8 @@ class Engine:
         with ones) to the next multiple of 4, the block's alignment; rows
         already that long -- a planner's own buffer -- are passed as they are."""
         import torch
+        if t is None:  # (a call that carries only a later block)
+            return None, (None, 0)
         _check_tensor("slot_w", t, device)
         ns4 = (self.nslot + 3) & ~3
         if t.dim() not in (1, 2) or t.shape[-1] not in (self.nslot, ns4):
@@ -475,7 +499,7 @@ class Engine:
                            theta=None, thetadot=None, best_keys=None, index_base: int = 0, status=None,
                            reset_best: bool = True, stream=None, ctrl=None, ctrl_per_step: bool = False,
                            geom_pose=None, geom_pose_per_step: bool = False, target=None,
-                           target_per_step: bool = False, slot_w=None):
+                           target_per_step: bool = False, slot_w=None, step_w=None):
         """``rollout_cost_multi`` from a given full state and / or returning
         the final states (``mpcr_rollout_cost_state``).  ``start``: a device
         tensor of one state block (``pack_state``, ``Plant.copy_state``) shared
@@ -509,12 +533,20 @@ class Engine:
         with one per problem: cost_c sums w[slot] times the slot's terms, the
         values used as they are.  Cost only -- every other output is bitwise
         the call without it, and ones are that call exactly -- and read when
-        the kernel runs.  None prices every slot at 1."""
+        the kernel runs.  None prices every slot at 1.
+        ``step_w`` (``mpcr_rollout_cost_stepw``): when the cost's terms
+        matter, a device tensor of step-weight schedules
+        (``Engine.step_weights``), (H, 4) for every problem or (nprob, H, 4)
+        with one per problem; row t is a_pos a_rot a_col 0 and prices step
+        t's position, rotation and collision terms, the values used as they
+        are.  Cost only -- ones are the call without it exactly, theta,
+        thetadot, final states and statuses never move -- and read when the
+        kernel runs.  None prices every step at 1."""
         return self._rollout_dp(int(nprob), inp, layout, params, cost4, theta, thetadot, best_keys, index_base,
                                 status, reset_best, stream, state=(start, final_state), ctrl=ctrl,
                                 ctrl_per_step=ctrl_per_step, geom_pose=geom_pose,
                                 geom_pose_per_step=geom_pose_per_step, target=target,
-                                target_per_step=target_per_step, slot_w=slot_w)
+                                target_per_step=target_per_step, slot_w=slot_w, step_w=step_w)
 
     @staticmethod
     def _cost_rows(name, t, rows, device=None):
@@ -557,7 +589,7 @@ class Engine:
                                cost4=None, start=None, final_state=None, theta=None, thetadot=None, best_keys=None,
                                index_base: int = 0, status=None, reset_best: bool = True, stream=None, ctrl=None,
                                ctrl_per_step: bool = False, geom_pose=None, geom_pose_per_step: bool = False,
-                               target=None, target_per_step: bool = False, slot_w=None):
+                               target=None, target_per_step: bool = False, slot_w=None, step_w=None):
         """One set of candidates priced in ``nscen`` scenarios per problem
         (``mpcr_rollout_cost_scenarios``).  ``inp`` holds nprob * n_per rows;
         rollout problem r = p nscen + s is scenario s of problem p and is
@@ -574,7 +606,14 @@ class Engine:
         (``mpcr_rollout_cost_scenarios_target``).  ``slot_w``
         (``mpcr_rollout_cost_scenarios_slotw``): (nslot,), (nprob, nslot) -- a
         problem's block for all its scenarios -- or (nprob, nscen, nslot), one
-        per hypothesis.
+        per hypothesis.  ``step_w`` (``mpcr_rollout_cost_scenarios_stepw``):
+        (H, 4), (nprob, H, 4) -- a problem's schedule for all its scenarios --
+        or (nprob, nscen, H, 4), one per hypothesis.  A per-problem ``slot_w``
+        or ``step_w`` given with scenarios, and a ``slot_w`` whose rows need
+        padding, are expanded into a temporary the launch reads: on the
+        current stream the allocator keeps it alive for the kernel; a caller
+        that passes a ``stream=`` of its own should pass the per-scenario
+        (padded) tensor itself and keep it alive until the launch has run.
         Returns ``cost4`` (or ``cost4_scen`` without one).  Graph-capturable."""
         nprob, nscen = int(nprob), int(nscen)
         worst = nscen if worst is None else int(worst)
@@ -594,9 +633,15 @@ class Engine:
         args = self._state_args(R, R * n_per, inp, start, final_state, ctrl, ctrl_per_step, geom_pose,
                                 geom_pose_per_step)
         fn = _lib.load().mpcr_rollout_cost_scenarios
-        if target is not None or slot_w is not None:
+        if target is not None or slot_w is not None or step_w is not None:
             fn = _lib.load().mpcr_rollout_cost_scenarios_target
             args += self._block_args("target", target, (8,), R, inp.device, target_per_step)
+        if step_w is not None:
+            _check_tensor("step_w", step_w, inp.device)
+            if step_w.dim() == 3 and nscen > 1 and step_w.shape[0] == nprob:  # a problem's schedule for its scenarios
+                step_w = step_w.unsqueeze(1).expand(nprob, nscen, *step_w.shape[1:]).contiguous()
+            if step_w.dim() == 4 and tuple(step_w.shape[:2]) == (nprob, nscen):
+                step_w = step_w.reshape(R, *step_w.shape[2:])
         if slot_w is not None:
             fn = _lib.load().mpcr_rollout_cost_scenarios_slotw
             _check_tensor("slot_w", slot_w, inp.device)
@@ -606,6 +651,10 @@ class Engine:
                 slot_w = slot_w.reshape(R, slot_w.shape[-1])
             slot_w, sw_args = self._slot_w_args(slot_w, R, inp.device)
             args += sw_args
+        if step_w is not None:
+            fn = _lib.load().mpcr_rollout_cost_scenarios_stepw
+            args += ((None, 0) if slot_w is None else ()) + self._block_args("step_w", step_w, (self.H, 4), R,
+                                                                             inp.device)[:2]
         check(fn(
             self.handle, _ptr(inp), layout, nprob, nscen, worst, n_per, self._params_arg(params, R), *args,
             _ptr(cost4_scen), _ptr(cost4), _ptr(theta), _ptr(thetadot), _ptr(best_keys), int(index_base),

@@ -24,7 +24,7 @@ import time
 
 import numpy as np
 
-from .engine import Plant
+from .engine import Engine, Plant
 from .planner import cem_planner
 from .quat_math import quaternion_distance
 
@@ -130,7 +130,8 @@ def run_cem_planner(num_dof=None, num_batch=None, num_steps=None, maxiter_cem=No
                     position_threshold=None, rotation_threshold=None, save_data=None, data_dir=None,
                     stop_at_final_target=None, *, max_ticks=100, model_path=None, device=None, graph=True,
                     verbose=True, planner_kwargs=None, plan_from_state=False, ctrl=None, geom_poses=None,
-                    hypotheses=None, scenario_worst=None, target_velocity=None, touch_target=False):
+                    hypotheses=None, scenario_worst=None, target_velocity=None, touch_target=False,
+                    terminal_weight=None, discount=None):
     """Run the CEM planner in closed loop for ``max_ticks`` ticks (headless).
     plan_from_state: every tick's rollouts start from the plant's full state
     (a device copy of its block) instead of the template state with the arm
@@ -161,8 +162,14 @@ def run_cem_planner(num_dof=None, num_batch=None, num_steps=None, maxiter_cem=No
     its collision geoms cost nothing (``cem_planner(collision_weights=)``,
     weight 0): the plan may near and touch the body it is sent to, and every
     other contact costs what it did.  The weights are restored when the target
-    switches; "home" exempts nothing.  False: the loop makes the calls it made."""
+    switches; "home" exempts nothing.  False: the loop makes the calls it made.
+    terminal_weight, discount: the horizon's cost is weighed per step
+    (``cem_planner(cost_schedule=)``, ``Engine.step_weights``): step t's terms
+    count ``discount**t``, and the last step's position and rotation terms
+    ``terminal_weight`` times that.  Staged once, ahead of the first tick.
+    Both None: the flat sum, and the loop makes the calls it made."""
     hypotheses = list(hypotheses or [])
+    scheduled = terminal_weight is not None or discount is not None
     if initial_qpos is None:
         initial_qpos = [1.5, -1.8, 1.75, -1.25, -1.6, 0]
     if target_names is None:
@@ -189,7 +196,8 @@ def run_cem_planner(num_dof=None, num_batch=None, num_steps=None, maxiter_cem=No
                                           | ({"num_scenarios": 1 + len(hypotheses), "scenario_worst": scenario_worst}
                                              if hypotheses else {})
                                           | ({"target_schedule": True} if target_velocity is not None else {})
-                                          | ({"collision_weights": True} if touch_target else {})))
+                                          | ({"collision_weights": True} if touch_target else {})
+                                          | ({"cost_schedule": True} if scheduled else {})))
     log(f"Initialized CEM Planner: {round(time.time() - start_time, 2)}s")
 
     model = cem.model
@@ -263,8 +271,13 @@ def run_cem_planner(num_dof=None, num_batch=None, num_steps=None, maxiter_cem=No
         except ValueError:
             return {"slot_w": m.slot_weights()}
 
+    # the horizon's step weights, staged once: every later tick keeps them
+    step_w = ({"step_w": Engine.step_weights(num_steps, discount=1.0 if discount is None else discount,
+                                             terminal=1.0 if terminal_weight is None else terminal_weight)}
+              if scheduled else {})
     _ = cem.compute_cem(xi_mean, data.qpos[ctrl_q], data.qvel[ctrl_v], data.qacc[ctrl_v], target_pos, target_rot,
-                        **from_plant, **apply_ctrl(0), **apply_geom_poses(0), **touch_weights(target_names[0]))
+                        **from_plant, **apply_ctrl(0), **apply_geom_poses(0), **touch_weights(target_names[0]),
+                        **step_w)
     log(f"Compute CEM: {round(time.time() - start_time, 2)}s")
 
     thetadot = np.zeros(num_dof)
@@ -395,6 +408,10 @@ def main(argv=None):  # SBP/mpc_planner.py:256-314
     parser.add_argument("--touch_target", action="store_true",
                         help="while a target body is current, contacts with its geoms cost nothing: the plan may touch "
                              "the body it is sent to")
+    parser.add_argument("--terminal_weight", type=float, default=None, metavar="K",
+                        help="the last step's position and rotation cost count K times (Engine.step_weights)")
+    parser.add_argument("--discount", type=float, default=None, metavar="G",
+                        help="step t of the horizon counts G**t in every cost term (Engine.step_weights)")
     a = parser.parse_args(argv)
     geom_poses = None
     if a.obstacle is not None:
@@ -417,7 +434,7 @@ def main(argv=None):  # SBP/mpc_planner.py:256-314
                            ctrl=ctrl, geom_poses=geom_poses,
                            hypotheses=[(h[0], [float(x) for x in h[1:]]) for h in a.hypothesis or []],
                            scenario_worst=a.scenario_worst, target_velocity=a.target_velocity,
-                           touch_target=a.touch_target)
+                           touch_target=a.touch_target, terminal_weight=a.terminal_weight, discount=a.discount)
 
 
 if __name__ == "__main__":

@@ -136,6 +136,15 @@ class cem_planner:  # noqa: N801 (reference name)
                         alike: 0 permits a contact, 2 charges it double.  A
                         planner with the flag and nothing staged plans what a
                         planner without it plans, bit for bit
+    cost_schedule       the rollouts weigh each step's cost terms with a row
+                        a_pos a_rot a_col 0 read per problem (and scenario)
+                        from a static device buffer of step-weight schedules
+                        (``compute_cem(step_w=...)``, ``Engine.step_weights``),
+                        initialised to ones, instead of summing the horizon
+                        flat: a terminal weight, a discount, a term that
+                        counts only on arrival.  A planner with the flag and
+                        nothing staged plans what a planner without it plans,
+                        bit for bit
     num_scenarios       world hypotheses per problem (default 1: none).  With
                         S > 1 the state, control and geom-pose buffers hold
                         one block per problem and scenario -- ``compute_cem``'s
@@ -155,7 +164,8 @@ class cem_planner:  # noqa: N801 (reference name)
                  model_path=None, device=None, seed=0, elite_from_filtered=False, graph=False, group=None,
                  gather_rollouts=False, return_rollouts=True, capture_exchange=True, verbose=True,
                  num_problems=1, seed_step=0, plan_from_state=False, actuator_ctrl=False, geom_poses=False,
-                 num_scenarios=1, scenario_worst=None, target_schedule=False, collision_weights=False):
+                 num_scenarios=1, scenario_worst=None, target_schedule=False, collision_weights=False,
+                 cost_schedule=False):
         import torch
         import torch.distributed as tdist
 
@@ -283,6 +293,9 @@ class cem_planner:  # noqa: N801 (reference name)
             if self.engine.nslot == 0:
                 raise ValueError("collision_weights: the model has no robot-masked contact slot")
             self._slot_w = torch.ones((B,) + sb + ((self.engine.nslot + 3) & ~3,), **f32)
+        # one step-weight schedule per problem (and scenario), H rows of 4: ones until a tick stages another
+        self.cost_schedule = bool(cost_schedule)
+        self._step_w = torch.ones((B,) + sb + (H, 4), **f32) if self.cost_schedule else None
         self._graphs = None
         if verbose and self.rank == 0:
             self.print_info()
@@ -332,7 +345,7 @@ class cem_planner:  # noqa: N801 (reference name)
                                                geom_pose=flat(self._gpose),
                                                geom_pose_per_step=self.geom_poses == "per_step",
                                                target=flat(self._target), target_per_step=self.target_schedule,
-                                               slot_w=self._slot_w, **out)
+                                               slot_w=self._slot_w, step_w=self._step_w, **out)
         else:
             # one launch over the problems, reading each one's start / control /
             # geom-pose block where the planner stages one (None: the model's own)
@@ -340,7 +353,7 @@ class cem_planner:  # noqa: N801 (reference name)
                                            self._costs[it], start=self._state, ctrl=self._ctrl,
                                            geom_pose=self._gpose, geom_pose_per_step=self.geom_poses == "per_step",
                                            target=self._target, target_per_step=self.target_schedule,
-                                           slot_w=self._slot_w, **out)
+                                           slot_w=self._slot_w, step_w=self._step_w, **out)
 
     def _seg_local_update(self, it):
         """compute_ellite_samples + compute_mean_cov on one rank (:355-360)."""
@@ -540,6 +553,28 @@ class cem_planner:  # noqa: N801 (reference name)
             self._slot_w[p][..., :ns].copy_(torch.as_tensor(np.broadcast_to(w, tuple(self._slot_w.shape[1:-1]) + (ns,))
                                                             .copy()))
 
+    def _stage_step_weights(self, scheds):
+        """Each problem's step-weight schedule into the static buffer: (H, 4)
+        (``Engine.step_weights``) or, with scenarios, also (S, H, 4), one per
+        scenario.  None keeps what is staged (at first ones).  Every rank of a
+        sharded planner stages the same schedule."""
+        import torch
+        if scheds is None:
+            return
+        if not self.cost_schedule:
+            raise ValueError("step weights need a planner built with cost_schedule=True")
+        if len(scheds) != self.num_problems:
+            raise ValueError(f"{len(scheds)} step-weight schedules for {self.num_problems} problem(s)")
+        H, S = self.num, self.num_scenarios
+        for p, a in enumerate(scheds):
+            if a is None:
+                continue
+            a = np.asarray(a.cpu() if hasattr(a, "cpu") else a, dtype=np.float32)
+            if a.shape != (H, 4) and not (S > 1 and a.shape == (S, H, 4)):
+                raise ValueError(f"a step-weight schedule is ({H}, 4)" + (f" or ({S}, {H}, 4), one per scenario"
+                                                                          if S > 1 else "") + f"; got {a.shape}")
+            self._step_w[p].copy_(torch.as_tensor(np.broadcast_to(a, tuple(self._step_w.shape[1:])).copy()))
+
     def _stage_targets(self, trajs, target_pos, target_rot):
         """Each problem's target schedule into the static buffer: (H, 8) target
         rows (``Engine.target_rows``) or a (pos (H, 3), rot (H, 4)) pair; with
@@ -577,7 +612,7 @@ class cem_planner:  # noqa: N801 (reference name)
 
     def compute_cem(self, xi_mean, init_pos=(1.5, -1.8, 1.75, -1.25, -1.6, 0.0), init_vel=None, init_acc=None,
                     target_pos=None, target_rot=None, state=None, ctrl=None, geom_pose=None, target_traj=None,
-                    slot_w=None):
+                    slot_w=None, step_w=None):
         """One MPC tick of CEM (SBP/mjx_planner.py:364-406). Returns the reference 9-tuple (numpy).
         state (planners built with plan_from_state): the full state the
         rollouts start from, a ``Plant`` or ``(qpos, qvel[, qacc_warmstart])``;
@@ -594,6 +629,9 @@ class cem_planner:  # noqa: N801 (reference name)
         the horizon.  slot_w (planners built with collision_weights): what
         each contact slot costs, (nslot,) (``Model.slot_weights``) or, with
         scenarios, also (S, nslot); None keeps the block staged last (at
+        first ones).  step_w (planners built with cost_schedule): the
+        horizon's step weights, (H, 4) (``Engine.step_weights``) or, with
+        scenarios, also (S, H, 4); None keeps the schedule staged last (at
         first ones)."""
         import torch
 
@@ -620,6 +658,7 @@ class cem_planner:  # noqa: N801 (reference name)
         self._stage_geom_poses(None if geom_pose is None else [geom_pose])
         self._stage_targets(None if target_traj is None else [target_traj], target_pos[None], target_rot[None])
         self._stage_slot_weights(None if slot_w is None else [slot_w])
+        self._stage_step_weights(None if step_w is None else [step_w])
         self._run_iterations()
 
         costs, theta, thetadot = self._costs, self._theta, self._thetadot
@@ -647,7 +686,7 @@ class cem_planner:  # noqa: N801 (reference name)
 
     def compute_cem_batch(self, xi_mean, init_pos, init_vel=None, init_acc=None, target_pos=None, target_rot=None,
                           weights=None, states=None, ctrls=None, geom_poses=None, target_trajs=None,
-                          slot_ws=None):
+                          slot_ws=None, step_ws=None):
         """One MPC tick of ``num_problems`` independent CEM problems in one
         batched sequence of launches (each kernel of ``compute_cem`` once,
         over every problem): xi_mean (B, nvar), init_pos / init_vel /
@@ -666,7 +705,9 @@ class cem_planner:  # noqa: N801 (reference name)
         ``compute_cem``'s ``target_traj``; a None entry holds that problem's
         target_pos / target_rot over the horizon.  slot_ws (planners built
         with collision_weights): one slot-weight block per problem as
-        ``compute_cem``'s ``slot_w``; a None entry keeps that problem's."""
+        ``compute_cem``'s ``slot_w``; a None entry keeps that problem's.
+        step_ws (planners built with cost_schedule): one step-weight schedule
+        per problem as ``compute_cem``'s ``step_w``, likewise."""
         import torch
 
         B, d, H, n, it_n = self.num_problems, self.num_dof, self.num, self.n_local, self.maxiter_cem
@@ -695,6 +736,7 @@ class cem_planner:  # noqa: N801 (reference name)
         self._stage_geom_poses(geom_poses)
         self._stage_targets(target_trajs, target_pos, target_rot)
         self._stage_slot_weights(slot_ws)
+        self._stage_step_weights(step_ws)
         self._run_iterations()
 
         # each problem's best candidate of the last iteration: the low word of

@@ -10,7 +10,8 @@ block holding the template state, which alone selects the STATE kernels;
 TARGET=none, const (one target row, the parameter block's) or sched (one row
 per step, the target translating and yawing over the horizon); SLOTW=none,
 ones (one slot-weight block of ones) or mixed (one block of weights 0, 0.25,
-1 and 2 in turn)."""
+1 and 2 in turn); STEPW=none, ones (one step-weight schedule of ones) or mixed
+(one schedule discounted by 0.85 a step, the last step's pose terms times 4)."""
 import os
 import sys
 
@@ -46,7 +47,7 @@ key = torch.empty(1, dtype=torch.int64, device="cuda")
 args = (xi, MPCR_LAYOUT_XI, q0, (20., 3., 80.), (-0.3, -0.3, 0.5), (0., 1., 0., 0.))
 entry, ctrl_mode = os.environ.get("ENTRY", "cost"), os.environ.get("CTRL", "none")
 geom_mode, target_mode = os.environ.get("GEOM", "none"), os.environ.get("TARGET", "none")
-slotw_mode = os.environ.get("SLOTW", "none")
+slotw_mode, stepw_mode = os.environ.get("SLOTW", "none"), os.environ.get("STEPW", "none")
 if entry == "state":
     par = torch.as_tensor(Engine.params(*args[2:])).cuda()
     ckw = {}
@@ -70,6 +71,9 @@ if entry == "state":
         ns4 = (e.nslot + 3) & ~3
         w = np.ones(ns4, np.float32) if slotw_mode == "ones" else np.tile(np.float32([0, 0.25, 1, 2]), ns4 // 4)
         ckw["slot_w"] = torch.as_tensor(w).cuda()
+    if stepw_mode != "none":
+        a = Engine.step_weights(H) if stepw_mode == "ones" else Engine.step_weights(H, discount=0.85, terminal=4)
+        ckw["step_w"] = torch.as_tensor(a).cuda()
 
     def run(theta=None, thetadot=None, best_key=None, status=None):
         e.rollout_cost_state(xi, MPCR_LAYOUT_XI, par, 1, c4, theta=theta, thetadot=thetadot, best_keys=best_key,
@@ -102,7 +106,8 @@ sv = st.cpu().numpy()
 rows = f" rows/step {float((sv >> 11).mean()) / H:.1f} max-rows p50/p90/p99 " + "/".join(
     str(int(np.percentile((sv >> 2) & 255, q))) for q in (50, 90, 99))
 tag = (f" {entry}/ctrl={ctrl_mode}/geom={geom_mode}/start={os.environ.get('START', '0')}/target={target_mode}"
-       + (f"/slotw={slotw_mode}" if slotw_mode != "none" else "") if entry == "state" else "")
+       + (f"/slotw={slotw_mode}" if slotw_mode != "none" else "")
+       + (f"/stepw={stepw_mode}" if stepw_mode != "none" else "") if entry == "state" else "")
 print(f"{os.path.basename(sys.argv[1])}{tag}{occ}{rows} {name} {n}x{H} median {np.median(ts):.3f} ms min {np.min(ts):.3f} "
       f"-> {n / np.median(ts) * 1e3:.0f} rollouts/s  cost0 {float(c4[:, 0].sum()):.6e}")
 if os.environ.get("SAVE"):  # outputs of the last launch, for bitwise comparisons between variants

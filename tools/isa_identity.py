@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Is the device code of two source trees the same?  A plain text diff.
 
-    python tools/isa_identity.py OLD_TREE NEW_TREE [--keep DIR] [-j N]
+    python tools/isa_identity.py OLD_TREE NEW_TREE [--keep DIR] [-j N] [--functions] [--strip-new TEXT]
 
 For each unit of build.UNITS (paired by position: engine, rollout, the
 dual-arm rollout) both trees' source is compiled to device-only assembly with
@@ -12,7 +12,11 @@ line.  Prints, per unit, `identical` or the first differing function and how
 many lines differ; exit status 1 on any difference.  With --functions a unit
 that differs is also broken down by function: which ones differ, and whether
 in integer literals alone (a changed struct size or field offset folded into
-an instruction) or in their instructions.  No GPU needed.
+an instruction) or in their instructions.  --strip-new TEXT drops TEXT from
+every line of the new tree's listings first: where the new tree lengthens a
+kernel's argument list, its mangled names gain a suffix (an argument of type
+mpcr::StepWArgs adds NS_9StepWArgsE) and the functions pair up again without
+it.  No GPU needed.
 """
 import argparse
 import importlib.util
@@ -45,11 +49,11 @@ def unit_cmds(b):
     return cmds
 
 
-def assembly(cmd, out):
-    """Compile, drop the __hip_cuid_ lines in place, return the lines."""
+def assembly(cmd, out, strip=None):
+    """Compile, drop the __hip_cuid_ lines (and every occurrence of `strip`) in place, return the lines."""
     subprocess.run(cmd + ["-o", out], check=True)
     with open(out) as f:
-        lines = [ln for ln in f if "__hip_cuid_" not in ln]
+        lines = [ln.replace(strip, "") if strip else ln for ln in f if "__hip_cuid_" not in ln]
     with open(out, "w") as f:
         f.writelines(lines)
     return lines
@@ -125,6 +129,8 @@ def main():
     ap.add_argument("-j", type=int, default=3, help="compiles in flight")
     ap.add_argument("--functions", action="store_true",
                     help="for a unit that differs, also say per function how: integer literals alone, or more")
+    ap.add_argument("--strip-new", metavar="TEXT",
+                    help="drop TEXT from the new tree's listings before comparing (a mangled-name suffix)")
     a = ap.parse_args()
     old, new = unit_cmds(load_build(a.old)), unit_cmds(load_build(a.new))
     if len(old) != len(new):
@@ -133,7 +139,7 @@ def main():
         d = a.keep or tmp
         os.makedirs(d, exist_ok=True)
         jobs = [(pool.submit(assembly, o[1], os.path.join(d, f"old{i}.s")),
-                 pool.submit(assembly, n[1], os.path.join(d, f"new{i}.s"))) for i, (o, n) in enumerate(zip(old, new))]
+                 pool.submit(assembly, n[1], os.path.join(d, f"new{i}.s"), a.strip_new)) for i, (o, n) in enumerate(zip(old, new))]
         bad = 0
         for i, ((o, n), (fo, fn)) in enumerate(zip(zip(old, new), jobs)):
             so, sn = fo.result(), fn.result()
